@@ -10,7 +10,14 @@ histogram/expansion, flow-error QC, hole filling) — nothing is skipped inside 
 Work per GPU is fixed as N grows (weak scaling: every GPU is an independent serving replica, the
 reference's scaling model — Ray Serve replicas, ``apps/model-runner/runtime_deployment.py:40-50``).
 
-After the timed inference steps, the same process measures (untimed for the headline):
+A plain run does only what the headline needs: set-up, warm-up, the K timed steps and the one JSON
+line (``ms_per_step`` = wall milliseconds of one timed step).  ``--dump-outputs DIR`` additionally
+writes what the last timed step returned (masks, flows, styles) as ``DIR/<name>.npy``; the inputs
+are seeded, so two builds run with the same arguments can be compared output for output.
+
+With ``--full``, after the timed inference steps, the same process measures (untimed for the headline):
+  * the same batches one ``eval()`` at a time (``imgs_per_sec_sequential_batches``) and whether the
+    pipelined masks equal the sequential ones,
   * p50 / p95 latency of single-image requests (batch 1, direct call),
   * ``imgs_per_sec_cell_like``: the same pipeline with cell-like network outputs (~150 masks per
     image), so the mask stage does realistic work,
@@ -24,7 +31,8 @@ and reports them as extra fields of the one JSON line rank 0 prints.
 
 The reference publishes no number for these metrics (BASELINE.md §2), so ``vs_baseline`` is null;
 ``vs_reference_algorithm`` is the speedup over the same pipeline with the network run by PyTorch
-eager bf16 (MIOpen) — the "reference-algorithm baseline" of BASELINE.md — measured in-process.
+eager bf16 (MIOpen) — the "reference-algorithm baseline" of BASELINE.md — measured in-process
+under ``--full``.
 """
 from __future__ import annotations
 
@@ -97,6 +105,31 @@ def _max_over_ranks(v: float, world: int) -> float:
     return float(t.item())
 
 
+DUMP_BUDGET_BYTES = 60 << 20  # all dumped arrays together stay under 64 MB
+
+
+def dump_outputs(out_dir, tensors: dict) -> None:
+    """Write each tensor as ``out_dir/<name>.npy`` (float32; float64 inputs stay float64).  The byte
+    budget is shared smallest-first; an output larger than its share is written as a fixed sample:
+    the flattened elements at sorted indices drawn without replacement by a generator seeded with 0,
+    so the same shape always yields the same positions."""
+    import numpy as np
+
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    left = DUMP_BUDGET_BYTES
+    todo = sorted(tensors.items(), key=lambda kv: kv[1].numel())
+    for i, (name, t) in enumerate(todo):
+        a = t.detach().cpu().numpy()
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32, copy=False)
+        share = left // (len(todo) - i) // a.itemsize
+        if a.size > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=share, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(out_dir / f"{name}.npy", a)
+        left -= a.nbytes
+
+
 def bench_infer(args, world, rank, dev):
     from bioengine_worker_amd.cellpose.pipeline import CellposeRunner, EvalParams, synthetic_cells
 
@@ -111,7 +144,7 @@ def bench_infer(args, world, rank, dev):
         _barrier(world)
         t0 = time.perf_counter()
         for _ in range(args.steps):
-            masks, flows, _ = runner.eval(imgs, p)
+            masks, flows, styles = runner.eval(imgs, p)
         _barrier(world)
         dt = time.perf_counter() - t0
     else:
@@ -126,19 +159,22 @@ def bench_infer(args, world, rank, dev):
         t0 = time.perf_counter()
         for _ in range(args.steps):
             st.submit(imgs)
-        masks, flows, _ = st.flush()
+        masks, flows, styles = st.flush()
         _barrier(world)
         dt = time.perf_counter() - t0
-        # the same batches one eval() at a time (no overlap between consecutive batches)
-        _barrier(world)
-        t1 = time.perf_counter()
-        for _ in range(args.steps):
-            m1, _, _ = runner.eval(imgs, p)
-        _barrier(world)
-        dt_seq = _max_over_ranks(time.perf_counter() - t1, world)
-        extra["imgs_per_sec_sequential_batches"] = round(args.batch * args.steps * world / dt_seq, 2)
-        extra["pipelined_masks_match_sequential"] = bool(torch.equal(m1, masks))
+        if args.full:
+            # the same batches one eval() at a time (no overlap between consecutive batches)
+            _barrier(world)
+            t1 = time.perf_counter()
+            for _ in range(args.steps):
+                m1, _, _ = runner.eval(imgs, p)
+            _barrier(world)
+            dt_seq = _max_over_ranks(time.perf_counter() - t1, world)
+            extra["imgs_per_sec_sequential_batches"] = round(args.batch * args.steps * world / dt_seq, 2)
+            extra["pipelined_masks_match_sequential"] = bool(torch.equal(m1, masks))
     dt = _max_over_ranks(dt, world)
+    if args.dump_outputs and rank == 0:  # outside the timed region
+        dump_outputs(args.dump_outputs, {"masks": masks, "flows": flows, "styles": styles})
     extra.update({"masks_per_image": float(masks.amax(dim=(1, 2)).float().mean().item()),
                   "fg_fraction": float((flows[:, 2] > 0).float().mean().item())})
     if getattr(args, "trace", None) and rank == 0:  # outside the timed region
@@ -676,7 +712,12 @@ def main():
     ap.add_argument("--train-steps", type=int, default=30, help="timed steps of each fine-tune line (10 read +-10 %% apart across runs)")
     ap.add_argument("--chunks", type=int, default=1, help="micro-batches of the two-stream net/mask pipeline")
     ap.add_argument("--sequential", action="store_true", help="headline: one eval() per step, no cross-batch overlap")
-    ap.add_argument("--no-extras", action="store_true", help="skip latency / train / reference-algorithm extras")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also measure the extras: sequential batches, latency, reference "
+                         "algorithm, mask recovery, served stack, ViT, fine-tune, EM volumes, CPU model-runner")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's masks / flows / styles as DIR/<name>.npy (rank 0)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip latency / train / reference-algorithm extras")
     ap.add_argument("--no-served", action="store_true", help="skip the served (full worker stack) measurement")
     ap.add_argument("--served-seconds", type=float, default=4.0, help="seconds per served concurrency level")
     ap.add_argument("--cpsam-batch", type=int, default=8, help="256x256 crops per step per GPU (Cellpose-SAM)")
@@ -728,7 +769,7 @@ def main():
         },
     }
     out.update(extra)
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         _progress("latency / reference algorithm / masks", rank)
         try:
             if rank == 0:
@@ -853,7 +894,7 @@ def main():
                             "*_bf16: torch.autocast bf16"}
             except Exception as e:  # noqa: BLE001
                 out["extras_error_train_autograd"] = f"{type(e).__name__}: {e}"
-    if world > 1 and not args.no_extras and not args.no_served:
+    if world > 1 and args.full and not args.no_extras and not args.no_served:
         _progress("served node", rank)
         out.update(bench_served_node(args, world, rank))
     if rank == 0:

@@ -365,6 +365,9 @@ class ProcessReplica(ReplicaBase):
     def __init__(self, *a, log_dir: str | Path | None = None, python: str | None = None, **k):
         super().__init__(*a, **k)
         self.log_dir = Path(log_dir or tempfile.gettempdir()) / "bioengine_replicas"
+        if self.log_dir.exists() and not os.access(self.log_dir, os.W_OK | os.X_OK):
+            # a shared temp directory where another user's worker created the folder first
+            self.log_dir = self.log_dir.with_name(f"bioengine_replicas-{os.getuid()}")
         self.log_dir.mkdir(parents=True, exist_ok=True)
         self.log_file = self.log_dir / f"{self.tag.replace('#', '_')}.log"
         self.python = python or sys.executable

@@ -1,8 +1,9 @@
 """Cellpose fine-tuning app end-to-end through the worker, offline (the reference's app tests need a
 live Hypha server, Ray and pretrained weights).
 
-* The reference's own offline fixtures (``tests/apps/cellpose/test_metadata_and_glob.py``) run
-  unmodified against this app's ``main.py`` when the reference tree is present.
+* The inputs and expected results of the reference's own offline fixtures
+  (``tests/apps/cellpose/test_metadata_and_glob.py``), kept as data under ``tests/golden/``, run
+  against this app's ``main.py``.
 * A dataset artifact with a nested glob layout is created on the in-process hub; ``start_training``
   (reference signature, default model ``cpsam``) pairs, downloads and trains; the session is used
   for inference, restarted from disk, and exported as a committed BioImage.IO model artifact.
@@ -12,8 +13,8 @@ Runs on CPU with a tiny Cellpose-SAM encoder; the HIP paths are covered by the G
 """
 import asyncio
 import importlib.util
-import inspect
 import io
+import json
 import sys
 from pathlib import Path
 
@@ -27,7 +28,7 @@ from bioengine_worker_amd.worker.worker import BioEngineWorker
 
 ROOT = Path(__file__).resolve().parents[1]
 APP_MAIN = ROOT / "apps" / "cellpose-finetuning" / "main.py"
-REF_TEST = Path("/root/reference/tests/apps/cellpose/test_metadata_and_glob.py")
+PAIRING_CASES = ROOT / "tests" / "golden" / "cellpose_pairing.json"
 
 
 def _load_app_module():
@@ -40,24 +41,52 @@ def _load_app_module():
     return mod
 
 
-@pytest.mark.unit
-@pytest.mark.skipif(not REF_TEST.exists(), reason="reference tree not present")
-def test_reference_pairing_fixtures_pass(tmp_path):
-    """Execute the reference's test module with its ``_main_path`` pointed at this app."""
-    from bioengine_worker_amd.compat import install
+class _DictArtifact:
+    """Dataset artifact backed by a fixture case: ``folders`` maps a folder (with trailing slash) to
+    the file paths it lists, ``documents`` maps a path to the JSON document stored there; every
+    other downloaded file gets placeholder bytes."""
 
-    install()
-    src = REF_TEST.read_text()
-    src = src.replace('Path(__file__).parents[3] / "apps" / "cellpose-finetuning" / "main.py"', repr(str(APP_MAIN)))
-    ns = {"__name__": "ref_cellpose_pairing", "__file__": str(REF_TEST)}
-    exec(compile(src, str(REF_TEST), "exec"), ns)  # noqa: S102 - test fixture code, no I/O beyond tmp_path
-    tests = [(k, v) for k, v in ns.items() if k.startswith("test_") and callable(v)]
-    assert len(tests) >= 5
-    for i, (name, fn) in enumerate(tests):
-        kw = {"tmp_path": tmp_path / str(i)} if "tmp_path" in inspect.signature(fn).parameters else {}
-        if kw:
-            kw["tmp_path"].mkdir()
-        fn(**kw)
+    def __init__(self, folders, documents=None):
+        self.folders, self.documents = folders, documents or {}
+
+    async def ls(self, folder_path):
+        return [{"path": p, "type": "file"} for p in self.folders.get(folder_path.rstrip("/") + "/", [])]
+
+    async def get(self, remote_paths, local_paths, on_error="ignore"):
+        for remote, local in zip(remote_paths, local_paths):
+            local = Path(local)
+            local.parent.mkdir(parents=True, exist_ok=True)
+            doc = self.documents.get(str(remote).lstrip("/"))
+            local.write_bytes(b"placeholder" if doc is None else json.dumps(doc, indent=2).encode())
+
+
+@pytest.mark.unit
+def test_reference_pairing_fixtures_pass(tmp_path):
+    """The reference app's offline pairing fixtures (nested globs, mixed ``.ome.tif`` suffixes, a
+    folder pattern without trailing slash, flat and nested metadata records), stored as data in
+    ``tests/golden/cellpose_pairing.json``, against this app's ``main.py``."""
+    m = _load_app_module()
+    cases = json.loads(PAIRING_CASES.read_text())
+    assert len(cases["pairing"]) + len(cases["listing"]) + len(cases["metadata"]) >= 5
+    for c in cases["pairing"]:
+        pairs = m.match_image_annotation_pairs(c["images"], c["annotations"], c["image_pattern"],
+                                               c["annotation_pattern"])
+        assert pairs == [tuple(p) for p in c["pairs"]], c["name"]
+    for c in cases["listing"]:
+        got = asyncio.run(m.list_matching_artifact_paths(_DictArtifact(c["folders"]), c["pattern"]))
+        assert got == c["matches"], c["name"]
+    for c in cases["metadata"]:
+        save = tmp_path / c["name"]
+        save.mkdir()
+        train, test = asyncio.run(m.make_training_pairs_from_metadata(
+            artifact=_DictArtifact(c["folders"], c["documents"]), metadata_dir="metadata/", save_path=save,
+            n_samples=None))
+        for got, want in ((train, c["train"]), (test, c["test"])):
+            assert len(got) == len(want), c["name"]
+            for pair, (img, ann) in zip(got, want):
+                assert pair["image"].exists() and pair["annotation"].exists(), c["name"]
+                assert pair["image"].as_posix().endswith(img), c["name"]
+                assert pair["annotation"].as_posix().endswith(ann), c["name"]
 
 
 @pytest.mark.unit

@@ -21,6 +21,12 @@ def test_em_app_e2e(tmp_path, monkeypatch):
     monkeypatch.setenv("HOME", str(tmp_path / "home"))
     monkeypatch.delenv("BIOENGINE_MODEL_ZOO", raising=False)
     monkeypatch.setenv("BIOENGINE_EM_DATA_ROOT", str(tmp_path / "emdata"))
+    # the worker below has no GPUs, so its gangs are gloo ranks on the CPU; keep the app's in-process
+    # pipeline (local replica mode) on the CPU too when the box happens to have a GPU, so that the
+    # single-process and the sharded labels compared below come from the same code path
+    import torch
+
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: False)
     reset_local_hubs()
 
     async def main():

@@ -61,17 +61,17 @@ def test_model_runner_e2e(tmp_path, monkeypatch):
         rep2 = await app.test(model_id="tiny-unet")  # served from the cached report
         assert rep2 == rep
         x = np.load(zoo / "tiny-unet" / "test_input.npy")
-        out = await app.infer(model_id="tiny-unet", inputs=x)
+        out = await app.infer(model_id="tiny-unet", device="cpu", inputs=x)
         ref = np.load(zoo / "tiny-unet" / "test_output.npy")
         assert np.abs(out["probabilities"] - ref).max() < 1e-4
-        out2 = await app.infer(model_id="tiny-unet", inputs=x[0, 0, :80, :72], default_blocksize_parameter=0)
+        out2 = await app.infer(model_id="tiny-unet", device="cpu", inputs=x[0, 0, :80, :72], default_blocksize_parameter=0)
         assert out2["probabilities"].shape == (1, 2, 80, 72)
         with pytest.raises(Exception):
-            await app.infer(model_id="no-such-model", inputs=x)
+            await app.infer(model_id="no-such-model", device="cpu", inputs=x)
         # ONNX-only package: own graph executor (no onnxruntime), test + infer through the app
         assert (await app.test(model_id="tiny-onnx"))["status"] == "passed"
         xo = np.load(zoo / "tiny-onnx" / "test_input.npy")
-        outo = await app.infer(model_id="tiny-onnx", inputs=xo, weights_format="onnx")
+        outo = await app.infer(model_id="tiny-onnx", device="cpu", inputs=xo, weights_format="onnx")
         assert np.abs(outo["probabilities"] - np.load(zoo / "tiny-onnx" / "test_output.npy")).max() < 1e-4
         await svc.stop_worker(blocking=True)
         await admin.disconnect()

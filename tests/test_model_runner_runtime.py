@@ -86,13 +86,13 @@ def test_model_runner_runtime_batching_health_and_requirements(tmp_path, monkeyp
         x = np.load(zoo / "tiny-unet" / "test_input.npy")
         ref = np.load(zoo / "tiny-unet" / "test_output.npy")
         assert (await app.test(model_id="tiny-unet"))["status"] == "passed"  # report cached from here on
-        await app.infer(model_id="tiny-unet", inputs=x)  # pipeline loaded
+        await app.infer(model_id="tiny-unet", device="cpu", inputs=x)  # pipeline loaded
 
         # ---- concurrent same-model requests while the device is busy: batched, loop stays live
         slow["on"] = True
         scales = [1.0, 0.5, 2.0, 1.5]
         t0 = time.perf_counter()
-        reqs = [asyncio.ensure_future(app.infer(model_id="tiny-unet", inputs=(x * s).astype(x.dtype)))
+        reqs = [asyncio.ensure_future(app.infer(model_id="tiny-unet", device="cpu", inputs=(x * s).astype(x.dtype)))
                 for s in scales]
         await asyncio.sleep(0.15)
         t = time.perf_counter()
@@ -106,7 +106,7 @@ def test_model_runner_runtime_batching_health_and_requirements(tmp_path, monkeyp
         assert sum(slow["batches"]) == 4 and max(slow["batches"]) >= 2 and len(slow["batches"]) < 4, slow["batches"]
         np.testing.assert_allclose(outs[0]["probabilities"], ref, atol=1e-4)
         for s, o in zip(scales, outs):  # batched forwards return each request's own result
-            solo = await app.infer(model_id="tiny-unet", inputs=(x * s).astype(x.dtype))
+            solo = await app.infer(model_id="tiny-unet", device="cpu", inputs=(x * s).astype(x.dtype))
             np.testing.assert_allclose(o["probabilities"], solo["probabilities"], atol=1e-5)
 
         # ---- additional_requirements: isolated test task with a wheelhouse-installed extra package

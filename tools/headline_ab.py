@@ -20,6 +20,7 @@ def main():
     ap.add_argument("--batch", type=int, default=32)
     a = ap.parse_args()
     a.chunks, a.sequential, a.trace = 1, False, None
+    a.full, a.dump_outputs = True, None  # full: the sequential rate next to the pipelined one
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
     dt, runner, imgs, p, extra = bench.bench_infer(a, 1, 0, dev)
