@@ -442,8 +442,13 @@ class CellposeFinetune:
         return_flows: bool = Field(False, description="Also return [RGB flow, dY/dX flows, cell probability]."),
         json_safe: bool = Field(False, description="Masks as PNG overlay payloads instead of arrays."),
         enable_clahe: bool = Field(False, description="CLAHE pre-processing (brightfield / phase contrast)."),
+        stitch_threshold: float = Field(0.0, ge=0, le=1, description="z-stacks: join masks of adjacent planes whose "
+                                                                     "IoU is at least this into 3-D labels (0 = off)."),
+        z_axis: int | None = Field(None, description="z-stacks: axis of the planes in each input array (default 0 "
+                                                     "when stitch_threshold > 0)."),
     ) -> list:
-        """Segment images; returns one {input_path, output(, flows)} per image."""
+        """Segment images; returns one {input_path, output(, flows)} per image.  With ``z_axis`` or
+        ``stitch_threshold > 0`` every input array is one z-stack and ``output`` is [Z, H, W]."""
         if isinstance(artifact, dict):
             w = artifact
             artifact = w.get("artifact", w.get("artifact_id", w.get("id")))
@@ -453,6 +458,11 @@ class CellposeFinetune:
             cellprob_threshold = w.get("cellprob_threshold", cellprob_threshold)
             niter, return_flows = w.get("niter", niter), w.get("return_flows", return_flows)
             json_safe, enable_clahe = w.get("json_safe", json_safe), w.get("enable_clahe", enable_clahe)
+            stitch_threshold, z_axis = w.get("stitch_threshold", stitch_threshold), w.get("z_axis", z_axis)
+        stitch_threshold = float(_opt(stitch_threshold) or 0.0)
+        z_axis = _opt(z_axis)
+        if not 0.0 <= stitch_threshold <= 1.0:
+            raise ValueError(f"stitch_threshold must be in [0, 1], got {stitch_threshold}")
         model = _opt(model) or self.default_model
         model_id = await self.resolve_model_id(model)
         if _opt(input_arrays) is not None:
@@ -463,11 +473,20 @@ class CellposeFinetune:
             images = await self._images_from_artifact(artifact, names)
         else:
             raise ValueError("Provide input_arrays or artifact + image_paths")
+        stack_mode = z_axis is not None or stitch_threshold > 0
         if enable_clahe:
+            if stack_mode:
+                raise ValueError("enable_clahe is not supported for z-stacks (z_axis / stitch_threshold)")
             images = [clahe_image(im, self._device()) for im in images]
         runner = await self._runner(model_id)
         prm = {"diameter": _opt(diameter), "flow_threshold": float(flow_threshold),
                "cellprob_threshold": float(cellprob_threshold), "niter": int(_opt(niter) or 200)}
+        if stack_mode:
+            out = await self._infer_stacks(runner, names, images, prm, stitch_threshold, int(z_axis or 0),
+                                           bool(return_flows), bool(json_safe))
+            if self._weights.get(model_id) == "random" and out:
+                out[0]["weights"] = "random"
+            return out
         on_gpu = str(getattr(runner, "device", "cpu")).startswith("cuda")
         chw = [image_for_batch(im, runner.nchan, on_gpu) for im in images]
         with trace.span("app.batched", images=len(chw)):
@@ -484,6 +503,39 @@ class CellposeFinetune:
             out.append(item)
         if self._weights.get(model_id) == "random" and out:
             out[0]["weights"] = "random"
+        return out
+
+    async def _infer_stacks(self, runner, names: list, stacks: list, prm: dict, stitch_threshold: float, z_axis: int,
+                            return_flows: bool, json_safe: bool) -> list:
+        """Stack mode of :meth:`infer`: every array is one z-stack ([Z,H,W], [Z,C,H,W] or [Z,H,W,C] once
+        ``z_axis`` is moved to the front); its planes are one batch of ``runner.eval_stack`` (no
+        continuous batching across requests), stitched on the device."""
+        out = []
+        for name, a in zip(names, stacks):
+            a = np.asarray(a)
+            if a.ndim < 3:
+                raise ValueError(f"{name}: stack mode (z_axis / stitch_threshold) needs a z-stack of at least 3 "
+                                 f"dimensions, got shape {a.shape}")
+            if not -a.ndim <= z_axis < a.ndim:
+                raise ValueError(f"{name}: z_axis {z_axis} out of range for shape {a.shape}")
+            a = np.ascontiguousarray(np.moveaxis(a, z_axis, 0))
+            if a.dtype not in (np.uint8, np.uint16, np.float16, np.float32):
+                a = a.astype(np.float32)
+
+            def run(a=a):
+                with self._gpu_lock:
+                    m, f, _ = runner.eval_stack(a, stitch_threshold=stitch_threshold, **prm)
+                    m = m.cpu().numpy()
+                    return m, (f.cpu().numpy() if return_flows else None)
+
+            with trace.span("app.stack_eval", planes=int(a.shape[0])):
+                m, f = await offload(run)
+            m = m.astype(np.uint16) if int(m.max(initial=0)) < 65536 else m.astype(np.int32)
+            item = {"input_path": name, "output": [mask_png_payload(pl) for pl in m] if json_safe else m}
+            if return_flows:
+                fl = [np.stack([flow_rgb(y[:2]) for y in f]), f[:, :2], f[:, 2]]
+                item["flows"] = [x.tolist() for x in fl] if json_safe else fl
+            out.append(item)
         return out
 
     # ------------------------------------------------------------------ training

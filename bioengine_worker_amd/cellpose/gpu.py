@@ -1,6 +1,6 @@
 """GPU (HIP) implementation of Cellpose pre/post-processing on batches of images.
 
-Every heavy step is a kernel in ``csrc/kernels/{tiles,cellpose_dynamics,cellpose_masks}.hip``;
+Every heavy step is a kernel in ``csrc/kernels/{tiles,cellpose_dynamics,cellpose_masks,cellpose_stitch}.hip``;
 torch is only used for tiny bookkeeping (sorting the seed keys, prefix sums over labels, building
 per-mask job lists).  The semantics are those of :mod:`bioengine_worker_amd.cellpose.reference`
 (the CPU oracle), which the GPU tests compare against.
@@ -609,3 +609,78 @@ def compute_masks_gpu(y: torch.Tensor, niter: int = 200, cellprob_threshold: flo
         M = torch.gather(qc_keep.to(torch.int32), 1, M.reshape(M.shape[0], -1).long()).reshape(M.shape) * M
         fill_keep &= qc_keep
     return _fill_run(M.contiguous(), _rank_lut(fill_keep), nlab, plans[-1])
+
+
+# ------------------------------------------------------------------ z-stacks
+
+
+def _stitch_capacity(nlab: int, HW: int) -> int:
+    """Hash slots per plane pair.  A label of plane z overlaps a handful of labels of plane z-1 (its
+    own continuation plus the neighbours it grazes), so 8 slots per possible label keep the load
+    factor under ~1/2; never below 1024, and never above the first power of two >= 2 * H * W (a
+    pair has at most H * W distinct overlaps, so that size cannot overflow).  Always a power of two."""
+    cap = 1 << max(10, (8 * max(nlab, 1) - 1).bit_length())
+    return min(cap, 1 << max(1, (2 * HW - 1).bit_length()))
+
+
+def stitch3d_gpu(M: torch.Tensor, stitch_threshold: float = 0.25, min_size: int = 0, nlab: int | None = None,
+                 capacity: int | None = None) -> torch.Tensor:
+    """Stitch per-plane label images M [Z, H, W] int32 into volumetric labels ``1..K`` (same shape and
+    dtype): HIP implementation of :func:`reference.stitch3d` (``csrc/kernels/cellpose_stitch.hip``),
+    exactly equal to it.  ``nlab``: optional upper bound on the labels + 1 (saves the ``M.max()``
+    sync; it must be a true bound, the per-label tables are sized by it); ``capacity``: hash slots per plane pair, a power of two (default :func:`_stitch_capacity`).
+    One host read (the overflow word of the overlap launch; a set word re-runs that launch with twice
+    the capacity).  CPU tensors run the oracle."""
+    if M.dim() != 3:
+        raise ValueError(f"stitch3d_gpu expects [Z, H, W] masks, got shape {tuple(M.shape)}")
+    if M.device.type != "cuda":
+        out = ref.stitch3d(M.numpy(), stitch_threshold, min_size)
+        return torch.from_numpy(out).to(M.dtype)
+    if M.dtype != torch.int32:
+        raise TypeError(f"stitch3d_gpu expects int32 masks, got {M.dtype}")
+    Z, H, W = M.shape
+    HW = H * W
+    dev = M.device
+    if Z == 0 or HW == 0:
+        return torch.zeros_like(M)
+    if HW >= 2 ** 31:
+        raise ValueError("stitch3d_gpu: planes of 2^31 pixels or more are not supported")
+    if nlab is None:
+        nlab = int(M.max().item()) + 1
+    nlab = max(int(nlab), 1)
+    Mc = M.contiguous()
+    st = _native.stream(dev)
+    counts = label_counts(Mc, nlab)
+    n = Z * nlab
+    # one zero-filled block: bestA, bestB, vol (64-bit), then owner, link (32-bit) and the two flag words
+    ws = torch.zeros(2 * n + (n + 1) + n + 1, dtype=torch.int64, device=dev)
+    best_a, best_b, vol = ws[:n], ws[n: 2 * n], ws[2 * n: 3 * n + 1]
+    w32 = ws[3 * n + 1:].view(torch.int32)
+    owner, link, flags = w32[:n], w32[n: 2 * n], w32[2 * n: 2 * n + 2]
+    if Z > 1 and nlab > 1:
+        max_cap = 1 << max(1, (2 * HW - 1).bit_length())
+        cap = _stitch_capacity(nlab, HW) if capacity is None else int(capacity)
+        if cap < 1 or cap & (cap - 1):
+            raise ValueError("capacity must be a power of two")
+        while True:
+            keys = torch.zeros(Z - 1, cap, dtype=torch.int64, device=dev)
+            vals = torch.zeros(Z - 1, cap, dtype=torch.int32, device=dev)
+            _native.call("be_cp_stitch_overlap", _native.ptr(Mc), Z, HW, nlab, _native.ptr(keys), _native.ptr(vals), cap,
+                         _native.ptr(flags), st)
+            if int(flags[0].item()) == 0:  # host read: did every increment find a slot?
+                break
+            if cap >= max_cap:
+                raise RuntimeError("stitch3d_gpu: overlap table overflowed at its maximum size")
+            cap *= 2  # sizing retry of a launch that completed normally; bounded by the pixel count
+            flags[0] = 0
+        _native.call("be_cp_stitch_match", _native.ptr(keys), _native.ptr(vals), Z, cap, _native.ptr(counts), nlab,
+                     float(stitch_threshold), _native.ptr(best_a), _native.ptr(owner), _native.ptr(best_b),
+                     _native.ptr(link), st)
+    gid = torch.empty(Z, nlab, dtype=torch.int32, device=dev)
+    lut = torch.empty(n + 1, dtype=torch.int32, device=dev)
+    _native.call("be_cp_stitch_number", _native.ptr(counts), _native.ptr(link), Z, nlab, int(min_size), _native.ptr(gid),
+                 _native.ptr(vol), _native.ptr(lut), _native.ptr(flags), st)
+    out = torch.empty_like(Mc)
+    _native.call("be_cp_stitch_relabel", _native.ptr(Mc), Z, HW, nlab, _native.ptr(gid), _native.ptr(lut), _native.ptr(out),
+                 st)
+    return out

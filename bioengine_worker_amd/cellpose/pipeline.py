@@ -11,6 +11,7 @@ CPU path: the numpy/torch oracle (:mod:`.reference`) — used by CPU tests and C
 """
 from __future__ import annotations
 
+import dataclasses
 import math
 import os
 from dataclasses import dataclass
@@ -44,6 +45,13 @@ class EvalParams:
     pipeline_chunks: int = 1  # measured: 2 -> -9 %, 4 -> -18 % (latency-bound mask stages run once per chunk)
     pipeline_min_chunk: int = 4
     max_tiles: int = 0  # network tiles per launch (0 = sized to free HBM, CellposeRunner.tile_budget)
+    # ---- z-stacks (CellposeRunner.eval_stack only; eval() ignores these)
+    #: join masks of adjacent planes whose IoU is at least this (0 = return the per-plane masks)
+    stitch_threshold: float = 0.0
+    #: percentiles over the whole stack instead of per plane.  The library's default for this switch
+    #: could not be checked offline; True follows its documented stitching behaviour.
+    norm3d: bool = True
+    stack_batch: int = 32  # planes per eval() call
 
 
 def as_batch(images, nchan: int, device=None) -> torch.Tensor:
@@ -222,6 +230,58 @@ class CellposeRunner:
         if self.device.type == "cuda" and p.compute_masks and nch >= 2:
             return self._eval_pipelined(x, p, nch)
         return self._eval_one(x, p)
+
+    @torch.no_grad()
+    def eval_stack(self, stack, p: EvalParams | None = None, **kw):
+        """Segment a z-stack plane by plane and stitch the masks of adjacent planes into volumetric
+        labels (cellpose ``eval(..., stitch_threshold=t)``; semantics in :func:`reference.stitch3d`).
+
+        ``stack``: [Z, H, W], [Z, C, H, W] or [Z, H, W, C], numpy or torch.  Returns
+        ``(masks [Z, H, W] int32, flows [Z, 3, H, W] fp32, styles [Z, S])``.  With ``p.normalize and
+        p.norm3d`` the percentiles are taken per channel over the whole stack; the planes then run
+        through :meth:`eval` in chunks of ``p.stack_batch``.  ``p.stitch_threshold == 0`` returns the
+        per-plane masks unstitched."""
+        p = dataclasses.replace(p) if p is not None else EvalParams()
+        for k, v in kw.items():
+            setattr(p, k, v)
+        x = torch.as_tensor(np.asarray(stack) if not torch.is_tensor(stack) else stack)
+        if x.dim() == 3:
+            x = x[:, None]
+        elif x.dim() == 4:
+            if x.shape[-1] <= 4 and x.shape[1] > 4:  # channel-last, as as_batch decides for one image
+                x = x.permute(0, 3, 1, 2)
+        else:
+            raise ValueError(f"eval_stack expects [Z,H,W], [Z,C,H,W] or [Z,H,W,C], got shape {tuple(x.shape)}")
+        x = as_batch(x, self.nchan, self.device)
+        Z, C, H, W = x.shape
+        if Z == 0:
+            raise ValueError("eval_stack: empty stack")
+        pp = dataclasses.replace(p)
+        if p.normalize and p.norm3d:
+            with trace.span("cellpose.normalize99", cuda=self.device.type == "cuda", images=Z):
+                xs = x.permute(1, 0, 2, 3).reshape(1, C, Z * H, W)
+                x = self._normalize(xs).reshape(C, Z, H, W).permute(1, 0, 2, 3).contiguous()
+            pp.normalize = False
+        masks, flows, styles = [], [], []
+        step = max(1, int(p.stack_batch))
+        for i in range(0, Z, step):
+            m, y, s = self.eval(x[i: i + step], dataclasses.replace(pp))
+            masks.append(m)
+            flows.append(y)
+            styles.append(s)
+        flows, styles = torch.cat(flows), torch.cat(styles)
+        if not p.compute_masks:
+            return None, flows, styles
+        M = torch.cat(masks)
+        if p.stitch_threshold > 0:
+            with trace.span("cellpose.stitch3d", cuda=M.is_cuda, planes=Z):
+                if M.is_cuda:
+                    from .gpu import stitch3d_gpu
+
+                    M = stitch3d_gpu(M.to(torch.int32), p.stitch_threshold, min_size=p.min_size)
+                else:
+                    M = torch.from_numpy(ref.stitch3d(M.numpy(), p.stitch_threshold, min_size=p.min_size))
+        return M, flows, styles
 
     def _stage(self, images):
         """numpy batch -> view of a reusable pinned host buffer, so the H2D copy is one DMA at full

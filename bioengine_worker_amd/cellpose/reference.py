@@ -17,6 +17,7 @@ get_masks        histogram of end points -> 5x5 max seeds (count > 10) -> 5x 3x3
 masks_to_flows   per-mask heat diffusion from the median-nearest pixel, gradient of log(1 + T)
 flow QC          mean squared error between mask flows and dP/5 per mask; drop masks above threshold
 fill_holes       drop masks smaller than min_size, fill holes, renumber
+stitch3d         z-stacks: join the masks of adjacent planes by exact mutual-best IoU into 3-D labels
 """
 from __future__ import annotations
 
@@ -251,3 +252,90 @@ def compute_masks(dP, cellprob, niter=200, cellprob_threshold=0.0, flow_threshol
     if mask.max() > 0 and flow_threshold is not None and flow_threshold > 0:
         mask = remove_bad_flow_masks(mask, dP, flow_threshold)
     return fill_holes_and_remove_small_masks(mask, min_size)
+
+
+# ------------------------------------------------------------------ z-stacks: stitch 2-D masks into 3-D labels
+
+
+def stitch3d(masks: np.ndarray, stitch_threshold: float = 0.25, min_size: int = 0) -> np.ndarray:
+    """Join per-plane label images ``masks`` [Z, H, W] (0 = background, labels of different planes
+    unrelated, gaps allowed) into volumetric labels, int32 [Z, H, W] numbered ``1..K``.
+
+    For adjacent planes ``z-1``, ``z``: ``ov(b, a)`` common pixels of label ``b`` (plane ``z``) and
+    ``a`` (plane ``z-1``), ``u = A[b] + A_prev[a] - ov``, IoU the rational ``ov / u``.
+
+    * candidate: ``ov > 0`` and ``float64(ov) >= float64(stitch_threshold) * float64(u)`` (equality links);
+    * owner: every ``a`` is owned by its candidate ``b`` of largest IoU, ratios compared exactly by
+      integer cross-multiplication, the smaller ``b`` on equal ratios;
+    * link: every ``b`` links to the ``a`` it owns of largest IoU, the smaller ``a`` on equal ratios;
+      a ``b`` that owns nothing starts a new instance;
+    * global ids in order of plane, then ascending local label: a linked label takes its link's id,
+      any other label with pixels the next unused id;
+    * ``min_size > 0`` drops instances of fewer voxels over the whole stack;
+    * the result is numbered ``1..K`` in order of first appearance (plane, then local label).
+
+    This is the mutual-best rule of cellpose's ``utils.stitch3D`` (threshold, best row per column,
+    argmax per row) with two deliberate departures: on an exact IoU tie the library lets two masks
+    take one id, here the smaller label wins and the other starts a new instance; and across empty
+    leading planes the library can hand out ids that are already taken, here an unlinked label
+    always gets a fresh id."""
+    M = np.asarray(masks)
+    if M.ndim != 3:
+        raise ValueError(f"stitch3d expects [Z, H, W] masks, got shape {M.shape}")
+    Z = M.shape[0]
+    thr = float(stitch_threshold)
+    planes = []  # per plane: (labels ascending, dense index image, areas)
+    gids: list[np.ndarray] = []
+    vol = [0]  # voxels per global id (index 0 unused)
+    for z in range(Z):
+        cur = M[z].ravel()
+        labs, inv = np.unique(cur, return_inverse=True)
+        inv = inv.ravel()
+        area = np.bincount(inv, minlength=labs.size)
+        fg = labs > 0
+        link = {}
+        if z > 0 and fg.any():
+            plabs, pinv, parea, pgid = planes[-1]
+            both = (cur > 0) & (M[z - 1].ravel() > 0)
+            if both.any():
+                pk, ov = np.unique(inv[both].astype(np.int64) * plabs.size + pinv[both], return_counts=True)
+                best_a: dict = {}  # a -> (ov, u, b): the owner so far
+                cand = []
+                for k, o in zip(pk.tolist(), ov.tolist()):
+                    bi, ai = divmod(k, plabs.size)
+                    u = int(area[bi]) + int(parea[ai]) - o
+                    if not (o > 0 and float(o) >= thr * float(u)):
+                        continue
+                    cand.append((bi, ai, o, u))
+                    cur_best = best_a.get(ai)
+                    # pairs come in ascending b, so a strict improvement keeps the smaller b on ties
+                    if cur_best is None or o * cur_best[1] > cur_best[0] * u:
+                        best_a[ai] = (o, u, bi)
+                best_b: dict = {}  # b -> (ov, u, a)
+                for bi, ai, o, u in cand:  # ascending (b, a): strict improvement keeps the smaller a
+                    if best_a[ai][2] != bi:
+                        continue
+                    cur_best = best_b.get(bi)
+                    if cur_best is None or o * cur_best[1] > cur_best[0] * u:
+                        best_b[bi] = (o, u, ai)
+                link = {bi: v[2] for bi, v in best_b.items()}
+        gid = np.zeros(labs.size, np.int64)
+        for bi in range(labs.size):
+            if not fg[bi]:
+                continue
+            if bi in link:
+                gid[bi] = planes[-1][3][link[bi]]
+            else:
+                gid[bi] = len(vol)
+                vol.append(0)
+            vol[gid[bi]] += int(area[bi])
+        planes.append((labs, inv, area, gid))
+        gids.append(gid[inv].reshape(M.shape[1:]))
+    volume = np.asarray(vol, np.int64)
+    keep = volume > 0
+    if min_size > 0:
+        keep &= volume >= int(min_size)
+    lut = (np.cumsum(keep) * keep).astype(np.int32)
+    if Z == 0:
+        return np.zeros(M.shape, np.int32)
+    return lut[np.stack(gids)]
