@@ -445,10 +445,17 @@ class CellposeFinetune:
         stitch_threshold: float = Field(0.0, ge=0, le=1, description="z-stacks: join masks of adjacent planes whose "
                                                                      "IoU is at least this into 3-D labels (0 = off)."),
         z_axis: int | None = Field(None, description="z-stacks: axis of the planes in each input array (default 0 "
-                                                     "when stitch_threshold > 0)."),
+                                                     "when stitch_threshold > 0 or do_3D)."),
+        do_3D: bool = Field(False, description="z-stacks: volumetric segmentation -- the network runs on the YX, ZX "
+                                               "and ZY planes and the flows are followed in 3-D (flow_threshold is "
+                                               "unused; not with stitch_threshold > 0)."),
+        anisotropy: float | None = Field(None, description="do_3D: z spacing / xy spacing; the volume is resampled "
+                                                           "along z by this factor before the views run."),
     ) -> list:
-        """Segment images; returns one {input_path, output(, flows)} per image.  With ``z_axis`` or
-        ``stitch_threshold > 0`` every input array is one z-stack and ``output`` is [Z, H, W]."""
+        """Segment images; returns one {input_path, output(, flows)} per image.  With ``z_axis``,
+        ``stitch_threshold > 0`` or ``do_3D`` every input array is one z-stack and ``output`` is
+        [Z, H, W].  ``do_3D`` with ``return_flows``: ``flows`` is [per-plane RGB of (dY, dX), dP
+        [3, Z', H, W] (dZ, dY, dX), cellprob [Z', H, W]], ``Z'`` the depth after ``anisotropy``."""
         if isinstance(artifact, dict):
             w = artifact
             artifact = w.get("artifact", w.get("artifact_id", w.get("id")))
@@ -459,10 +466,19 @@ class CellposeFinetune:
             niter, return_flows = w.get("niter", niter), w.get("return_flows", return_flows)
             json_safe, enable_clahe = w.get("json_safe", json_safe), w.get("enable_clahe", enable_clahe)
             stitch_threshold, z_axis = w.get("stitch_threshold", stitch_threshold), w.get("z_axis", z_axis)
+            do_3D, anisotropy = w.get("do_3D", do_3D), w.get("anisotropy", anisotropy)
         stitch_threshold = float(_opt(stitch_threshold) or 0.0)
         z_axis = _opt(z_axis)
         if not 0.0 <= stitch_threshold <= 1.0:
             raise ValueError(f"stitch_threshold must be in [0, 1], got {stitch_threshold}")
+        do_3D = bool(_opt(do_3D) or False)
+        anisotropy = _opt(anisotropy)
+        if anisotropy is not None:
+            anisotropy = float(anisotropy)
+            if not anisotropy > 0:
+                raise ValueError(f"anisotropy must be positive, got {anisotropy}")
+        if do_3D and stitch_threshold > 0:
+            raise ValueError("do_3D and stitch_threshold > 0 are two ways to segment a z-stack: give one of them")
         model = _opt(model) or self.default_model
         model_id = await self.resolve_model_id(model)
         if _opt(input_arrays) is not None:
@@ -473,17 +489,17 @@ class CellposeFinetune:
             images = await self._images_from_artifact(artifact, names)
         else:
             raise ValueError("Provide input_arrays or artifact + image_paths")
-        stack_mode = z_axis is not None or stitch_threshold > 0
+        stack_mode = z_axis is not None or stitch_threshold > 0 or do_3D
         if enable_clahe:
             if stack_mode:
-                raise ValueError("enable_clahe is not supported for z-stacks (z_axis / stitch_threshold)")
+                raise ValueError("enable_clahe is not supported for z-stacks (z_axis / stitch_threshold / do_3D)")
             images = [clahe_image(im, self._device()) for im in images]
         runner = await self._runner(model_id)
         prm = {"diameter": _opt(diameter), "flow_threshold": float(flow_threshold),
                "cellprob_threshold": float(cellprob_threshold), "niter": int(_opt(niter) or 200)}
         if stack_mode:
             out = await self._infer_stacks(runner, names, images, prm, stitch_threshold, int(z_axis or 0),
-                                           bool(return_flows), bool(json_safe))
+                                           bool(return_flows), bool(json_safe), do_3D, anisotropy)
             if self._weights.get(model_id) == "random" and out:
                 out[0]["weights"] = "random"
             return out
@@ -506,10 +522,12 @@ class CellposeFinetune:
         return out
 
     async def _infer_stacks(self, runner, names: list, stacks: list, prm: dict, stitch_threshold: float, z_axis: int,
-                            return_flows: bool, json_safe: bool) -> list:
+                            return_flows: bool, json_safe: bool, do_3D: bool = False,
+                            anisotropy: float | None = None) -> list:
         """Stack mode of :meth:`infer`: every array is one z-stack ([Z,H,W], [Z,C,H,W] or [Z,H,W,C] once
         ``z_axis`` is moved to the front); its planes are one batch of ``runner.eval_stack`` (no
-        continuous batching across requests), stitched on the device."""
+        continuous batching across requests), stitched on the device.  ``do_3D`` routes the stack to
+        ``runner.eval_3d`` instead (orthogonal views, 3-D dynamics; ``flow_threshold`` is unused)."""
         out = []
         for name, a in zip(names, stacks):
             a = np.asarray(a)
@@ -524,7 +542,10 @@ class CellposeFinetune:
 
             def run(a=a):
                 with self._gpu_lock:
-                    m, f, _ = runner.eval_stack(a, stitch_threshold=stitch_threshold, **prm)
+                    if do_3D:
+                        m, f, _ = runner.eval_3d(a, anisotropy=anisotropy, **prm)
+                    else:
+                        m, f, _ = runner.eval_stack(a, stitch_threshold=stitch_threshold, **prm)
                     m = m.cpu().numpy()
                     return m, (f.cpu().numpy() if return_flows else None)
 
@@ -533,7 +554,10 @@ class CellposeFinetune:
             m = m.astype(np.uint16) if int(m.max(initial=0)) < 65536 else m.astype(np.int32)
             item = {"input_path": name, "output": [mask_png_payload(pl) for pl in m] if json_safe else m}
             if return_flows:
-                fl = [np.stack([flow_rgb(y[:2]) for y in f]), f[:, :2], f[:, 2]]
+                if do_3D:  # f [4, Z', H, W] (dZ, dY, dX, cellprob)
+                    fl = [np.stack([flow_rgb(f[1:3, z]) for z in range(f.shape[1])]), f[:3], f[3]]
+                else:
+                    fl = [np.stack([flow_rgb(y[:2]) for y in f]), f[:, :2], f[:, 2]]
                 item["flows"] = [x.tolist() for x in fl] if json_safe else fl
             out.append(item)
         return out

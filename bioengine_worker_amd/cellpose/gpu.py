@@ -1,6 +1,6 @@
 """GPU (HIP) implementation of Cellpose pre/post-processing on batches of images.
 
-Every heavy step is a kernel in ``csrc/kernels/{tiles,cellpose_dynamics,cellpose_masks,cellpose_stitch}.hip``;
+Every heavy step is a kernel in ``csrc/kernels/{tiles,cellpose_dynamics,cellpose_dynamics3d,cellpose_masks,cellpose_stitch}.hip``;
 torch is only used for tiny bookkeeping (sorting the seed keys, prefix sums over labels, building
 per-mask job lists).  The semantics are those of :mod:`bioengine_worker_amd.cellpose.reference`
 (the CPU oracle), which the GPU tests compare against.
@@ -684,3 +684,184 @@ def stitch3d_gpu(M: torch.Tensor, stitch_threshold: float = 0.25, min_size: int 
     _native.call("be_cp_stitch_relabel", _native.ptr(Mc), Z, HW, nlab, _native.ptr(gid), _native.ptr(lut), _native.ptr(out),
                  st)
     return out
+
+
+# ------------------------------------------------------------------ do_3D: orthogonal views + 3-D dynamics
+
+
+def _check_volume(Z: int, H: int, W: int) -> None:
+    """The padded histogram is indexed with 32-bit integers."""
+    if min(Z, H, W) < 0 or (Z + 2 * RPAD) * (H + 2 * RPAD) * (W + 2 * RPAD) >= 2 ** 31:
+        raise ValueError(f"3-D dynamics: volume {Z} x {H} x {W} is too large ((Z+40)*(H+40)*(W+40) must be below 2^31)")
+
+
+def accum_view3d(acc: torch.Tensor, y: torch.Tensor, view: int, p0: int) -> None:
+    """Add one chunk of one view's network output into the accumulator ``acc`` [4, Z, H, W] fp32
+    (dZ, dY, dX, cellprob), in place.  ``y`` [n, 3, h, w] are planes ``p0 .. p0 + n - 1`` of ``view``:
+    0 = YX ([n, 3, H, W], planes along z; *writes* dY, dX, cellprob and zeroes dZ), 1 = ZX
+    ([n, 3, Z, W], planes along y; adds dZ, dX, cellprob), 2 = ZY ([n, 3, Z, H], planes along x; adds
+    dZ, dY, cellprob).  Running all YX chunks, then ZX, then ZY gives the sums of
+    :func:`reference.combine_views3d` bit for bit (``be_cp_accum_view3d``)."""
+    _, Z, H, W = acc.shape
+    _check_volume(Z, H, W)
+    if acc.dtype != torch.float32 or not acc.is_contiguous() or acc.shape[0] != 4:
+        raise ValueError("accum_view3d: acc must be a contiguous [4, Z, H, W] float32 tensor")
+    want = ((Z, H, W), (H, Z, W), (W, Z, H))[view]
+    n = y.shape[0]
+    if y.dim() != 4 or y.shape[1] != 3 or tuple(y.shape[2:]) != want[1:] or p0 < 0 or p0 + n > want[0]:
+        raise ValueError(f"accum_view3d: view {view} chunk of shape {tuple(y.shape)} at plane {p0} does not fit "
+                         f"a {Z} x {H} x {W} volume")
+    y = y.float().contiguous()
+    _native.call("be_cp_accum_view3d", _native.ptr(y), int(view), int(p0), n, Z, H, W, _native.ptr(acc),
+                 _native.stream(acc.device))
+
+
+def combine_views3d_gpu(y_yx: torch.Tensor, y_zx: torch.Tensor, y_zy: torch.Tensor, chunk: int = 32) -> torch.Tensor:
+    """The three whole view outputs -> accumulator [4, Z, H, W] (dZ, dY, dX, cellprob), fed to
+    :func:`accum_view3d` in chunks of ``chunk`` planes.  CPU tensors run the oracle."""
+    if y_yx.device.type != "cuda":
+        dP, cp = ref.combine_views3d(y_yx.numpy(), y_zx.numpy(), y_zy.numpy())
+        return torch.from_numpy(np.concatenate([dP, cp[None]]))
+    Z, _, H, W = y_yx.shape
+    _check_volume(Z, H, W)
+    acc = torch.empty(4, Z, H, W, dtype=torch.float32, device=y_yx.device)
+    for view, y in enumerate((y_yx, y_zx, y_zy)):
+        for i in range(0, y.shape[0], max(1, int(chunk))):
+            accum_view3d(acc, y[i: i + chunk], view, i)
+    return acc
+
+
+def _as_flow4(flow, cellprob=None) -> torch.Tensor:
+    """``flow`` [4, Z, H, W] or (dP [3, Z, H, W], cellprob [Z, H, W]) -> contiguous fp32 [4, Z, H, W]."""
+    if isinstance(flow, (tuple, list)):
+        flow, cellprob = flow
+    if cellprob is not None:
+        flow = torch.cat([flow.float(), cellprob.float()[None]])
+    if flow.dim() != 4 or flow.shape[0] != 4:
+        raise ValueError(f"3-D dynamics expect a [4, Z, H, W] field (dZ, dY, dX, cellprob), got shape {tuple(flow.shape)}")
+    return flow.float().contiguous()
+
+
+def follow_flows3d_gpu(flow: torch.Tensor, niter: int = 200, cellprob_threshold: float = 0.0, variant: int = 0):
+    """Accumulator ``flow`` [4, Z, H, W] -> ``(hist [Z+40, H+40, W+40] int32, pos [Z, H, W] int32)``:
+    the histogram of the end points of :func:`reference.follow_flows3d` in the padded volume and every
+    foreground voxel's padded linear bin index (-1 for background).  ``variant`` 0 = XCD-ordered,
+    block-compacted launch, 1 = plain one-lane-per-voxel launch; identical results."""
+    _, Z, H, W = flow.shape
+    _check_volume(Z, H, W)
+    dev = flow.device
+    st = _native.stream(dev)
+    flow4 = torch.empty(Z, H, W, 4, dtype=torch.float32, device=dev)
+    fg = torch.empty(Z, H, W, dtype=torch.uint8, device=dev)
+    _native.call("be_cp_prep_flow3d", _native.ptr(flow), Z, H, W, float(cellprob_threshold), _native.ptr(flow4),
+                 _native.ptr(fg), st)
+    hist = torch.zeros(Z + 2 * RPAD, H + 2 * RPAD, W + 2 * RPAD, dtype=torch.int32, device=dev)
+    pos = torch.empty(Z, H, W, dtype=torch.int32, device=dev)
+    _native.call("be_cp_follow_flows3d", _native.ptr(flow4), _native.ptr(fg), _native.ptr(hist), _native.ptr(pos), Z, H, W,
+                 int(niter), int(variant), st)
+    return hist, pos
+
+
+def get_masks3d_gpu(hist: torch.Tensor, pos: torch.Tensor, shape=None, max_size_fraction: float = 0.4,
+                    with_bound: bool = False):
+    """The stages of :func:`reference.get_masks3d` after the histogram: ``hist`` [Z+40, H+40, W+40]
+    int32 and ``pos`` [Z, H, W] int32 (padded linear bin of every foreground voxel, -1 elsewhere) ->
+    raw labels [Z, H, W] int32 numbered ``1..k`` (before the hole fill); with ``with_bound`` also an
+    upper bound on its labels + 1.  5x5x5 seeds (``be_cp_seeds3d``), ``torch.sort`` of the seed keys,
+    11^3 window expansion (``be_cp_expand3d``), per-voxel lookup.  One host sync (the seed count).
+    CPU tensors run the oracle."""
+    Z, H, W = tuple(pos.shape) if shape is None else tuple(int(v) for v in shape)
+    _check_volume(Z, H, W)
+    Zp, Hp, Wp = Z + 2 * RPAD, H + 2 * RPAD, W + 2 * RPAD
+    if tuple(hist.shape) != (Zp, Hp, Wp) or tuple(pos.shape) != (Z, H, W):
+        raise ValueError(f"get_masks3d_gpu: hist {tuple(hist.shape)} / pos {tuple(pos.shape)} do not fit a "
+                         f"{Z} x {H} x {W} volume padded by {RPAD}")
+    N, Np = Z * H * W, Zp * Hp * Wp
+    if pos.device.type != "cuda":
+        pn = pos.numpy()
+        inds = np.nonzero(pn >= 0)
+        bins = np.stack(np.unravel_index(pn[inds].astype(np.int64), (Zp, Hp, Wp))) if N else np.zeros((3, 0), np.int64)
+        M = torch.from_numpy(ref.get_masks3d((bins - RPAD).astype(np.float32), inds, (Z, H, W), RPAD, max_size_fraction))
+        return (M, int(M.max()) + 1 if N else 1) if with_bound else M
+    dev = pos.device
+    st = _native.stream(dev)
+    hist = hist.to(torch.int32).contiguous()
+    pos = pos.to(torch.int32).contiguous()
+    M0 = torch.zeros(Z, H, W, dtype=torch.int32, device=dev)
+    if N == 0:
+        return (M0, 1) if with_bound else M0
+    cap = N // 11 + 1  # a seed holds more than 10 of the at most N end points
+    keys = torch.empty(cap, dtype=torch.int64, device=dev)
+    nseeds = torch.zeros(1, dtype=torch.int32, device=dev)
+    _native.call("be_cp_seeds3d", _native.ptr(hist), Zp, Hp, Wp, _native.ptr(keys), _native.ptr(nseeds), cap, st)
+    k = min(int(nseeds.item()), cap)  # host sync: sizes the sort and the expansion grid
+    if k == 0:
+        return (M0, 1) if with_bound else M0
+    keys_sorted, _ = torch.sort(keys[:k])
+    M1 = torch.zeros(Zp, Hp, Wp, dtype=torch.int32, device=dev)
+    _native.call("be_cp_expand3d", _native.ptr(hist), _native.ptr(keys_sorted), k, Zp, Hp, Wp, _native.ptr(M1), st)
+    nlab = k + 1
+    counts = torch.zeros(1, nlab, dtype=torch.int32, device=dev)
+    _native.call("be_cp_label_lookup", _native.ptr(pos), _native.ptr(M1), 1, N, Np, _native.ptr(M0), _native.ptr(counts),
+                 nlab, st)
+    keep = (counts > 0) & (counts <= N * max_size_fraction)
+    M = _renumber(M0.view(1, N), keep).view(Z, H, W)
+    return (M, nlab) if with_bound else M
+
+
+def follow_and_label3d(flow, niter: int = 200, cellprob_threshold: float = 0.0, max_size_fraction: float = 0.4,
+                       with_bound: bool = False, variant: int = 0):
+    """``flow`` [4, Z, H, W] (dZ, dY, dX, cellprob) or ``(dP [3, Z, H, W], cellprob [Z, H, W])`` -> raw
+    3-D labels [Z, H, W] int32 (before the hole fill): :func:`follow_flows3d_gpu` then
+    :func:`get_masks3d_gpu`.  CPU tensors run the oracle."""
+    flow = _as_flow4(flow)
+    _, Z, H, W = flow.shape
+    _check_volume(Z, H, W)
+    if flow.device.type != "cuda":
+        f = flow.numpy()
+        p, inds = ref.follow_flows3d(f[:3], f[3], cellprob_threshold, niter)
+        M = torch.from_numpy(ref.get_masks3d(p, inds, (Z, H, W), RPAD, max_size_fraction))
+        return (M, int(M.max()) + 1 if M.numel() else 1) if with_bound else M
+    hist, pos = follow_flows3d_gpu(flow, niter, cellprob_threshold, variant)
+    return get_masks3d_gpu(hist, pos, (Z, H, W), max_size_fraction, with_bound)
+
+
+def fill_holes3d_gpu(M: torch.Tensor, min_size: int = 15, nlab: int | None = None) -> torch.Tensor:
+    """:func:`reference.fill_holes_and_remove_small_masks3d` on the device: the 2-D fill kernels with
+    one image per plane and a lut that keeps the ids (``lut[z, l] = l`` where label ``l`` occurs in
+    plane ``z``), then the volume ``min_size`` on the per-plane counts summed over z and a renumber in
+    id order.  ``nlab``: optional upper bound on the labels + 1."""
+    Z, H, W = M.shape
+    if M.device.type != "cuda":
+        return torch.from_numpy(ref.fill_holes_and_remove_small_masks3d(M.numpy(), min_size))
+    if nlab is None:
+        nlab = int(M.max().item()) + 1 if M.numel() else 1
+    if nlab <= 1 or M.numel() == 0:
+        return torch.zeros_like(M)
+    M = M.to(torch.int32).contiguous()
+    present = label_counts(M, nlab) > 0
+    present[:, 0] = False
+    lut = (present.int() * torch.arange(nlab, dtype=torch.int32, device=M.device)[None]).contiguous()
+    plan = _plan_masks(mask_bboxes(M, nlab), present, _fill_plan_kind(), [LDS_FILL_BYTES])
+    out = _fill_run(M, lut, nlab, plan)
+    vol = label_counts(out, nlab).sum(0, keepdim=True)
+    keep = vol > 0
+    if min_size > 0:
+        keep &= vol >= min_size
+    return _renumber(out.view(1, -1), keep).view(Z, H, W)
+
+
+def compute_masks3d_gpu(dP, cellprob=None, niter: int = 200, cellprob_threshold: float = 0.0, min_size: int = 15,
+                        max_size_fraction: float = 0.4) -> torch.Tensor:
+    """3-D Cellpose mask recovery: ``dP`` [3, Z, H, W] (dZ, dY, dX) and ``cellprob`` [Z, H, W] (or one
+    [4, Z, H, W] field with ``cellprob=None``) -> masks [Z, H, W] int32 numbered ``1..K``.  HIP
+    implementation of :func:`reference.compute_masks3d` (``csrc/kernels/cellpose_dynamics3d.hip`` plus
+    the 2-D lookup and fill kernels); no flow QC in 3-D.  CPU tensors run the oracle."""
+    flow = _as_flow4(dP, cellprob)
+    if flow.device.type != "cuda":
+        f = flow.numpy()
+        return torch.from_numpy(ref.compute_masks3d(f[:3], f[3], niter, cellprob_threshold, min_size, max_size_fraction))
+    M, nlab = follow_and_label3d(flow, niter, cellprob_threshold, max_size_fraction, with_bound=True)
+    if nlab <= 1:
+        return M
+    return fill_holes3d_gpu(M, min_size, nlab)

@@ -52,6 +52,10 @@ class EvalParams:
     #: could not be checked offline; True follows its documented stitching behaviour.
     norm3d: bool = True
     stack_batch: int = 32  # planes per eval() call
+    # ---- do_3D (CellposeRunner.eval_3d only; eval() and eval_stack() ignore this)
+    #: z spacing / xy spacing: the volume is resampled along z to round(Z * anisotropy) planes before
+    #: the three views run (None or 1 = isotropic voxels)
+    anisotropy: float | None = None
 
 
 def as_batch(images, nchan: int, device=None) -> torch.Tensor:
@@ -282,6 +286,106 @@ class CellposeRunner:
                 else:
                     M = torch.from_numpy(ref.stitch3d(M.numpy(), p.stitch_threshold, min_size=p.min_size))
         return M, flows, styles
+
+    #: fewest planes along any axis of an :meth:`eval_3d` volume.  The ZX and ZY views are Z planes
+    #: high; the tiled network pads every plane to a multiple of 16 plus an 8-pixel margin, so it
+    #: runs from one row up, but trilinear resampling, the 8x downsampling of the untiled path and
+    #: the ``diameter`` rescale (never below 8 rows) all need a real third dimension: below 2 planes
+    #: a volume is an image and belongs to :meth:`eval`; the untiled path needs 8.
+    MIN_DEPTH_3D = 2
+    MIN_DEPTH_3D_UNTILED = 8
+
+    @torch.no_grad()
+    def eval_3d(self, volume, p: EvalParams | None = None, **kw):
+        """Volumetric segmentation (cellpose ``eval(..., do_3D=True)``): the network runs on the YX,
+        ZX and ZY planes of the volume, the three outputs are summed into one (dZ, dY, dX, cellprob)
+        field (:func:`reference.combine_views3d`) and the flow dynamics, seeding and labelling run in
+        three dimensions (:func:`reference.compute_masks3d`; no flow QC, ``flow_threshold`` is unused).
+
+        ``volume``: [Z, H, W], [Z, C, H, W] or [Z, H, W, C], numpy or torch, as :meth:`eval_stack`
+        takes.  Returns ``(masks [Z, H, W] int32, flows [4, Z', H, W] fp32 (dZ, dY, dX, cellprob),
+        styles [S])``; ``styles`` is the mean style of the YX planes.  The volume is normalised once,
+        per channel over all voxels; every view's planes then go through the network stage in chunks
+        of ``p.stack_batch`` planes (so ``diameter`` rescales each plane as in :meth:`eval`) and each
+        chunk is added to the accumulator as soon as it exists.
+
+        ``p.anisotropy`` (z spacing over xy spacing), when set and not 1: the normalised volume is
+        resampled along z to ``Z' = round(Z * anisotropy)`` planes (trilinear, ``align_corners=False``),
+        masks are computed there and brought back with the nearest-plane rule ``z_src = min(floor((z +
+        0.5) * Z' / Z), Z' - 1)`` and numbered ``1..K`` again.  ``flows`` stay at the resampled depth ``Z'`` (``Z' = Z`` otherwise)."""
+        p = dataclasses.replace(p) if p is not None else EvalParams()
+        for k, v in kw.items():
+            setattr(p, k, v)
+        x = torch.as_tensor(np.asarray(volume) if not torch.is_tensor(volume) else volume)
+        if x.dim() == 3:
+            x = x[:, None]
+        elif x.dim() == 4:
+            if x.shape[-1] <= 4 and x.shape[1] > 4:  # channel-last, as as_batch decides for one image
+                x = x.permute(0, 3, 1, 2)
+        else:
+            raise ValueError(f"eval_3d expects [Z,H,W], [Z,C,H,W] or [Z,H,W,C], got shape {tuple(x.shape)}")
+        x = as_batch(x, self.nchan, self.device)
+        Z, C, H, W = x.shape
+        aniso = p.anisotropy
+        if aniso is not None and not aniso > 0:
+            raise ValueError(f"anisotropy must be positive, got {aniso}")
+        Zr = Z if aniso is None or aniso == 1 else max(1, int(round(Z * float(aniso))))
+        need = self.MIN_DEPTH_3D if p.tile else self.MIN_DEPTH_3D_UNTILED
+        if min(Z, Zr, H, W) < need:
+            raise ValueError(f"eval_3d needs at least {need} planes along every axis (tile={p.tile}), got a "
+                             f"{Z} x {H} x {W} volume" + (f" resampled to {Zr} planes" if Zr != Z else ""))
+        on_gpu = self.device.type == "cuda"
+        if on_gpu:
+            from . import gpu
+
+            gpu._check_volume(Zr, H, W)
+        if p.normalize:
+            with trace.span("cellpose.normalize99", cuda=on_gpu, images=Z):
+                xs = x.permute(1, 0, 2, 3).reshape(1, C, Z * H, W)
+                x = self._normalize(xs).reshape(C, Z, H, W).permute(1, 0, 2, 3).contiguous()
+        if Zr != Z:
+            x = F.interpolate(x.permute(1, 0, 2, 3)[None], size=(Zr, H, W), mode="trilinear",
+                              align_corners=False)[0].permute(1, 0, 2, 3).contiguous()
+        pp = dataclasses.replace(p, normalize=False)
+        step = max(1, int(p.stack_batch))
+        acc = torch.empty(4, Zr, H, W, dtype=torch.float32, device=self.device) if on_gpu else None
+        outs, style, rescale = [], None, 1.0
+        with trace.span("cellpose.views3d", cuda=on_gpu, planes=Zr + H + W):
+            for view, perm in enumerate(((0, 1, 2, 3), (2, 1, 0, 3), (3, 1, 0, 2))):
+                xv = x.permute(*perm)  # [planes, C, rows, columns] of this view
+                ys = []
+                for i in range(0, xv.shape[0], step):
+                    y, s, rescale = self._net_stage(xv[i: i + step].contiguous(), dataclasses.replace(pp))
+                    if view == 0:
+                        style = s.sum(0) if style is None else style + s.sum(0)
+                    if on_gpu:
+                        gpu.accum_view3d(acc, y, view, i)
+                    else:
+                        ys.append(y)
+                    del y
+                if not on_gpu:
+                    outs.append(torch.cat(ys).numpy())
+            if not on_gpu:
+                dP, cp = ref.combine_views3d(*outs)
+                acc = torch.from_numpy(np.concatenate([dP, cp[None]]))
+        style = style / Zr
+        if not p.compute_masks:
+            return None, acc, style
+        niter = p.niter if p.niter else int(200 / max(rescale, 1e-3))
+        with trace.span("cellpose.masks3d", cuda=on_gpu, planes=Zr):
+            if on_gpu:
+                M = gpu.compute_masks3d_gpu(acc, None, niter=niter, cellprob_threshold=p.cellprob_threshold,
+                                            min_size=p.min_size, max_size_fraction=p.max_size_fraction)
+            else:
+                a = acc.numpy()
+                M = torch.from_numpy(ref.compute_masks3d(a[:3], a[3], niter=niter, cellprob_threshold=p.cellprob_threshold,
+                                                         min_size=p.min_size, max_size_fraction=p.max_size_fraction))
+            if Zr != Z:
+                zs = ((torch.arange(Z, device=M.device) * 2 + 1) * Zr // (2 * Z)).clamp_(max=Zr - 1)
+                # an instance that lives only on planes the rule skips is gone: number the rest 1..K again
+                u, inv = torch.unique(M[zs], return_inverse=True)
+                M = (inv if int(u[0]) == 0 else inv + 1).to(torch.int32).contiguous()
+        return M, acc, style
 
     def _stage(self, images):
         """numpy batch -> view of a reusable pinned host buffer, so the H2D copy is one DMA at full

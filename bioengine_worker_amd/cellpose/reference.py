@@ -18,6 +18,9 @@ masks_to_flows   per-mask heat diffusion from the median-nearest pixel, gradient
 flow QC          mean squared error between mask flows and dP/5 per mask; drop masks above threshold
 fill_holes       drop masks smaller than min_size, fill holes, renumber
 stitch3d         z-stacks: join the masks of adjacent planes by exact mutual-best IoU into 3-D labels
+do_3D            volumes: combine_views3d (YX + ZX + ZY network outputs -> dZ, dY, dX, cellprob),
+                 follow_flows3d / get_masks3d / fill_holes_and_remove_small_masks3d: the 2-D stages
+                 with one more axis (trilinear sampling, 5x5x5 seeds, 11x11x11 windows, no flow QC)
 """
 from __future__ import annotations
 
@@ -339,3 +342,143 @@ def stitch3d(masks: np.ndarray, stitch_threshold: float = 0.25, min_size: int = 
     if Z == 0:
         return np.zeros(M.shape, np.int32)
     return lut[np.stack(gids)]
+
+
+# ------------------------------------------------------------------ do_3D: orthogonal views + 3-D dynamics
+#
+# The 2-D stages above with one more axis, after cellpose 3.x ``_run_3D`` / ``dynamics.compute_masks``
+# with ``do_3D=True``.  cellpose is not installed where this was written, so nothing below could be
+# compared with the library: the semantics are the ones spelled out in the docstrings.
+
+
+def combine_views3d(y_yx: np.ndarray, y_zx: np.ndarray, y_zy: np.ndarray):
+    """Network outputs of the three orthogonal plane families of one volume -> ``(dP [3, Z, H, W]
+    (dZ, dY, dX), cellprob [Z, H, W])`` float32.
+
+    ``y_yx`` [Z, 3, H, W] (one plane per z), ``y_zx`` [H, 3, Z, W] (one per y), ``y_zy`` [W, 3, Z, H]
+    (one per x); each view's channels are (flow along the plane's rows, flow along its columns,
+    cellprob).  ``dZ = zx[0] + zy[0]``, ``dY = yx[0] + zy[1]``, ``dX = yx[1] + zx[1]``, ``cellprob =
+    (yx[2] + zx[2]) + zy[2]``: sums, not means, as cellpose 3.x ``_run_3D`` adds them (not compared
+    with the library, see above).  The order of the float additions is part of the definition."""
+    yx = np.asarray(y_yx, np.float32).transpose(1, 0, 2, 3)  # [3, Z, H, W]
+    zx = np.asarray(y_zx, np.float32).transpose(1, 2, 0, 3)  # [3, Z, H, W] from [H, 3, Z, W]
+    zy = np.asarray(y_zy, np.float32).transpose(1, 2, 3, 0)  # [3, Z, H, W] from [W, 3, Z, H]
+    dP = np.stack([zx[0] + zy[0], yx[0] + zy[1], yx[1] + zx[1]])
+    cellprob = (yx[2] + zx[2]) + zy[2]
+    return np.ascontiguousarray(dP), np.ascontiguousarray(cellprob)
+
+
+def follow_flows3d(dP: np.ndarray, cellprob: np.ndarray, cellprob_threshold: float = 0.0, niter: int = 200):
+    """:func:`follow_flows` with one more axis.  ``dP`` [3, Z, H, W] (dZ, dY, dX); returns
+    ``(p_final [3, npts] float32 (z, y, x), inds (z, y, x) arrays)``.
+
+    ``niter`` Euler steps of ``dP * fg / 5`` sampled trilinearly with 5-D ``grid_sample(
+    align_corners=False)`` semantics: the sample position along an axis of length ``L`` is
+    ``p * L / (L - 1) - 0.5`` (an axis of length 1 samples its only plane with weight 1), zeros
+    outside the volume; positions are clamped to ``[0, L - 1]`` per axis after every step.  Not
+    compared with cellpose (see above)."""
+    fg = cellprob > cellprob_threshold
+    inds = np.nonzero(fg)
+    Lz, Ly, Lx = cellprob.shape
+    flow = torch.from_numpy((dP * fg / 5.0).astype(np.float32))
+    p = torch.from_numpy(np.stack(inds).astype(np.float32))  # [3, n] (z, y, x)
+    n = p.shape[1]
+    if n == 0:
+        return p.numpy(), inds
+    im = flow[[2, 1, 0]].unsqueeze(0)  # (x, y, z) channel order as grid_sample expects
+    pt = torch.zeros(1, 1, 1, n, 3)
+    L = (Lx, Ly, Lz)
+    for t in range(niter):
+        for a in range(3):  # grid axis a (x, y, z) is position row 2 - a
+            pt[0, 0, 0, :, a] = 2 * p[2 - a] / (L[a] - 1) - 1 if L[a] > 1 else 0.0
+        d = F.grid_sample(im, pt, align_corners=False)[0, :, 0, 0, :]  # [3 (x, y, z), n]
+        for a in range(3):
+            p[2 - a] = torch.clamp(p[2 - a] + d[a], 0, L[a] - 1)
+    return p.numpy(), inds
+
+
+def end_bins3d(p: np.ndarray, shape, rpad: int = 20) -> np.ndarray:
+    """Truncated end points ``p`` [3, n] -> their (z, y, x) bins [3, n] int64 in the volume padded by
+    ``rpad`` on every side (clipped to ``[0, L + rpad - 1]`` per axis)."""
+    pt = p.astype(np.int64) + rpad  # truncation (p >= 0)
+    for a in range(3):
+        pt[a] = np.clip(pt[a], 0, shape[a] + rpad - 1)
+    return pt
+
+
+def get_masks3d(p: np.ndarray, inds, shape, rpad: int = 20, max_size_fraction: float = 0.4) -> np.ndarray:
+    """:func:`get_masks` with one more axis: histogram of the end points in the padded volume, seeds
+    where ``h > 10`` and ``h >=`` its 5x5x5 maximum (zero outside) ordered by ascending count (ties by
+    raster index), per seed five 3x3x3 dilations from the centre of its 11x11x11 window and-ed with
+    ``h > 2`` (later seeds overwrite earlier ones), every voxel labelled by its end point's bin,
+    labels of more than ``max_size_fraction`` of the voxels dropped, renumbered.  Not compared with
+    cellpose (see above)."""
+    Lz, Ly, Lx = shape
+    M0 = np.zeros(shape, np.int32)
+    if p.shape[1] == 0:
+        return M0
+    pt = end_bins3d(p, shape, rpad)
+    hs = (Lz + 2 * rpad, Ly + 2 * rpad, Lx + 2 * rpad)
+    h1 = np.zeros(hs, np.int32)
+    np.add.at(h1, (pt[0], pt[1], pt[2]), 1)
+    hmax = ndimage.maximum_filter(h1, size=5, mode="constant", cval=0)
+    seeds = np.argwhere((h1 >= hmax) & (h1 > 10))
+    if len(seeds) == 0:
+        return M0
+    npts = h1[seeds[:, 0], seeds[:, 1], seeds[:, 2]]
+    lin = (seeds[:, 0] * hs[1] + seeds[:, 1]) * hs[2] + seeds[:, 2]
+    order = np.lexsort((lin, npts))  # ascending count, ties by raster index
+    seeds = seeds[order]
+    M1 = np.zeros(hs, np.int32)
+    struct = np.ones((3, 3, 3), bool)
+    for k, (sz, sy, sx) in enumerate(seeds):
+        win = h1[sz - 5: sz + 6, sy - 5: sy + 6, sx - 5: sx + 6] > 2
+        sm = np.zeros((11, 11, 11), bool)
+        sm[5, 5, 5] = True
+        for _ in range(5):
+            sm = ndimage.binary_dilation(sm, structure=struct) & win
+        zz, yy, xx = np.nonzero(sm)
+        M1[zz + sz - 5, yy + sy - 5, xx + sx - 5] = k + 1
+    M0[inds] = M1[pt[0], pt[1], pt[2]]
+    big = Lz * Ly * Lx * max_size_fraction
+    labels, counts = np.unique(M0, return_counts=True)
+    for lab, c in zip(labels, counts):
+        if lab != 0 and c > big:
+            M0[M0 == lab] = 0
+    return renumber(M0)
+
+
+def fill_holes_and_remove_small_masks3d(masks: np.ndarray, min_size: int = 15) -> np.ndarray:
+    """Volumetric labels [Z, H, W] -> holes filled plane by plane in z (the 2-D rule of
+    :func:`fill_holes_and_remove_small_masks`: a hole voxel is claimed only where no other mask
+    lives; where two masks claim one background voxel the larger id takes it), then instances of
+    fewer than ``min_size`` voxels over the whole volume (counted after the fill) dropped and the
+    rest numbered ``1..K`` in id order.  A cavity that no single plane closes stays open.  Not
+    compared with cellpose (see above)."""
+    masks = np.asarray(masks)
+    out = np.zeros(masks.shape, np.int32)
+    for z in range(masks.shape[0]):
+        pl = masks[z]
+        for i, sl in enumerate(ndimage.find_objects(pl)):
+            if sl is None:
+                continue
+            msk = pl[sl] == i + 1
+            filled = ndimage.binary_fill_holes(msk)
+            claim = filled & ((pl[sl] == 0) | msk)
+            out[z][sl][claim] = i + 1
+    counts = np.bincount(out.ravel(), minlength=1)
+    keep = counts > 0
+    if min_size > 0:
+        keep &= counts >= min_size
+    keep[0] = False
+    lut = (np.cumsum(keep) * keep).astype(np.int32)
+    return lut[out]
+
+
+def compute_masks3d(dP, cellprob, niter=200, cellprob_threshold=0.0, min_size=15, max_size_fraction=0.4) -> np.ndarray:
+    """3-D mask recovery: :func:`follow_flows3d` -> :func:`get_masks3d` ->
+    :func:`fill_holes_and_remove_small_masks3d`.  No flow QC: cellpose documents ``flow_threshold``
+    as unused in 3-D."""
+    p, inds = follow_flows3d(dP, cellprob, cellprob_threshold, niter)
+    mask = get_masks3d(p, inds, cellprob.shape, max_size_fraction=max_size_fraction)
+    return fill_holes_and_remove_small_masks3d(mask, min_size)
