@@ -169,6 +169,14 @@ def mask_png_payload(mask: np.ndarray) -> dict:
             "object_count": int(ids.size), "png_base64": base64.b64encode(buf.getvalue()).decode("ascii")}
 
 
+def measurement_items(table: dict, json_safe: bool) -> dict:
+    """The ``measurements`` / ``diameter_px`` entries of one ``infer`` result (arrays as lists when
+    ``json_safe``)."""
+    if json_safe:
+        table = {k: (v.tolist() if isinstance(v, np.ndarray) else v) for k, v in table.items()}
+    return {"measurements": table, "diameter_px": float(table["diameter_px"])}
+
+
 def flow_rgb(dP: np.ndarray) -> np.ndarray:
     """cellpose ``dx_to_circ``: flow angle -> hue, magnitude -> value, as uint8 RGB [H, W, 3]."""
     dy, dx = dP[0], dP[1]
@@ -322,7 +330,8 @@ class CellposeFinetune:
     # ------------------------------------------------------------------ inference (continuous batching)
     @serve.batch(max_batch_size=32, batch_wait_timeout_s=0.005, max_concurrent_batches=2)
     async def _segment_batch(self, reqs: list) -> list:
-        """reqs: [(model_id, image CHW, params dict, want_flows)] -> [(masks, flows | None)].
+        """reqs: [(model_id, image CHW, params dict, want_flows[, want_measure])] -> [(masks, flows | None,
+        measurement table | None)].
 
         Two batches are in flight: while one batch's kernels run (under the GPU lock, on the
         default stream), the other stacks its images or copies its masks back on a side stream
@@ -331,13 +340,15 @@ class CellposeFinetune:
 
         out = [None] * len(reqs)
         groups: dict = {}
-        for i, (mid, img, prm, want_flows) in enumerate(reqs):
+        for i, (mid, img, prm, *_) in enumerate(reqs):
             key = (mid, img.shape, img.dtype.str, isinstance(img, HWCImage), tuple(sorted(prm.items())))
             groups.setdefault(key, []).append(i)
         for (mid, shape, _, _, prm_items), idxs in groups.items():
             runner = await self._runner(mid)
             prm = dict(prm_items)
             flows_needed = any(reqs[i][3] for i in idxs)
+            # like want_flows, not part of the grouping key: the batch measures if any request asks
+            measure_needed = any(len(reqs[i]) > 4 and reqs[i][4] for i in idxs)
 
             def run():
                 import torch
@@ -361,7 +372,8 @@ class CellposeFinetune:
                                 ev.record()
                 with trace.span("app.d2h", images=len(idxs)):
                     if not m.is_cuda:
-                        return m.numpy(), (f.numpy() if flows_needed else None)
+                        tabs = runner.measure(m, batch) if measure_needed else None
+                        return m.numpy(), (f.numpy() if flows_needed else None), tabs
                     if getattr(self, "_d2h_stream", None) is None:
                         self._d2h_stream = torch.cuda.Stream(m.device)
                     st = self._d2h_stream
@@ -383,16 +395,34 @@ class CellposeFinetune:
                             oh = torch.empty(1, dtype=torch.bool, pin_memory=True)
                             oh.copy_(over, non_blocking=True)
                         fh = f.to("cpu", non_blocking=True) if flows_needed else None
+                        rh = None
+                        if measure_needed:
+                            # on the copy stream, behind the masks' ready event and outside the network
+                            # lock: the staged batch and the masks are still on the device, the
+                            # tables come back in the same synchronisation as the masks
+                            from bioengine_worker_amd.cellpose.pipeline import as_batch, measure_launch
+
+                            raws = measure_launch(m, as_batch(batch, runner.nchan, m.device),
+                                                  nlab=getattr(m, "label_bound", None))
+                            rh = {k: v.to("cpu", non_blocking=True) for k, v in raws.items()}
+                            for t in list(raws.values()) + [batch]:
+                                t.record_stream(st)
                         for t in (m, m16) + ((over,) if over is not None else ()) + ((f,) if f is not None else ()):
                             t.record_stream(st)
                     st.synchronize()
-                    if oh is not None and bool(oh[0]):  # more than 65535 objects in an image: int32 labels
-                        return m.cpu().numpy(), (fh.numpy() if fh is not None else None)
-                    return mh.numpy().view(np.uint16), (fh.numpy() if fh is not None else None)
+                    tabs = None
+                    if rh is not None:
+                        from bioengine_worker_amd.cellpose.pipeline import measure_tables
 
-            masks, flows = await offload(run)
+                        tabs = measure_tables(rh)
+                    if oh is not None and bool(oh[0]):  # more than 65535 objects in an image: int32 labels
+                        return m.cpu().numpy(), (fh.numpy() if fh is not None else None), tabs
+                    return mh.numpy().view(np.uint16), (fh.numpy() if fh is not None else None), tabs
+
+            masks, flows, tabs = await offload(run)
             for j, i in enumerate(idxs):
-                out[i] = (masks[j], flows[j] if flows is not None and reqs[i][3] else None)
+                want = tabs is not None and len(reqs[i]) > 4 and reqs[i][4]
+                out[i] = (masks[j], flows[j] if flows is not None and reqs[i][3] else None, tabs[j] if want else None)
         return out
 
     def _stage_batch(self, images: list, runner):
@@ -451,11 +481,17 @@ class CellposeFinetune:
                                                "unused; not with stitch_threshold > 0)."),
         anisotropy: float | None = Field(None, description="do_3D: z spacing / xy spacing; the volume is resampled "
                                                            "along z by this factor before the views run."),
+        return_measurements: bool = Field(False, description="Also return per-cell measurements (area, centroid, "
+                                                             "box, shape, per-channel intensity) and the median "
+                                                             "cell diameter in pixels."),
     ) -> list:
-        """Segment images; returns one {input_path, output(, flows)} per image.  With ``z_axis``,
+        """Segment images; returns one {input_path, output(, flows)(, measurements, diameter_px)} per image.  With ``z_axis``,
         ``stitch_threshold > 0`` or ``do_3D`` every input array is one z-stack and ``output`` is
         [Z, H, W].  ``do_3D`` with ``return_flows``: ``flows`` is [per-plane RGB of (dY, dX), dP
-        [3, Z', H, W] (dZ, dY, dX), cellprob [Z', H, W]], ``Z'`` the depth after ``anisotropy``."""
+        [3, Z', H, W] (dZ, dY, dX), cellprob [Z', H, W]], ``Z'`` the depth after ``anisotropy``.
+        ``return_measurements``: ``measurements`` is the table of ``reference.derive_measurements`` (one
+        row per label of ``output``; a z-stack is measured as one volume against the stack as given)
+        and ``diameter_px`` the median cell diameter, the value ``diameter`` expects."""
         if isinstance(artifact, dict):
             w = artifact
             artifact = w.get("artifact", w.get("artifact_id", w.get("id")))
@@ -467,6 +503,8 @@ class CellposeFinetune:
             json_safe, enable_clahe = w.get("json_safe", json_safe), w.get("enable_clahe", enable_clahe)
             stitch_threshold, z_axis = w.get("stitch_threshold", stitch_threshold), w.get("z_axis", z_axis)
             do_3D, anisotropy = w.get("do_3D", do_3D), w.get("anisotropy", anisotropy)
+            return_measurements = w.get("return_measurements", return_measurements)
+        return_measurements = bool(_opt(return_measurements) or False)
         stitch_threshold = float(_opt(stitch_threshold) or 0.0)
         z_axis = _opt(z_axis)
         if not 0.0 <= stitch_threshold <= 1.0:
@@ -499,7 +537,7 @@ class CellposeFinetune:
                "cellprob_threshold": float(cellprob_threshold), "niter": int(_opt(niter) or 200)}
         if stack_mode:
             out = await self._infer_stacks(runner, names, images, prm, stitch_threshold, int(z_axis or 0),
-                                           bool(return_flows), bool(json_safe), do_3D, anisotropy)
+                                           bool(return_flows), bool(json_safe), do_3D, anisotropy, return_measurements)
             if self._weights.get(model_id) == "random" and out:
                 out[0]["weights"] = "random"
             return out
@@ -507,12 +545,15 @@ class CellposeFinetune:
         chw = [image_for_batch(im, runner.nchan, on_gpu) for im in images]
         with trace.span("app.batched", images=len(chw)):
             if len(chw) == 1:
-                res = [await self._segment_batch((model_id, chw[0], prm, bool(return_flows)))]
+                res = [await self._segment_batch((model_id, chw[0], prm, bool(return_flows), return_measurements))]
             else:
-                res = await asyncio.gather(*[self._segment_batch((model_id, c, prm, bool(return_flows))) for c in chw])
+                res = await asyncio.gather(*[self._segment_batch((model_id, c, prm, bool(return_flows),
+                                                                  return_measurements)) for c in chw])
         out = []
-        for name, (m, f) in zip(names, res):
+        for name, (m, f, tab) in zip(names, res):
             item = {"input_path": name, "output": mask_png_payload(m) if json_safe else m}
+            if return_measurements:
+                item.update(measurement_items(tab, bool(json_safe)))
             if return_flows:
                 fl = [flow_rgb(f[:2]), f[:2], f[2]]
                 item["flows"] = [x.tolist() for x in fl] if json_safe else fl
@@ -523,7 +564,7 @@ class CellposeFinetune:
 
     async def _infer_stacks(self, runner, names: list, stacks: list, prm: dict, stitch_threshold: float, z_axis: int,
                             return_flows: bool, json_safe: bool, do_3D: bool = False,
-                            anisotropy: float | None = None) -> list:
+                            anisotropy: float | None = None, return_measurements: bool = False) -> list:
         """Stack mode of :meth:`infer`: every array is one z-stack ([Z,H,W], [Z,C,H,W] or [Z,H,W,C] once
         ``z_axis`` is moved to the front); its planes are one batch of ``runner.eval_stack`` (no
         continuous batching across requests), stitched on the device.  ``do_3D`` routes the stack to
@@ -546,13 +587,17 @@ class CellposeFinetune:
                         m, f, _ = runner.eval_3d(a, anisotropy=anisotropy, **prm)
                     else:
                         m, f, _ = runner.eval_stack(a, stitch_threshold=stitch_threshold, **prm)
+                    # the final labels as one volume, against the stack as given (not resampled)
+                    tab = runner.measure(m, a, volume=True) if return_measurements else None
                     m = m.cpu().numpy()
-                    return m, (f.cpu().numpy() if return_flows else None)
+                    return m, (f.cpu().numpy() if return_flows else None), tab
 
             with trace.span("app.stack_eval", planes=int(a.shape[0])):
-                m, f = await offload(run)
+                m, f, tab = await offload(run)
             m = m.astype(np.uint16) if int(m.max(initial=0)) < 65536 else m.astype(np.int32)
             item = {"input_path": name, "output": [mask_png_payload(pl) for pl in m] if json_safe else m}
+            if return_measurements:
+                item.update(measurement_items(tab, json_safe))
             if return_flows:
                 if do_3D:  # f [4, Z', H, W] (dZ, dY, dX, cellprob)
                     fl = [np.stack([flow_rgb(f[1:3, z]) for z in range(f.shape[1])]), f[:3], f[3]]

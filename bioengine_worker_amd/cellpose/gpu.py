@@ -1,6 +1,6 @@
 """GPU (HIP) implementation of Cellpose pre/post-processing on batches of images.
 
-Every heavy step is a kernel in ``csrc/kernels/{tiles,cellpose_dynamics,cellpose_dynamics3d,cellpose_masks,cellpose_stitch}.hip``;
+Every heavy step is a kernel in ``csrc/kernels/{tiles,cellpose_dynamics,cellpose_dynamics3d,cellpose_masks,cellpose_stitch,cellpose_measure}.hip``;
 torch is only used for tiny bookkeeping (sorting the seed keys, prefix sums over labels, building
 per-mask job lists).  The semantics are those of :mod:`bioengine_worker_amd.cellpose.reference`
 (the CPU oracle), which the GPU tests compare against.
@@ -608,7 +608,9 @@ def compute_masks_gpu(y: torch.Tensor, niter: int = 200, cellprob_threshold: flo
         qc_keep[:, 0] = False
         M = torch.gather(qc_keep.to(torch.int32), 1, M.reshape(M.shape[0], -1).long()).reshape(M.shape) * M
         fill_keep &= qc_keep
-    return _fill_run(M.contiguous(), _rank_lut(fill_keep), nlab, plans[-1])
+    out = _fill_run(M.contiguous(), _rank_lut(fill_keep), nlab, plans[-1])
+    out.label_bound = nlab  # labels + 1 never exceed it: measure_masks_gpu(nlab=...) then plans without a sync
+    return out
 
 
 # ------------------------------------------------------------------ z-stacks
@@ -865,3 +867,111 @@ def compute_masks3d_gpu(dP, cellprob=None, niter: int = 200, cellprob_threshold:
     if nlab <= 1:
         return M
     return fill_holes3d_gpu(M, min_size, nlab)
+
+
+# ------------------------------------------------------------------ per-label measurements
+
+MEASURE_BAND_PX = 1024  # BAND_PX of cellpose_measure.hip
+_MEASURE_INT_FIELDS = ("area", "sum_z", "sum_y", "sum_x", "sum_yy", "sum_xx", "sum_xy", "boundary")
+
+
+def _check_measure(B: int, Z: int, H: int, W: int, volume: bool) -> None:
+    """The second coordinate sums are 64-bit: ``y * y * area`` stays below 2^63 up to 2^15 rows and
+    columns.  Offsets inside one volume are 32-bit."""
+    if volume:
+        if Z * H * W >= 2 ** 31:
+            raise ValueError(f"measure_masks_gpu: volume {Z} x {H} x {W} is too large (Z*H*W must be below 2^31)")
+    elif max(H, W) > 2 ** 15:
+        raise ValueError(f"measure_masks_gpu: image {H} x {W} is too large (H and W must not exceed 2^15)")
+
+
+def _measure_oracle(M, img, K: int, volume: bool, outlines: bool) -> dict:
+    """CPU tensors: :func:`reference.measure_masks` per image, rows padded to ``K``."""
+    Ms = [M] if volume else list(M)
+    rows = []
+    for b, m in enumerate(Ms):
+        im = None
+        if img is not None:
+            im = (img.permute(1, 0, 2, 3) if volume else img[b]).numpy()
+        raw = ref.measure_masks(m.numpy(), im, outlines)
+        out = {}
+        for k, v in raw.items():
+            t = torch.from_numpy(np.ascontiguousarray(v))
+            if k != "outlines":
+                t = t[:K]
+                t = torch.cat([t, torch.zeros((K - t.shape[0],) + tuple(t.shape[1:]), dtype=t.dtype)])
+            out[k] = t
+        rows.append(out)
+    return rows[0] if volume else {k: torch.stack([r[k] for r in rows]) for k in rows[0]}
+
+
+def measure_masks_gpu(M: torch.Tensor, img: torch.Tensor | None = None, nlab: int | None = None, volume: bool = False,
+                      outlines: bool = False) -> dict:
+    """Raw per-label measurements of label images on the device: HIP implementation of
+    :func:`reference.measure_masks` (``csrc/kernels/cellpose_measure.hip``), exactly equal to it in
+    every integer field, box, minimum, maximum and outline, and bit-identical from run to run in
+    every field.
+
+    ``M`` [B, H, W] labels with ``img`` [B, C, H, W] or None; with ``volume=True`` ``M`` is one
+    [Z, H, W] volume and ``img`` [Z, C, H, W].  Returns the oracle's fields as device tensors
+    [B, K, ...] ([K, ...] for a volume; ``outlines`` [B, H, W] / [Z, H, W] bool), with ``K`` the
+    largest label of the batch; rows above an image's own maximum are zero.  ``nlab``: optional
+    upper bound on the labels + 1, as the sibling wrappers take it (``K = nlab - 1``; saves the
+    ``M.max()`` sync -- nothing else is read back; labels above the bound are not measured).
+    Runs on the current stream.  CPU tensors run the oracle."""
+    if M.dim() != 3:
+        raise ValueError(f"measure_masks_gpu expects [B, H, W] masks (or one [Z, H, W] volume), got {tuple(M.shape)}")
+    (B, Z), (H, W) = ((1, M.shape[0]) if volume else (M.shape[0], 1)), M.shape[1:]
+    _check_measure(B, Z, H, W, volume)
+    C = 0
+    if img is not None:
+        if img.dim() != 4 or img.shape[0] != M.shape[0] or tuple(img.shape[2:]) != (H, W):
+            raise ValueError(f"measure_masks_gpu: image {tuple(img.shape)} does not fit masks {tuple(M.shape)}")
+        C = img.shape[1]
+    dev = M.device
+    if nlab is None:
+        nlab = int(M.max().item()) + 1 if M.numel() else 1
+    K = max(int(nlab) - 1, 0)
+    if dev.type != "cuda":
+        return _measure_oracle(M, img.float() if img is not None else None, K, volume, outlines)
+    Mc = M.to(torch.int32).contiguous()
+    imc = img.float().contiguous() if img is not None and C > 0 else None
+    lead = () if volume else (B,)
+    out_i = torch.empty(B, K, len(_MEASURE_INT_FIELDS), dtype=torch.int64, device=dev)
+    out_box = torch.empty(B, K, 6, dtype=torch.int32, device=dev)
+    out_f = torch.empty(B, K, C, 2, dtype=torch.float64, device=dev)
+    out_m = torch.empty(B, K, C, 2, dtype=torch.float32, device=dev)
+    edge = torch.zeros(Mc.shape, dtype=torch.uint8, device=dev) if outlines else None
+    if K > 0 and Mc.numel() > 0:
+        # job slots per image: one per label plus 2 * s_half bands (see the kernel file's header)
+        s_half = 2 * (-(-Z * H * W // MEASURE_BAND_PX)) + 32
+        slots = K + 2 * s_half
+        # one workspace, 8-byte fields first: band size, partial integers and sums, job list, then
+        # the 4-byte ones: partial min / max, boxes, offsets, band counts, job counts
+        n8 = B + B * slots * (len(_MEASURE_INT_FIELDS) + 2 * C + 1)
+        n4 = B * slots * 2 * C + B * K * 8 + B
+        ws = torch.empty(n8 + (n4 + 1) // 2, dtype=torch.int64, device=dev)
+        w8 = ws[:n8].split([B, B * slots * len(_MEASURE_INT_FIELDS), B * slots * 2 * C, B * slots])
+        bandpx, part_i, part_f, jobs = w8[0], w8[1], w8[2].view(torch.float64), w8[3]
+        w4 = ws[n8:].view(torch.int32)[:n4].split([B * slots * 2 * C, B * K * 6, B * K, B * K, B])
+        part_m, bbox, off, nb, njobs = w4[0].view(torch.float32), w4[1], w4[2], w4[3], w4[4]
+        _native.call("be_cp_measure", _native.ptr(Mc), _native.ptr(imc), B, Z, H, W, C, K, int(bool(volume)), slots, s_half,
+                     _native.ptr(bbox), _native.ptr(off), _native.ptr(nb), _native.ptr(jobs), _native.ptr(njobs),
+                     _native.ptr(bandpx), _native.ptr(part_i), _native.ptr(part_f), _native.ptr(part_m),
+                     _native.ptr(out_i), _native.ptr(out_box), _native.ptr(out_f), _native.ptr(out_m), _native.ptr(edge),
+                     _native.stream(dev))
+    else:
+        for t in (out_i, out_box, out_f, out_m):
+            t.zero_()
+    res = {}
+    for j, name in enumerate(_MEASURE_INT_FIELDS):
+        if name in (("sum_yy", "sum_xx", "sum_xy") if volume else ("sum_z",)):
+            continue
+        res[name] = out_i[..., j].reshape(lead + (K,))
+    res["bbox"] = (out_box if volume else out_box[..., [1, 2, 4, 5]]).reshape(lead + (K, 6 if volume else 4))
+    if img is not None:
+        res["int_sum"], res["int_sumsq"] = (out_f[..., j].reshape(lead + (K, C)) for j in (0, 1))
+        res["int_min"], res["int_max"] = (out_m[..., j].reshape(lead + (K, C)) for j in (0, 1))
+    if outlines:
+        res["outlines"] = edge.bool()
+    return res

@@ -601,6 +601,63 @@ class CellposeRunner:
             out.append(torch.from_numpy(m.astype(np.int32)))
         return torch.stack(out)
 
+    # ---------------------------------------------------------------- measurements
+    def measure(self, masks, images=None, volume: bool = False):
+        """Per-cell measurement tables (:func:`reference.derive_measurements`) of label images.
+
+        ``masks``: [B, H, W] (or one [H, W] image), as :meth:`eval` returns them; with ``volume=True``
+        one [Z, H, W] volume, as :meth:`eval_stack` / :meth:`eval_3d` return it.  ``images``: what was
+        segmented (any form :meth:`eval` / :meth:`eval_stack` takes) or None for the geometry alone;
+        its channels are padded or cut to the network's, and it is *not* normalised: intensities are in
+        the caller's units.  Returns a list with one table (a dict of numpy arrays plus ``n_cells`` and
+        ``diameter_px``) per image, or the one table of a volume.  Masks on the GPU are measured by
+        the HIP kernel (:func:`gpu.measure_masks_gpu`), everything else by the numpy oracle."""
+        m = masks if torch.is_tensor(masks) else torch.as_tensor(np.asarray(masks))
+        if m.dim() == 2 and not volume:
+            m = m[None]
+        if m.dim() != 3:
+            raise ValueError(f"measure expects [B, H, W] masks or one [Z, H, W] volume, got shape {tuple(m.shape)}")
+        img = None
+        if images is not None:
+            img = as_batch(_planes_first(images) if volume else images, self.nchan, m.device)
+            if img.shape[0] != m.shape[0] or img.shape[2:] != m.shape[1:]:
+                raise ValueError(f"measure: images {tuple(img.shape)} do not fit masks {tuple(m.shape)}")
+        raws = measure_launch(m, img, volume=volume)
+        return measure_tables(raws, volume)
+
+
+def _planes_first(stack) -> torch.Tensor:
+    """[Z, H, W], [Z, C, H, W] or [Z, H, W, C] -> [Z, C, H, W], as eval_stack reads a z-stack."""
+    x = torch.as_tensor(np.asarray(stack) if not torch.is_tensor(stack) else stack)
+    if x.dim() == 3:
+        return x[:, None]
+    if x.dim() == 4:
+        return x.permute(0, 3, 1, 2) if x.shape[-1] <= 4 and x.shape[1] > 4 else x
+    raise ValueError(f"a z-stack is [Z,H,W], [Z,C,H,W] or [Z,H,W,C], got shape {tuple(x.shape)}")
+
+
+def measure_launch(m: torch.Tensor, img: torch.Tensor | None, volume: bool = False, nlab: int | None = None) -> dict:
+    """Raw measurement fields of masks ``m`` [B, H, W] (or one [Z, H, W] volume) with ``img``
+    [B or Z, C, H, W] on the same device, as tensors on that device: the HIP kernel on the GPU (queued
+    on the current stream, nothing waited for when ``nlab`` is given), the numpy oracle elsewhere."""
+    from .gpu import measure_masks_gpu
+
+    return measure_masks_gpu(m, img, nlab=nlab, volume=volume)
+
+
+def measure_tables(raws: dict, volume: bool = False):
+    """Host side of :meth:`CellposeRunner.measure`: raw fields (tensors or arrays, [B, K, ...] or
+    [K, ...] for a volume) -> one table per image, each cut to its image's own largest label."""
+    host = {k: (v.cpu().numpy() if torch.is_tensor(v) else np.asarray(v)) for k, v in raws.items()}
+    if volume:
+        host = {k: v[None] for k, v in host.items()}
+    tables = []
+    for b in range(host["area"].shape[0]):
+        present = np.nonzero(host["area"][b] > 0)[0]
+        kb = int(present[-1]) + 1 if present.size else 0
+        tables.append(ref.derive_measurements({k: (v[b] if k == "outlines" else v[b, :kb]) for k, v in host.items()}))
+    return tables[0] if volume else tables
+
 
 def mask_stream(device) -> "torch.cuda.Stream":
     """The second stream mask recovery runs on, beside the next batch's network.

@@ -482,3 +482,144 @@ def compute_masks3d(dP, cellprob, niter=200, cellprob_threshold=0.0, min_size=15
     p, inds = follow_flows3d(dP, cellprob, cellprob_threshold, niter)
     mask = get_masks3d(p, inds, cellprob.shape, max_size_fraction=max_size_fraction)
     return fill_holes_and_remove_small_masks3d(mask, min_size)
+
+
+# ------------------------------------------------------------------ per-label measurements
+
+
+def measure_masks(masks, image=None, outlines: bool = False) -> dict:
+    """Raw per-label measurements of a label image: the specification of
+    ``csrc/kernels/cellpose_measure.hip``, which the GPU tests compare with exactly.  (cellpose and
+    scikit-image are not installed: the rules below are this project's own.)
+
+    ``masks``: [H, W] or [Z, H, W] integer labels (0 = background); ``image``: [C, H, W] or
+    [C, Z, H, W] float32 intensities on the same grid, or None.  ``K = masks.max()``; every array
+    has one row per label ``1..K`` (row ``l - 1`` is label ``l``) and a label without pixels has
+    zeros everywhere.  Coordinates are array indices.
+
+    ``area``                        int64    pixels (voxels) of the label
+    ``sum_y``, ``sum_x``            int64    coordinate sums (3-D: also ``sum_z``)
+    ``sum_yy``, ``sum_xx``, ``sum_xy``  int64    second coordinate sums, 2-D only
+    ``bbox``                        int32    half-open box: ``(y0, x0, y1, x1)`` in 2-D,
+                                             ``(z0, y0, x0, z1, y1, x1)`` in 3-D
+    ``boundary``                    int64    pixels of the label with at least one 4-neighbour
+                                             (6-neighbour in 3-D) that lies outside the array or
+                                             carries a different label (background included)
+    ``int_sum``, ``int_sumsq``      float64  [K, C]: sum of ``x`` and of ``x * x`` over the label,
+                                             both taken in float64 (the square of a float32 is exact)
+    ``int_min``, ``int_max``        float32  [K, C], exact
+
+    The intensity fields exist only with an ``image``.  ``outlines=True`` adds ``outlines``: a bool
+    array of the masks' shape, true at exactly the pixels that ``boundary`` counts."""
+    m = np.asarray(masks)
+    if m.ndim not in (2, 3):
+        raise ValueError(f"measure_masks expects [H, W] or [Z, H, W] labels, got shape {m.shape}")
+    m = m.astype(np.int64)
+    nd = m.ndim
+    K = max(int(m.max()), 0) if m.size else 0
+    # boundary pixels: compare with each axis neighbour; outside the array counts as different
+    pad = np.pad(m, 1, constant_values=-1)
+    edge = np.zeros(m.shape, bool)
+    for ax in range(nd):
+        for start in (0, 2):
+            sl = [slice(1, -1)] * nd
+            sl[ax] = slice(start, start + m.shape[ax])
+            edge |= pad[tuple(sl)] != m
+    edge &= m > 0
+    idx = np.nonzero(m > 0)
+    row = m[idx] - 1
+
+    def total(values, dtype=np.int64):
+        out = np.zeros(K, dtype)
+        np.add.at(out, row, np.asarray(values, dtype))
+        return out
+
+    raw = {"area": total(np.ones(row.shape, np.int64))}
+    names = ("z", "y", "x")[3 - nd:]
+    for name, c in zip(names, idx):
+        raw["sum_" + name] = total(c)
+    if nd == 2:
+        y, x = idx
+        raw["sum_yy"], raw["sum_xx"], raw["sum_xy"] = total(y * y), total(x * x), total(x * y)
+    present = raw["area"] > 0
+    lo = np.full((K, nd), np.iinfo(np.int64).max)
+    hi = np.full((K, nd), -1)
+    for d, c in enumerate(idx):
+        np.minimum.at(lo[:, d], row, c)
+        np.maximum.at(hi[:, d], row, c)
+    raw["bbox"] = np.where(present[:, None], np.concatenate([lo, hi + 1], 1), 0).astype(np.int32)
+    raw["boundary"] = total(edge[idx])
+    if image is not None:
+        img = np.asarray(image)
+        if img.ndim != nd + 1 or img.shape[1:] != m.shape:
+            raise ValueError(f"measure_masks: image {img.shape} does not match masks {m.shape} (channels first)")
+        img = img.astype(np.float32)
+        C = img.shape[0]
+        raw["int_sum"], raw["int_sumsq"] = np.zeros((K, C)), np.zeros((K, C))
+        raw["int_min"], raw["int_max"] = np.zeros((K, C), np.float32), np.zeros((K, C), np.float32)
+        for c in range(C):
+            v = img[c][idx]
+            v64 = v.astype(np.float64)
+            raw["int_sum"][:, c] = total(v64, np.float64)
+            raw["int_sumsq"][:, c] = total(v64 * v64, np.float64)
+            mn, mx = np.full(K, np.inf, np.float32), np.full(K, -np.inf, np.float32)
+            np.minimum.at(mn, row, v)
+            np.maximum.at(mx, row, v)
+            raw["int_min"][:, c] = np.where(present, mn, 0)
+            raw["int_max"][:, c] = np.where(present, mx, 0)
+    if outlines:
+        raw["outlines"] = edge
+    return raw
+
+
+def derive_measurements(raw: dict) -> dict:
+    """Raw fields of :func:`measure_masks` (one image) -> the measurement table.  The only place
+    where derived values are computed: the CPU and the GPU path both end here.  All in float64;
+    a label without pixels has zeros everywhere.
+
+    ``label`` ``1..K``; ``area``, ``bbox``, ``boundary`` (and ``int_min``, ``int_max``, and
+    ``outlines`` when present) are passed through.  ``centroid`` [K, 2] (y, x) or [K, 3] (z, y, x)
+    ``= sum / area``; ``equivalent_diameter = sqrt(4 area / pi)`` in 2-D, ``cbrt(6 area / pi)`` in
+    3-D.  2-D only, from the central moments ``myy = sum_yy / area - cy^2`` (``mxx``, ``mxy``
+    likewise) and the eigenvalues ``l1 >= l2 >= 0`` (clamped at 0) of ``[[myy, mxy], [mxy, mxx]]``:
+    ``axis_major = 4 sqrt(l1)``, ``axis_minor = 4 sqrt(l2)``, ``eccentricity = sqrt(1 - l2 / l1)``
+    (0 when ``l1 = 0``), ``orientation = 0.5 atan2(2 mxy, mxx - myy)``.  With intensities:
+    ``int_mean = int_sum / area``, ``int_std = sqrt(max(int_sumsq / area - int_mean^2, 0))``.
+    Image level: ``n_cells`` = labels with ``area > 0``; ``diameter_px`` = the median over those
+    labels of ``sqrt(area)``, times ``2 / sqrt(pi)`` (0.0 without labels) -- the definition
+    cellpose's ``utils.diameters`` uses, i.e. the value its ``diameter`` argument expects."""
+    area_i = np.asarray(raw["area"]).astype(np.int64)
+    K = area_i.shape[0]
+    present = area_i > 0
+    area = area_i.astype(np.float64)
+    a = np.where(present, area, 1.0)
+    vol = "sum_z" in raw
+    out = {"label": np.arange(1, K + 1, dtype=np.int32), "area": area_i, "bbox": np.asarray(raw["bbox"]),
+           "boundary": np.asarray(raw["boundary"]).astype(np.int64)}
+    names = ("z", "y", "x") if vol else ("y", "x")
+    cen = [np.asarray(raw["sum_" + n]).astype(np.float64) / a for n in names]
+    out["centroid"] = np.stack(cen, 1) if K else np.zeros((0, len(names)))
+    if vol:
+        out["equivalent_diameter"] = np.cbrt(6.0 * area / np.pi)
+    else:
+        out["equivalent_diameter"] = np.sqrt(4.0 * area / np.pi)
+        cy, cx = cen
+        myy = np.asarray(raw["sum_yy"]).astype(np.float64) / a - cy * cy
+        mxx = np.asarray(raw["sum_xx"]).astype(np.float64) / a - cx * cx
+        mxy = np.asarray(raw["sum_xy"]).astype(np.float64) / a - cx * cy
+        half = 0.5 * (myy + mxx)
+        root = np.sqrt((0.5 * (myy - mxx)) ** 2 + mxy * mxy)
+        l1, l2 = np.maximum(half + root, 0.0), np.maximum(half - root, 0.0)
+        out["axis_major"], out["axis_minor"] = 4.0 * np.sqrt(l1), 4.0 * np.sqrt(l2)
+        out["eccentricity"] = np.where(l1 > 0, np.sqrt(np.maximum(1.0 - l2 / np.where(l1 > 0, l1, 1.0), 0.0)), 0.0)
+        out["orientation"] = np.where(present, 0.5 * np.arctan2(2.0 * mxy, mxx - myy), 0.0)
+    if "int_sum" in raw:
+        mean = np.asarray(raw["int_sum"], np.float64) / a[:, None]
+        out["int_mean"] = mean
+        out["int_std"] = np.sqrt(np.maximum(np.asarray(raw["int_sumsq"], np.float64) / a[:, None] - mean * mean, 0.0))
+        out["int_min"], out["int_max"] = np.asarray(raw["int_min"]), np.asarray(raw["int_max"])
+    if "outlines" in raw:
+        out["outlines"] = np.asarray(raw["outlines"])
+    out["n_cells"] = int(present.sum())
+    out["diameter_px"] = float(np.median(np.sqrt(area[present])) * 2.0 / np.sqrt(np.pi)) if present.any() else 0.0
+    return out
