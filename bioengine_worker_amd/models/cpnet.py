@@ -360,6 +360,10 @@ class CPnetEngine:
             has_x2 = key[0] == "up" and key[2] == 0
             res = "none" if key == ("down", 0, 0) else ("up2" if has_x2 else "full")
             assert sp.supports(has_x2, res), key
+            # fragment-order weights of the level-1 ping-pong kernel: packed here, not in the first forward
+            if (sp.cin, sp.cm, sp.inmode, has_x2, sp.pp is not None, res) in pairops.FRAG_CONFIGS \
+                    and torch.device(self.device).type == "cuda":
+                sp.frag(sp.pa.wp.device)
         return pairs
 
     def _build_igemm(self, net: CPnet) -> dict:

@@ -34,6 +34,31 @@ SUPPORTED = {
     (128, 64, "up2", True, False, "up2"),
 }
 RESMODES = {"none": 0, "full": 1, "up2": 2}
+#: configurations with a CM = 64 ping-pong build (``conv_pair_pp64.inc``): these calls also pass the
+#: weights in MFMA-fragment order (:func:`pack_frag`)
+FRAG_CONFIGS = {
+    (64, 64, "none", False, False, "full"),
+    (32, 64, "pool2", False, False, "full"),
+    (128, 64, "up2", True, False, "up2"),
+}
+
+
+def pack_frag(wp: torch.Tensor) -> torch.Tensor:
+    """``PackedConv.wp`` ``[64, nchunk, 288]`` (K index = tap * 32 + c) in MFMA-A-fragment order
+    ``[nchunk, 9 taps, 4 channel tiles, 64 lanes, 8]``: lane ``kq * 16 + lrow`` of channel tile ``ct``
+    holds ``wp[ct * 16 + lrow, chunk, tap * 32 + kq * 8 : ... + 8]``, the operand registers of one
+    ``v_mfma_f32_16x16x32_bf16``, so a wave fetches a fragment with one 16-byte-per-lane load."""
+    cout, nchunk, kp = wp.shape
+    assert cout == 64 and kp == 288, "fragment packing: 64 output channels, 3x3 taps of 32-channel chunks"
+    t = wp.reshape(4, 16, nchunk, 9, 4, 8)          # ct, lrow, chunk, tap, kq, e
+    return t.permute(2, 3, 0, 4, 1, 5).contiguous().reshape(nchunk, 9, 4, 64, 8)
+
+
+def unpack_frag(wf: torch.Tensor) -> torch.Tensor:
+    """Inverse of :func:`pack_frag`."""
+    nchunk = wf.shape[0]
+    t = wf.reshape(nchunk, 9, 4, 4, 16, 8)          # chunk, tap, ct, kq, lrow, e
+    return t.permute(2, 4, 0, 1, 3, 5).contiguous().reshape(64, nchunk, 288)
 
 
 @dataclass
@@ -55,6 +80,16 @@ class PairSpec:
     pp: PackedConv | None = None
     sp: torch.Tensor | None = None
     tp: torch.Tensor | None = None
+    #: fragment-order copies of ``pa.wp`` / ``pb.wp`` per device, built on first use (:meth:`frag`)
+    frag_cache: dict | None = None
+
+    def frag(self, device: torch.device) -> tuple[torch.Tensor, torch.Tensor]:
+        """``(pack_frag(pa.wp), pack_frag(pb.wp))`` on ``device``; packed once and kept with the spec
+        (repacked if the packed weights were replaced)."""
+        key = (str(device), self.pa.wp.data_ptr(), self.pb.wp.data_ptr())
+        if self.frag_cache is None or self.frag_cache.get("key") != key:
+            self.frag_cache = {"key": key, "w": (pack_frag(self.pa.wp.to(device)), pack_frag(self.pb.wp.to(device)))}
+        return self.frag_cache["w"]
 
     @property
     def cm(self) -> int:
@@ -157,13 +192,16 @@ def conv_pair(x: torch.Tensor, spec: PairSpec, *, ta=None, tb=None, x2=None, res
     ta_ns = _affine_stride(ta, N, Cin)
     tb_ns = _affine_stride(tb, N, CM)
     pp = spec.pp
-    rc = _native.call(
-        "be_conv_pair",
+    waf = wbf = None
+    if (Cin, CM, spec.inmode, x2 is not None, pp is not None, res_mode) in FRAG_CONFIGS:
+        waf, wbf = spec.frag(x.device)
+    _native.call(
+        "be_conv_pair_frag",
         _native.ptr(x), _native.ptr(x2), _native.ptr(spec.sa), _native.ptr(ta), ta_ns, _native.ptr(spec.sb),
         _native.ptr(tb), tb_ns, _native.ptr(spec.sp), _native.ptr(spec.tp), _native.ptr(spec.pa.wp),
         _native.ptr(spec.pb.wp), _native.ptr(None if pp is None else pp.wp), _native.ptr(spec.bias),
         _native.ptr(res), _native.ptr(out), N, H, W, Hs, Ws, Cin, CM, INMODES[spec.inmode], int(pp is not None),
-        RESMODES[res_mode], _native.stream(x.device),
+        RESMODES[res_mode], _native.ptr(waf), _native.ptr(wbf), _native.stream(x.device),
     )
     return out
 

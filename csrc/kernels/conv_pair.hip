@@ -29,6 +29,11 @@
 //  * CM = 32: every weight panel stays resident in LDS for the whole launch; CM = 64: one weight
 //    chunk buffer, the next chunk's weights and the next A chunk's halo are prefetched into
 //    registers while the current chunk's MFMAs run ("issue early, write late").
+//  * Calls with two tiles or more per workgroup run on the two-group ping-pong kernels instead
+//    (one group's VALU / LDS-store phases beside the other's MFMAs): conv_pair_pp_kernel below
+//    for CM = 32 (16 x 32 tiles, weights resident in LDS), conv_pair_pp64.inc for CM = 64
+//    (16 x 16 tiles, weights fetched from L2 in MFMA-fragment order, 81 KB of LDS).  The
+//    one-group kernel keeps the small calls (batch-1 latency).  All three give the same bits.
 //  * pixel strides are 8 (mod 16) dwords, so ds_read_b128 fragment reads are conflict-free for any
 //    tap offset (same rule as conv2d_nhwc.hip).
 #include <cstdlib>
@@ -47,6 +52,7 @@ struct PairArgs {
   const bf16_t* wb;                             // [CM][CM/32][288]
   const bf16_t* wp;                             // [CM][1][32]
   const float* bias;                            // [CM] convB bias (+ projection bias)
+  const bf16_t* waf; const bf16_t* wbf;         // wa / wb in MFMA-fragment order (conv_pair_pp64.inc), or null
   const bf16_t* res;                            // [N, H, W, CM] or [N, H/2, W/2, CM] (RES = 2)
   bf16_t* out;                                  // [N, H, W, CM]
   // HEAD (final up half-block only): the network's output conv fused into the epilogue,
@@ -63,16 +69,12 @@ struct PairArgs {
   unsigned long long* stamps;
 };
 
-// The one-group kernel and its helpers, once per tile geometry (conv_pair_onegroup.inc).
+// The one-group kernel and its helpers on the 16 x 32 tile geometry (conv_pair_onegroup.inc).
 namespace g32 {
 constexpr int TW = 32, TH = 16, NW = 8;
 #include "conv_pair_onegroup.inc"
 }  // namespace g32
-namespace g12 {
-constexpr int TW = 16, TH = 12, NW = 4;
-#include "conv_pair_onegroup.inc"
-}  // namespace g12
-using namespace g32;  // the ping-pong kernel and the launchers below use the 16 x 32 geometry
+using namespace g32;  // the level-0 ping-pong kernel and the launchers below use the 16 x 32 geometry
 
 unsigned long long* g_pair_stamps = nullptr;  // diagnostics: be_conv_pair_set_stamps
 int g_pair_stamps_cap = 0;                    // workgroups the stamp buffer holds
@@ -949,6 +951,35 @@ int launch_pair_pp(PairArgs a, int grid_cap, hipStream_t s) {
   hipLaunchKernelGGL((conv_pair_pp_kernel<NCA, INMODE, X2, RES, HEAD, STEM>), dim3(g), dim3(ppk::NTP), lds, s, a);
   return BE_CHECK_LAUNCH();
 }
+
+#include "conv_pair_pp64.inc"
+
+template <int NCA, int INMODE, bool X2, int RES>
+int launch_pair_pp64(PairArgs a, int grid_cap, hipStream_t s) {
+  a.tiles_x = (a.W + pp64::TS - 1) / pp64::TS;
+  a.tiles_y = (a.H + pp64::TS - 1) / pp64::TS;
+  const int tiles = a.N * a.tiles_x * a.tiles_y;
+  int g = grid_cap > 0 ? grid_cap : 256;
+  if (g > tiles) g = tiles;
+  if (g < 1) return 0;
+  a.stamps = nullptr;
+  static bool attr_set[BE_MAX_DEV] = {};
+  if (!attr_set[be_cur_dev()]) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&pp64::conv_pair_pp64_kernel<NCA, INMODE, X2, RES>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, pp64::LDS);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&pp64::conv_pair_pp64_kernel<NCA, INMODE, X2, RES, true>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, pp64::LDS);
+    attr_set[be_cur_dev()] = true;
+  }
+  if (g_pp_stamps != nullptr) {  // diagnostics: be_conv_pair_pp_set_stamps
+    if (g > g_pp_stamps_cap) return -30;
+    a.stamps = g_pp_stamps;
+    hipLaunchKernelGGL((pp64::conv_pair_pp64_kernel<NCA, INMODE, X2, RES, true>), dim3(g), dim3(pp64::NTP), pp64::LDS, s, a);
+    return BE_CHECK_LAUNCH();
+  }
+  hipLaunchKernelGGL((pp64::conv_pair_pp64_kernel<NCA, INMODE, X2, RES>), dim3(g), dim3(pp64::NTP), pp64::LDS, s, a);
+  return BE_CHECK_LAUNCH();
+}
 }  // namespace
 
 // tuning override (0 = one workgroup per CU); BE_PAIR_GRID sets it for A/B runs
@@ -963,41 +994,6 @@ static int g_pair_pp = [] {
   return e ? atoi(e) : 1;
 }();
 
-// BE_PAIR_G12 (A/B): the level-1 (CM = 64) half-blocks on the 12 x 16-tile geometry -- 4 waves and
-// <= 79 KB of LDS per workgroup, so two workgroups share each CU and one's halo / epilogue phases run
-// beside the other's MFMAs (the one-group 16 x 32 kernel leaves the MFMA pipe idle through them:
-// profiles/r04/conv/pair_phases.jsonl).  BE_PAIR_G12_GRID: workgroups (default 512).
-static int g_pair_g12 = [] {
-  const char* e = getenv("BE_PAIR_G12");
-  return e ? atoi(e) : 0;
-}();
-static int g_pair_g12_grid = [] {
-  const char* e = getenv("BE_PAIR_G12_GRID");
-  return e ? atoi(e) : 512;
-}();
-
-template <int CK, int CM, int INMODE, bool X2, int RES, int NCA>
-int launch_pair12(PairArgs a, hipStream_t s) {
-  using C = g12::PC<CK, CM, INMODE, X2, false, RES, NCA>;
-  constexpr size_t lds = C::LDS;
-  static_assert(2 * lds <= 160 * 1024, "two workgroups per CU");
-  a.tiles_x = (a.W + g12::TW - 1) / g12::TW;
-  a.tiles_y = (a.H + g12::TH - 1) / g12::TH;
-  const int tiles = a.N * a.tiles_x * a.tiles_y;
-  int g = g_pair_g12_grid > 0 ? g_pair_g12_grid : 512;
-  if (g > tiles) g = tiles;
-  if (g < 1) return 0;
-  a.stamps = nullptr;
-  constexpr auto kern = &g12::conv_pair_kernel<CK, CM, INMODE, X2, false, RES, NCA, false, false, 7>;
-  static bool attr_set[BE_MAX_DEV] = {};
-  if (!attr_set[be_cur_dev()]) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_set[be_cur_dev()] = true;
-  }
-  hipLaunchKernelGGL(kern, dim3(g), dim3(g12::NT), lds, s, a);
-  return BE_CHECK_LAUNCH();
-}
-
 // BE_PAIR_PP_STEM (default 1): the stem (8 -> 32 + projection) on the ping-pong kernel as well
 static int g_pair_pp_stem = [] {
   const char* e = getenv("BE_PAIR_PP_STEM");
@@ -1010,6 +1006,21 @@ static int g_pair_pp_stem = [] {
 static bool pp_ok(const PairArgs& a, int grid_cap) {
   if (!g_pair_pp || g_pair_stamps != nullptr) return false;
   const long long tiles = (long long)a.N * ((a.W + TW - 1) / TW) * ((a.H + TH - 1) / TH);
+  const int g = grid_cap > 0 ? grid_cap : 256;
+  return tiles >= 2LL * g;
+}
+
+// BE_PAIR_PP64 (default 1, A/B): the level-1 (CM = 64) half-blocks on the CM = 64 ping-pong kernel
+// (conv_pair_pp64.inc).  As pp_ok: only when every workgroup has a tile for each of its two groups
+// (16 x 16 tiles here) and the caller passed the fragment-order weights.
+static int g_pair_pp64 = [] {
+  const char* e = getenv("BE_PAIR_PP64");
+  return e ? atoi(e) : 1;
+}();
+
+static bool pp64_ok(const PairArgs& a, int grid_cap) {
+  if (!g_pair_pp64 || g_pair_stamps != nullptr || !a.waf || !a.wbf) return false;
+  const long long tiles = (long long)a.N * ((a.W + pp64::TS - 1) / pp64::TS) * ((a.H + pp64::TS - 1) / pp64::TS);
   const int g = grid_cap > 0 ? grid_cap : 256;
   return tiles >= 2LL * g;
 }
@@ -1054,11 +1065,15 @@ int be_conv_pair_lds(int cin, int cm, int inmode, int x2, int proj, int res) {
 //   (32,64,pool2,0,0,full) level-1 c0 + c1 + proj    (64,64,none,0,0,full) level-1 c2 + c3 + x1
 //   (128,64,up2,1,0,up2)  up level-1 c0 + c1 + skip + up2(proj)
 //   (64,32,up2,1,0,up2)   up level-0 c0 + c1 + skip + up2(proj)
-int be_conv_pair(const void* x, const void* x2, const float* sa, const float* ta, int ta_ns, const float* sb,
-                 const float* tb, int tb_ns, const float* sp, const float* tp, const void* wa, const void* wb,
-                 const void* wp, const float* bias, const void* res, void* out, int N, int H, int W, int Hs, int Ws,
-                 int Cin, int CM, int inmode, int proj, int resmode, hipStream_t stream) {
+// waf / wbf: wa / wb once more in MFMA-fragment order (ops/conv_pair.py pack_frag), or null: the
+// configurations with a CM = 64 ping-pong build read their weights from these (see pp64_ok).
+int be_conv_pair_frag(const void* x, const void* x2, const float* sa, const float* ta, int ta_ns, const float* sb,
+                      const float* tb, int tb_ns, const float* sp, const float* tp, const void* wa, const void* wb,
+                      const void* wp, const float* bias, const void* res, void* out, int N, int H, int W, int Hs,
+                      int Ws, int Cin, int CM, int inmode, int proj, int resmode, const void* waf, const void* wbf,
+                      hipStream_t stream) {
   PairArgs a;
+  a.waf = (const bf16_t*)waf; a.wbf = (const bf16_t*)wbf;
   a.x = (const bf16_t*)x; a.x2 = (const bf16_t*)x2;
   a.sa = sa; a.ta = ta; a.ta_ns = ta_ns; a.sb = sb; a.tb = tb; a.tb_ns = tb_ns; a.sp = sp; a.tp = tp;
   a.wa = (const bf16_t*)wa; a.wb = (const bf16_t*)wb; a.wp = (const bf16_t*)wp; a.bias = bias;
@@ -1084,13 +1099,27 @@ int be_conv_pair(const void* x, const void* x2, const float* sa, const float* ta
       return launch_pair_pp<2, 1, true, 2, false>(a, g, stream);
     return launch_pair<32, 32, 1, true, false, 2, 2>(a, g, stream);
   }
-  if (CM == 64 && Cin == 32 && inmode == 2 && !hx2 && !proj && resmode == 1)
-    return g_pair_g12 ? launch_pair12<32, 64, 2, false, 1, 1>(a, stream) : launch_pair<32, 64, 2, false, false, 1, 1>(a, g, stream);
-  if (CM == 64 && Cin == 64 && inmode == 0 && !hx2 && !proj && resmode == 1)
-    return g_pair_g12 ? launch_pair12<32, 64, 0, false, 1, 2>(a, stream) : launch_pair<32, 64, 0, false, false, 1, 2>(a, g, stream);
-  if (CM == 64 && Cin == 128 && inmode == 1 && hx2 && !proj && resmode == 2)
-    return g_pair_g12 ? launch_pair12<32, 64, 1, true, 2, 4>(a, stream) : launch_pair<32, 64, 1, true, false, 2, 4>(a, g, stream);
+  if (CM == 64 && Cin == 32 && inmode == 2 && !hx2 && !proj && resmode == 1) {
+    if (pp64_ok(a, g) && Hs == 2 * H && Ws == 2 * W) return launch_pair_pp64<1, 2, false, 1>(a, g, stream);
+    return launch_pair<32, 64, 2, false, false, 1, 1>(a, g, stream);
+  }
+  if (CM == 64 && Cin == 64 && inmode == 0 && !hx2 && !proj && resmode == 1) {
+    if (pp64_ok(a, g) && Hs == H && Ws == W) return launch_pair_pp64<2, 0, false, 1>(a, g, stream);
+    return launch_pair<32, 64, 0, false, false, 1, 2>(a, g, stream);
+  }
+  if (CM == 64 && Cin == 128 && inmode == 1 && hx2 && !proj && resmode == 2) {
+    if (pp64_ok(a, g) && 2 * Hs == H && 2 * Ws == W) return launch_pair_pp64<4, 1, true, 2>(a, g, stream);
+    return launch_pair<32, 64, 1, true, false, 2, 4>(a, g, stream);
+  }
   return -23;
+}
+
+int be_conv_pair(const void* x, const void* x2, const float* sa, const float* ta, int ta_ns, const float* sb,
+                 const float* tb, int tb_ns, const float* sp, const float* tp, const void* wa, const void* wb,
+                 const void* wp, const float* bias, const void* res, void* out, int N, int H, int W, int Hs, int Ws,
+                 int Cin, int CM, int inmode, int proj, int resmode, hipStream_t stream) {
+  return be_conv_pair_frag(x, x2, sa, ta, ta_ns, sb, tb, tb_ns, sp, tp, wa, wb, wp, bias, res, out, N, H, W, Hs, Ws, Cin,
+                           CM, inmode, proj, resmode, nullptr, nullptr, stream);
 }
 
 // The final up half-block (32 -> 32 channels, + x1) with the network's output layer fused into its
@@ -1105,7 +1134,7 @@ int be_conv_pair_head(const void* x, const float* sa, const float* ta, int ta_ns
   a.x = (const bf16_t*)x; a.x2 = nullptr;
   a.sa = sa; a.ta = ta; a.ta_ns = ta_ns; a.sb = sb; a.tb = tb; a.tb_ns = tb_ns; a.sp = nullptr; a.tp = nullptr;
   a.wa = (const bf16_t*)wa; a.wb = (const bf16_t*)wb; a.wp = nullptr; a.bias = bias;
-  a.res = (const bf16_t*)res; a.out = nullptr;
+  a.res = (const bf16_t*)res; a.out = nullptr; a.waf = a.wbf = nullptr;
   a.sh = sh; a.th = th; a.wh = (const bf16_t*)wh; a.bh = bh; a.hout = hout; a.nh = nh;
   a.N = N; a.H = H; a.W = W; a.Hs = H; a.Ws = W; a.Cin = 32;
   if (pp_ok(a, g_pair_grid)) return launch_pair_pp<1, 0, false, 1, true>(a, g_pair_grid, stream);

@@ -1,8 +1,6 @@
-// One-group fused residual half-block kernel (see conv_pair.hip for the design), included once per
-// tile geometry: the including namespace defines TW x TH (output tile) and NW (waves per workgroup).
+// One-group fused residual half-block kernel (see conv_pair.hip for the design).  The including
+// namespace defines TW x TH (output tile) and NW (waves per workgroup):
 //   g32: 16 x 32 tiles, 8 waves, one workgroup per CU (113-137 KB of LDS)
-//   g12: 12 x 16 tiles, 4 waves, <= 79 KB of LDS, so TWO workgroups share a CU and one's VALU /
-//        barrier phases overlap the other's MFMAs (the CM = 64 level-1 half-blocks)
 // NOT a standalone header: no include guard on purpose.
 constexpr int NT = NW * 64;
 constexpr int RPW = TH / NW, TPR = TW / 16, BPT = RPW * TPR;  // stage-B rows per wave, 16-px tiles per row, tiles per wave

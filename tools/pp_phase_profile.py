@@ -1,11 +1,12 @@
 #!/usr/bin/env python3
-"""Phase profile of the ping-pong level-0 half-blocks (csrc/kernels/conv_pair.hip,
-conv_pair_pp_kernel): wave 0 of each of the two wave groups accumulates s_memtime cycles of every
+"""Phase profile of the ping-pong half-blocks (csrc/kernels/conv_pair.hip: conv_pair_pp_kernel at
+level 0, conv_pair_pp64_kernel at level 1): wave 0 of each of the two wave groups accumulates s_memtime cycles of every
 phase's own work and of its wait at the closing workgroup barrier.  The slots pair one group's
 MFMA phase with the other's VALU phase, so a phase's wait is the time its partner phase ran longer.
 
 One CPnet forward at the headline batch (288 tiles of 224^2); one JSON line per ping-pong call with
-cycles per tile (mean over workgroups and both groups).  Usage: python tools/pp_phase_profile.py"""
+cycles per tile (mean over workgroups and both groups).  The level-1 kernel (cm 64) reports the
+commit / stage-A phases of its input chunks 1.. together as commit1 / stageA1.  Usage: python tools/pp_phase_profile.py"""
 from __future__ import annotations
 
 import argparse
@@ -43,15 +44,15 @@ def main():
     rows = []
     orig_pair, orig_head = cp.conv_pair, getattr(cp, "conv_pair_head", None)
 
-    def collect(tag, xin):
+    def collect(tag, xin, cm=32):
         torch.cuda.synchronize()
         s = buf.view(cap, 2, 16).cpu().double()
         used = s[:, :, 15] > 0
         if not used.any():
             return
-        nca = 2 if xin.shape[-1] == 64 else 1
+        nca = 2 if (xin.shape[-1] == 64 or cm == 64) else 1
         nm = names(nca)
-        out = {"call": tag, "cin": int(xin.shape[-1]), "workgroups": int(used[:, 0].sum())}
+        out = {"call": tag, "cin": int(xin.shape[-1]), "cm": cm, "workgroups": int(used[:, 0].sum())}
         for g in (0, 1):
             sg = s[:, g][used[:, g]]
             it = sg[:, 15]
@@ -63,7 +64,7 @@ def main():
     def pair(xin, spec, **kw):
         buf.zero_()
         y = orig_pair(xin, spec, **kw)
-        collect("pair", xin)
+        collect("pair", xin, spec.cm)
         return y
 
     def head(xin, *a, **kw):
