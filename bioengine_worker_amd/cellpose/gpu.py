@@ -538,11 +538,23 @@ def _fill_run(M: torch.Tensor, lut: torch.Tensor, nlab: int, plan) -> torch.Tens
     return out
 
 
-def follow_and_label(y: torch.Tensor, niter: int = 200, cellprob_threshold: float = 0.0,
-                     max_size_fraction: float = 0.4, with_bound: bool = False):
-    """Network output y [B, 3, H, W] -> raw masks M0 [B, H, W] int32 (before QC / fill); with
-    ``with_bound`` also an upper bound on its labels + 1 (known from the seed count, no extra sync)."""
+def _check_image2d(H: int, W: int) -> None:
+    """The flow sampler maps position ``p`` to ``p * L / (L - 1) - 0.5``: an axis needs two pixels."""
+    if H < 2 or W < 2:
+        raise ValueError(f"2-D dynamics need at least two rows and two columns, got an image of {H} x {W}")
+
+
+def follow_flows_gpu(y: torch.Tensor, niter: int = 200, cellprob_threshold: float = 0.0, entry: str | None = None,
+                     with_flow: bool = False):
+    """Network output ``y`` [B, 3, H, W] (dY, dX, cellprob) -> ``(hist [B, H+40, W+40] int32, pos
+    [B, H, W] int32)``: the histogram of the end points of :func:`reference.follow_flows` in the
+    padded image and every foreground pixel's padded linear bin index (-1 for background).
+    ``be_cp_prep_flow`` then one flow-following launch: ``entry`` names it (``be_cp_follow_flows``,
+    ``_xcd``, ``_xcd_pool`` or ``_lds``; identical results), None = :data:`FOLLOW_FLOWS_ENTRY`.
+    ``with_flow`` also returns prep_flow's outputs ``(flow2 [B, H, W, 2] fp32 (dy, dx) / 5 on the
+    foreground, fg [B, H, W] uint8)``.  No host sync."""
     B, _, H, W = y.shape
+    _check_image2d(H, W)
     dev = y.device
     st = _native.stream(dev)
     y = y.float().contiguous()
@@ -553,8 +565,31 @@ def follow_and_label(y: torch.Tensor, niter: int = 200, cellprob_threshold: floa
     Hp, Wp = H + 2 * RPAD, W + 2 * RPAD
     hist = torch.zeros(B, Hp, Wp, dtype=torch.int32, device=dev)
     pos = torch.empty(B, H, W, dtype=torch.int32, device=dev)
-    _native.call(FOLLOW_FLOWS_ENTRY, _native.ptr(flow2), _native.ptr(fg), _native.ptr(hist), _native.ptr(pos), B, H,
-                 W, int(niter), st)
+    _native.call(FOLLOW_FLOWS_ENTRY if entry is None else entry, _native.ptr(flow2), _native.ptr(fg), _native.ptr(hist),
+                 _native.ptr(pos), B, H, W, int(niter), st)
+    return (hist, pos, flow2, fg) if with_flow else (hist, pos)
+
+
+def get_masks_gpu(hist: torch.Tensor, pos: torch.Tensor, shape=None, max_size_fraction: float = 0.4,
+                  with_bound: bool = False):
+    """The stages of :func:`reference.get_masks` after the histogram, for a batch: ``hist``
+    [B, H+40, W+40] int32 and ``pos`` [B, H, W] int32 (padded linear bin of every foreground pixel, -1
+    elsewhere) -> raw labels [B, H, W] int32 numbered ``1..k`` per image (before QC / fill); with
+    ``with_bound`` also an upper bound on its labels + 1 (known from the seed count).  5x5 seeds
+    (``be_cp_seeds``), ``torch.sort`` of the seed keys, 11x11 window expansion (``be_cp_expand``),
+    per-pixel lookup, big-mask removal and renumber.  One host sync (the seed count)."""
+    B = pos.shape[0]
+    H, W = tuple(pos.shape[1:]) if shape is None else tuple(int(v) for v in shape)
+    _check_image2d(H, W)
+    Hp, Wp = H + 2 * RPAD, W + 2 * RPAD
+    if tuple(hist.shape) != (B, Hp, Wp) or tuple(pos.shape) != (B, H, W):
+        raise ValueError(f"get_masks_gpu: hist {tuple(hist.shape)} / pos {tuple(pos.shape)} do not fit {B} images of "
+                         f"{H} x {W} padded by {RPAD}")
+    if hist.dtype != torch.int32 or pos.dtype != torch.int32:
+        raise TypeError(f"get_masks_gpu expects int32 hist and pos, got {hist.dtype} and {pos.dtype}")
+    dev = pos.device
+    st = _native.stream(dev)
+    hist, pos = hist.contiguous(), pos.contiguous()
     cap = H * W // 11 + 1
     keys = torch.full((B, cap), torch.iinfo(torch.int64).max, dtype=torch.int64, device=dev)
     nseeds = torch.zeros(B, dtype=torch.int32, device=dev)
@@ -578,6 +613,15 @@ def follow_and_label(y: torch.Tensor, niter: int = 200, cellprob_threshold: floa
     keep = (counts > 0) & (counts <= big)
     M = _renumber(M0, keep)
     return (M, nlab) if with_bound else M
+
+
+def follow_and_label(y: torch.Tensor, niter: int = 200, cellprob_threshold: float = 0.0,
+                     max_size_fraction: float = 0.4, with_bound: bool = False):
+    """Network output y [B, 3, H, W] -> raw masks M0 [B, H, W] int32 (before QC / fill); with
+    ``with_bound`` also an upper bound on its labels + 1 (known from the seed count, no extra sync):
+    :func:`follow_flows_gpu` then :func:`get_masks_gpu`."""
+    hist, pos = follow_flows_gpu(y, niter, cellprob_threshold)
+    return get_masks_gpu(hist, pos, tuple(y.shape[2:]), max_size_fraction, with_bound)
 
 
 def compute_masks_gpu(y: torch.Tensor, niter: int = 200, cellprob_threshold: float = 0.0, flow_threshold: float = 0.4,

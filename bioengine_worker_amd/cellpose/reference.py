@@ -79,12 +79,13 @@ def make_tiles(img: np.ndarray, bsize: int = 224, overlap: float = 0.1):
     return tiles, ys, xs
 
 
-def average_tiles(y: np.ndarray, ys, xs, Ly: int, Lx: int) -> np.ndarray:
-    """y [nt, nout, by, bx] -> [nout, Ly, Lx] tapered weighted average."""
+def average_tiles(y: np.ndarray, ys, xs, Ly: int, Lx: int, dtype=np.float32) -> np.ndarray:
+    """y [nt, nout, by, bx] -> [nout, Ly, Lx] tapered weighted average, accumulated in ``dtype``
+    (float64: the yardstick of the float32 blends; the taper itself stays the float32 mask)."""
     nt, nout, by, bx = y.shape
-    acc = np.zeros((nout, Ly, Lx), np.float32)
-    nrm = np.zeros((Ly, Lx), np.float32)
-    mask = taper_mask(by, bx)
+    acc = np.zeros((nout, Ly, Lx), dtype)
+    nrm = np.zeros((Ly, Lx), dtype)
+    mask = taper_mask(by, bx).astype(dtype)
     k = 0
     for yy in ys:
         for xx in xs:
@@ -98,10 +99,13 @@ def average_tiles(y: np.ndarray, ys, xs, Ly: int, Lx: int) -> np.ndarray:
 
 
 def follow_flows(dP: np.ndarray, cellprob: np.ndarray, cellprob_threshold: float = 0.0, niter: int = 200):
-    """Returns (p_final [2, npts] float32 (y, x), inds (y, x) arrays)."""
+    """Returns (p_final [2, npts] float32 (y, x), inds (y, x) arrays).  A 2-D image needs two rows
+    and two columns (the sample position is ``p * L / (L - 1) - 0.5``): ``ValueError`` otherwise."""
+    Ly, Lx = cellprob.shape
+    if Ly < 2 or Lx < 2:
+        raise ValueError(f"2-D dynamics need at least two rows and two columns, got an image of {Ly} x {Lx}")
     fg = cellprob > cellprob_threshold
     inds = np.nonzero(fg)
-    Ly, Lx = cellprob.shape
     flow = torch.from_numpy((dP * fg / 5.0).astype(np.float32))
     p = torch.from_numpy(np.stack(inds).astype(np.float32))  # [2, n] (y, x)
     if p.shape[1] == 0:
