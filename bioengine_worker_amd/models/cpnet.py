@@ -214,6 +214,9 @@ class _FConv:
     def __init__(self, seq: nn.Sequential, relu: bool, device, cin_pad=None, cout_pad_to=None):
         bn, conv = seq[0], seq[-1]
         self.pc = convops.PackedConv.from_weight(conv.weight, conv.bias, cin_pad=cin_pad, cout_pad_to=cout_pad_to).to(device)
+        # fragment-order weights of the 128-channel ping-pong kernel: packed here, not in the first forward
+        if convops.frag_eligible(self.pc) and torch.device(device).type == "cuda":
+            self.pc.frag()
         s, t = _bn_fold(bn, device)
         self.scale = _pad_vec(s, self.pc.cin_pad, 0.0)
         self.shift = _pad_vec(t, self.pc.cin_pad, 0.0)

@@ -52,6 +52,10 @@ class PackedConv:
     tco: int
     kp: int
     wp: torch.Tensor | None = None
+    #: ``wp`` once more in MFMA-fragment order (:func:`pack_frag`), built by :meth:`frag` for the
+    #: layers :func:`frag_eligible` names, and the (address, version) of the ``wp`` it was packed from
+    wf: torch.Tensor | None = None
+    wf_key: tuple | None = None
 
     @staticmethod
     def choose(cin_pad: int, cout: int, ks: int = 3) -> tuple[int, int]:
@@ -109,8 +113,12 @@ class PackedConv:
         self.w = self.w.to(device)
         if self.bias is not None:
             self.bias = self.bias.to(device)
+        built = self.wp is not None and self.frag_built() is not None
         if self.wp is not None:
             self.wp = self.wp.to(device)
+        if built:
+            self.wf = self.wf.to(device)
+            self.wf_key = self._wp_key()
         return self
 
     def refresh(self, weight: torch.Tensor, bias: torch.Tensor | None = None) -> None:
@@ -119,6 +127,52 @@ class PackedConv:
         if bias is not None:
             self.bias = bias.detach().float()
         self.wp = self._pack(self.w)
+        self.wf = self.wf_key = None
+
+    def _wp_key(self) -> tuple:
+        return (self.wp.data_ptr(), self.wp._version, str(self.wp.device))
+
+    def frag(self) -> torch.Tensor:
+        """``pack_frag(wp)`` on ``wp``'s device: packed once and kept with the conv (packed again only
+        if ``wp`` was replaced or written since).  An engine calls this when it is built; a conv whose
+        fragments were never built, or went stale, runs on the per-layer kernel (:meth:`frag_built`)."""
+        if self.frag_built() is None:
+            self.wf = pack_frag(self.wp)
+            self.wf_key = self._wp_key()
+        return self.wf
+
+    def frag_built(self) -> torch.Tensor | None:
+        """The fragment-order weights if :meth:`frag` built them from the current ``wp``, else None
+        (the trainer rewrites ``wp`` in place every step and never asks for fragments)."""
+        if self.wf is not None and self.wf_key == self._wp_key() and self.wf.device == self.wp.device:
+            return self.wf
+        return None
+
+
+def frag_eligible(pc: PackedConv) -> bool:
+    """The layers with a ping-pong build that reads fragment-order weights
+    (``csrc/kernels/conv_pp128.hip``): 3x3, 128 -> 128 channels."""
+    return pc.ks == 3 and pc.ck == 32 and pc.cin_pad == 128 and pc.cout == 128 and pc.cout_pad == 128
+
+
+def pack_frag(wp: torch.Tensor) -> torch.Tensor:
+    """``PackedConv.wp`` ``[cout, nchunk, 288]`` (3x3, 32-channel chunks, K index = tap * 32 + c) in
+    MFMA-A-fragment order ``[nchunk, 9 taps, cout / 16 channel tiles, 64 lanes, 8]``: lane
+    ``kq * 16 + lrow`` of channel tile ``ct`` holds ``wp[ct * 16 + lrow, chunk, tap * 32 + kq * 8 : ... + 8]``,
+    the operand registers of one ``v_mfma_f32_16x16x32_bf16``, so a wave fetches a fragment with one
+    16-byte-per-lane load."""
+    cout, nchunk, kp = wp.shape
+    assert cout % 16 == 0 and kp == 288, "fragment packing: 3x3 taps of 32-channel chunks, whole channel tiles"
+    nct = cout // 16
+    t = wp.reshape(nct, 16, nchunk, 9, 4, 8)        # ct, lrow, chunk, tap, kq, e
+    return t.permute(2, 3, 0, 4, 1, 5).contiguous().reshape(nchunk, 9, nct, 64, 8)
+
+
+def unpack_frag(wf: torch.Tensor) -> torch.Tensor:
+    """Inverse of :func:`pack_frag`."""
+    nchunk, _, nct = wf.shape[:3]
+    t = wf.reshape(nchunk, 9, nct, 4, 16, 8)        # chunk, tap, ct, kq, lrow, e
+    return t.permute(2, 4, 0, 1, 3, 5).contiguous().reshape(nct * 16, nchunk, 288)
 
 
 register = _native.register_hip_signatures
@@ -275,14 +329,17 @@ def fused_conv2d(x: torch.Tensor, pc: PackedConv, *, x2=None, scale=None, shift=
     qshift_ns = _affine_stride(post_shift, N, pc.cout)
     if post_scale is not None:
         assert post_scale.dtype == torch.float32 and post_scale.is_contiguous() and post_scale.numel() == pc.cout
+    # the layers with a ping-pong build also pass their fragment-order weights; the entry point picks
+    # the kernel (csrc/kernels/conv_pp128.hip, be_conv2d_nhwc_frag)
+    wf = pc.frag_built() if frag_eligible(pc) else None
     _native.call(
-        "be_conv2d_nhwc",
+        "be_conv2d_nhwc_frag",
         _native.ptr(x), _native.ptr(x2), _native.ptr(scale), _native.ptr(shift), pshift_ns, pscale_ns,
         int(bool(relu)) | (2 if post_relu else 0),
         _native.ptr(pc.wp), _native.ptr(None if no_bias else pc.bias), _native.ptr(residual), _native.ptr(out),
         N, H, W, Hs, Ws, Cin, cout_store, cout_valid, pc.ks, pc.ck, pc.tco, INMODES[inmode], int(out_nchw_f32),
         int(nw or choose_nw(pc, H, W, inmode, x2 is not None)), _native.ptr(post_scale), _native.ptr(post_shift),
-        qshift_ns, _native.stream(x.device),
+        qshift_ns, _native.ptr(wf), _native.stream(x.device),
     )
     return out
 

@@ -1,0 +1,479 @@
+// Two-group ping-pong 3x3 conv with fused pre-activation for Cin = Cout = 128 (the plain level-2
+// convs of CPnet at 56^2): be_conv2d_nhwc's INMODE 0 / no-x2 / bf16-NHWC semantics,
+//
+//   out = conv3x3( relu?( x * scale[c] + shift[n, c] ) ) + bias [+ residual]
+//
+// in the scheme of conv_pair_pp64.inc.  One workgroup computes ALL 128 output channels of its pixel
+// tile, so the input is loaded, activated and written to LDS once (the per-layer kernel does it once
+// per 64-channel block).  The 8 waves are two groups of 4 that own alternate tiles of the
+// workgroup's range and run ONE PHASE APART on the same workgroup barriers, so one group's VALU /
+// LDS-store phase runs beside the other group's MFMA phase on every SIMD:
+//     per 32-channel input chunk c = 0..3:   P1 commit(c)   P2 MFMA(c), s_setprio 1
+//     then                                   P3 residual + bias + stores
+// Nine phases per tile: every MFMA phase of one group meets a VALU phase of the other; the one
+// VALU / VALU slot per tile is a group's epilogue beside the other's first commit.
+//
+// Geometry: an 8 x 28 pixel tile per group (7 x 2 tiles cover 56^2 exactly; 16-wide row fragments
+// would compute 64 columns per 56).  The MFMA's 16 pixels are a 4 x 4 patch: lane lrow is pixel
+// (lrow >> 2, lrow & 3) of its fragment, a wave owns 2 channel tiles (ct = 2 cp, 2 cp + 1; cp = wave
+// of the group) x all 14 fragments (2 rows x 7 columns of patches) = 112 accumulator VGPRs, so each
+// pixel-fragment read feeds 2 MFMAs and each weight fragment 14.
+//
+// LDS: per group ONE 10 x 30 image of the current chunk, 64-byte pixels (19,200 B; 38,400 B per
+// workgroup).  A group's commit of chunk c + 1 can only start once its own MFMA phase of chunk c is
+// over (the phases of a group are sequential), so a second image per group would never be written
+// while the first is read.  Pixels are unpadded.  Swizzle: the 16-byte unit c of pixel (y, x) lives
+// at unit c ^ 2 ((x >> 1) & 1).  Derivation: a ds_read_b128 is served in lane groups of 16 =
+// {kq, lrow 0-3, 12-15} + {kq + 1, lrow 4-11} (and the converse), i.e. patch rows 0 and 3 at unit k
+// and patch rows 1 and 2 at unit k ^ 1.  The 16-byte bank slot of unit c of pixel (y, x) is
+// 4 ((30 y + x) mod 4) + c = 4 ((2 y + x) mod 4) + c.  The 4 pixels of a patch row hit the 4
+// residues once each; the pixel of the same residue in patch row r + 1 or r + 3 sits 2 columns to
+// the left or right (2 (y + 1) + x +- 2 = 2 y + x mod 4).  Rows {0, 3} and {1, 2} already differ in
+// bit 0 of the unit; within each pair, flipping bit 1 by (x >> 1) & 1 separates the two pixels of a
+// residue, for any patch origin -- so all nine tap offsets are conflict-free.  Patch columns are 4
+// apart and rows do not enter, so a fragment address is a per-lane base (one per dx) + a
+// compile-time offset.
+//
+// Weights never pass through LDS: the host packs the conv once in MFMA-A-fragment order
+// [chunk][tap][ct 0..7][lane][8 bf16] (ops/conv.py, pack_frag) and a wave fetches a fragment with
+// one 16-byte-per-lane global load, WD K-steps ahead of its use (288 KB per conv, L2-resident).  The
+// first WD steps of an MFMA phase are issued at the end of the commit before it, behind the next
+// chunk's halo and affine, which are in flight across the barrier wait and the MFMA phase.
+//
+// Rounding points and the per-output accumulation order are conv2d_nhwc_kernel's (activation
+// rounded to bf16 before LDS, zero padding after the activation, chunks in order, taps 0..8 within
+// a chunk, 32-deep K-steps with lane group kq holding channels 8 kq..8 kq + 7, (acc + bias) +
+// residual, one rounding), so the output is bit-identical to it.
+#include <cstdlib>
+
+#include "common.h"
+
+namespace {
+namespace pp128 {
+constexpr int TH = 8, TW = 28;              // output tile
+constexpr int GW = 4, GT = GW * 64, NTP = 2 * GT;
+constexpr int IH = TH + 2, IW = TW + 2, IPIX = IH * IW;  // input image 10 x 30
+constexpr int IN_B = IPIX * 64;             // 19200
+constexpr int LDS = 2 * IN_B;
+constexpr int NF = 14, FC = 7;              // 4 x 4 pixel patches: 2 rows x 7 columns
+constexpr int NCH = 4;                      // 32-channel input chunks
+constexpr int C = 128;
+constexpr int HU = IPIX * 4, HUPT = (HU + GT - 1) / GT;  // 16-byte halo units per chunk, per thread
+constexpr int WD = 3;                       // weight fragments are fetched WD K-steps ahead
+constexpr int WSTEP = 8 * 64 * 8;           // elements per K-step of the fragment layout (8 ct)
+constexpr int BD = 6, BR = 7;               // pixel fragments are read BD MFMA pairs ahead, ring of BR
+static_assert(IW % 4 == 2, "the swizzle derivation needs 30 y = 2 y (mod 4)");
+static_assert(LDS <= 128 * 1024, "LDS budget of the ping-pong kernels");
+static_assert(BD < BR, "ring");
+
+struct Args {
+  const bf16_t* x;     // [N, H, W, 128]
+  const float* sa;     // scale [128] (sa_ns 0) or [N, sa_ns], or null (1)
+  const float* ta;     // shift likewise, or null (0)
+  const bf16_t* wf;    // fragment-order weights
+  const float* bias;   // [128] or null
+  const bf16_t* res;   // [N, H, W, 128] or null; may be `out`
+  bf16_t* out;         // [N, H, W, 128]
+  int N, H, W;
+  int sa_ns, ta_ns;
+  int relu;
+  int tiles_x, tiles_y;
+  // diagnostics (STAMP instantiation only, tools/pp128_phase_profile.py): [grid][2 groups][16] cycle
+  // counts of wave 0 of each group
+  unsigned long long* stamps;
+};
+
+struct TileXY {
+  int n, ty0, tx0;
+};
+
+__device__ __forceinline__ TileXY tile_of(const Args& a, int t) {
+  const int tpi = a.tiles_x * a.tiles_y;
+  TileXY r;
+  r.n = t / tpi;
+  const int q = t - r.n * tpi;
+  r.ty0 = (q / a.tiles_x) * TH;
+  r.tx0 = (q % a.tiles_x) * TW;
+  return r;
+}
+
+struct Halo {
+  u32x4 h[HUPT];
+  float4 aff[4];  // scale / shift of this thread's 8 channels ride along with the halo
+};
+
+// chunk ch of the tile's 10 x 30 input halo -> registers; clamped, unconditional loads (commit
+// zeroes what lies outside the image and skips units past HU)
+__device__ __forceinline__ void issue_halo(const Args& a, TileXY t, int ch, int gt, Halo& hr) {
+  const int c = ch * 32 + (gt & 3) * 8;  // a thread's channel group is the same for every unit (GT % 4 == 0)
+  hr.aff[0] = hr.aff[1] = make_float4(1.f, 1.f, 1.f, 1.f);
+  hr.aff[2] = hr.aff[3] = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (a.sa) {
+    const float* sr = a.sa + (size_t)t.n * a.sa_ns + c;
+    hr.aff[0] = *reinterpret_cast<const float4*>(sr);
+    hr.aff[1] = *reinterpret_cast<const float4*>(sr + 4);
+  }
+  if (a.ta) {
+    const float* tr = a.ta + (size_t)t.n * a.ta_ns + c;
+    hr.aff[2] = *reinterpret_cast<const float4*>(tr);
+    hr.aff[3] = *reinterpret_cast<const float4*>(tr + 4);
+  }
+#pragma unroll
+  for (int i = 0; i < HUPT; ++i) {
+    const int pi = min(gt + i * GT, HU - 1) >> 2;
+    const int y = pi / IW, x = pi - y * IW;
+    const int gy = min(max(t.ty0 - 1 + y, 0), a.H - 1);
+    const int gx = min(max(t.tx0 - 1 + x, 0), a.W - 1);
+    hr.h[i] = *reinterpret_cast<const u32x4*>(a.x + (((size_t)t.n * a.H + gy) * a.W + gx) * C + c);
+  }
+}
+
+// P1: activation -> bf16 -> the swizzled input image (zero outside the image: conv padding applies
+// after the activation)
+__device__ __forceinline__ void commit(const Args& a, TileXY t, int gt, const Halo& hr, unsigned char* rin) {
+  const int c = gt & 3;
+  const float sc[8] = {hr.aff[0].x, hr.aff[0].y, hr.aff[0].z, hr.aff[0].w, hr.aff[1].x, hr.aff[1].y, hr.aff[1].z, hr.aff[1].w};
+  const float sh[8] = {hr.aff[2].x, hr.aff[2].y, hr.aff[2].z, hr.aff[2].w, hr.aff[3].x, hr.aff[3].y, hr.aff[3].z, hr.aff[3].w};
+  const bool relu = a.relu != 0;
+#pragma unroll
+  for (int i = 0; i < HUPT; ++i) {
+    const int u = gt + i * GT;
+    if (u >= HU) continue;
+    const int pi = u >> 2;
+    const int y = pi / IW, x = pi - y * IW;
+    const int gy = t.ty0 - 1 + y, gx = t.tx0 - 1 + x;
+    u32x4 pk = (u32x4){0u, 0u, 0u, 0u};
+    if (gy >= 0 && gy < a.H && gx >= 0 && gx < a.W) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float lo = lo_bf(hr.h[i][j]), hi = hi_bf(hr.h[i][j]);
+        pk[j] = pack2bf(fmaf(lo, sc[2 * j], sh[2 * j]), fmaf(hi, sc[2 * j + 1], sh[2 * j + 1]));
+        if (relu) pk[j] = relu_bf16x2(pk[j]);
+      }
+    }
+    *reinterpret_cast<u32x4*>(rin + pi * 64 + ((c ^ (((x >> 1) & 1) << 1)) << 4)) = pk;
+  }
+}
+
+// The first WD K-steps' weight fragments of an MFMA phase, issued in the commit before it.
+struct WPre {
+  bf16x8 w[WD][2];
+};
+
+// wf: the conv's fragment-order weights; lane: 0..63, cp: channel-tile pair 0..3
+__device__ __forceinline__ const bf16_t* w_lane(const bf16_t* wf, int cp, int lane) {
+  return wf + cp * 2 * 512 + lane * 8;
+}
+
+__device__ __forceinline__ void issue_w(const bf16_t* wl, WPre& p) {
+#pragma unroll
+  for (int d = 0; d < WD; ++d)
+#pragma unroll
+    for (int ct = 0; ct < 2; ++ct) p.w[d][ct] = *reinterpret_cast<const bf16x8*>(wl + d * WSTEP + ct * 512);
+}
+
+// P2: the 9 taps of one input chunk over 14 pixel fragments x 2 channel tiles.  Pixel fragments go
+// through a ring of BR registers, read BD fragments (2 BD MFMAs) ahead; weight fragments come from
+// global memory WD steps ahead.  A0[dx]: this lane's byte address of patch pixel (ly, lx + dx).
+__device__ __forceinline__ void mma_chunk(f32x4 (&acc)[2][NF], const unsigned char* rin, const bf16_t* wl, const WPre& pre,
+                                          const int (&A0)[3]) {
+  bf16x8 w[9][2];  // fully unrolled: WD + 1 steps are live at a time
+#pragma unroll
+  for (int d = 0; d < WD; ++d) {
+    w[d][0] = pre.w[d][0];
+    w[d][1] = pre.w[d][1];
+  }
+  auto rd = [&](int f) {
+    const int s = f / NF, j = f % NF, dy = s / 3, dx = s % 3;
+    return *reinterpret_cast<const bf16x8*>(rin + A0[dx] + ((4 * (j / FC) + dy) * IW + 4 * (j % FC)) * 64);
+  };
+  bf16x8 bf[BR];
+#pragma unroll
+  for (int f = 0; f < BD; ++f) bf[f] = rd(f);
+#pragma unroll
+  for (int s = 0; s < 9; ++s) {
+    if (s + WD < 9) {
+#pragma unroll
+      for (int ct = 0; ct < 2; ++ct)
+        w[s + WD][ct] = *reinterpret_cast<const bf16x8*>(wl + (s + WD) * WSTEP + ct * 512);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int j = 0; j < NF; ++j) {
+      const int f = s * NF + j;
+      if (f + BD < 9 * NF) bf[(f + BD) % BR] = rd(f + BD);
+#pragma unroll
+      for (int ct = 0; ct < 2; ++ct)
+        acc[ct][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[s][ct], bf[f % BR], acc[ct][j], 0, 0, 0);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  }
+}
+
+// P3: (acc + bias) + residual -> bf16 -> 8-byte stores (4 channels of one pixel per lane; the four kq
+// lanes of a pixel write 32 contiguous bytes per channel tile).  Straight-line buffer accesses: a
+// branch per store makes the compiler's wait-count pass wait for ALL outstanding memory operations at
+// every join.  RES: with a residual.  Without one the per-layer kernel still adds a +0.0f residual,
+// which only matters when acc + bias is -0.0, i.e. when both are; adding +0.0f to the BIAS once gives
+// the same bits for 8 VALU operations per tile.  FULL: the tile lies inside the image (every tile at
+// 56^2), so one per-lane offset serves all 28 accesses and the fragment's offset is scalar; otherwise
+// pixels outside the image get an out-of-range offset, which the descriptor's range check drops, as do
+// tiles that are not this group's.  Every residual is loaded before the first store: `out` may be the
+// residual.
+template <bool RES, bool FULL>
+__device__ __forceinline__ void epilogue(const Args& a, TileXY t, const f32x4 (&acc)[2][NF], int cp, int lrow, int kq,
+                                         bool act) {
+  const int ly = lrow >> 2, lx = lrow & 3;
+  const int co = cp * 32 + kq * 4;
+  const int img_b = a.H * a.W * C * 2;  // host-checked: < 2^31
+  const size_t img = (size_t)t.n * a.H * a.W * C;
+  const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc(
+      const_cast<bf16_t*>(RES ? a.res + img : a.x), (short)0, RES ? img_b : 0, 0x00020000);
+  const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc(a.out + img, (short)0, img_b, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc(
+      const_cast<float*>(a.bias ? a.bias : a.sa), (short)0, a.bias ? C * 4 : 0, 0x00020000);  // null: loads give 0
+  // byte offset of this lane's 4 channels of fragment j's pixel: per-lane part, scalar part
+  auto voff = [&](int j, int y, int x) {
+    if constexpr (FULL) return (((t.ty0 + y) * a.W + t.tx0 + x) * C + co) * 2;
+    const int py = t.ty0 + 4 * (j / FC) + y, px = t.tx0 + 4 * (j % FC) + x;
+    return (py < a.H && px < a.W) ? ((py * a.W + px) * C + co) * 2 : 0x7ffffff0;
+  };
+  auto soff = [&](int j) { return FULL ? ((j / FC) * 4 * a.W + (j % FC) * 4) * C * 2 : 0; };
+  u32x2 rv[RES ? NF : 1][2];
+  f32x4 bias[2];
+#pragma unroll
+  for (int ct = 0; ct < 2; ++ct)
+    bias[ct] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rb, (co + ct * 16) * 4, 0, 0));
+  if constexpr (RES) {
+#pragma unroll
+    for (int j = 0; j < NF; ++j) {
+      const int o = voff(j, ly, lx);
+#pragma unroll
+      for (int ct = 0; ct < 2; ++ct) rv[j][ct] = __builtin_amdgcn_raw_buffer_load_b64(rr, o + ct * 32, soff(j), 0);
+    }
+  } else {
+#pragma unroll
+    for (int ct = 0; ct < 2; ++ct) bias[ct] = bias[ct] + (f32x4){0.f, 0.f, 0.f, 0.f};
+  }
+  __builtin_amdgcn_sched_barrier(0);
+  int sy = ly, sx = lx;
+  asm volatile("" : "+v"(sy), "+v"(sx));  // the store offsets are formed again, not kept across the loads
+#pragma unroll
+  for (int j = 0; j < NF; ++j) {
+    const int o = act ? voff(j, sy, sx) : 0x7ffffff0;
+#pragma unroll
+    for (int ct = 0; ct < 2; ++ct) {
+      u32x2 st;
+      if constexpr (RES) {
+        const u32x2 r = rv[j][ct];
+        st[0] = pack2bf(acc[ct][j][0] + bias[ct][0] + lo_bf(r[0]), acc[ct][j][1] + bias[ct][1] + hi_bf(r[0]));
+        st[1] = pack2bf(acc[ct][j][2] + bias[ct][2] + lo_bf(r[1]), acc[ct][j][3] + bias[ct][3] + hi_bf(r[1]));
+      } else {
+        st[0] = pack2bf(acc[ct][j][0] + bias[ct][0], acc[ct][j][1] + bias[ct][1]);
+        st[1] = pack2bf(acc[ct][j][2] + bias[ct][2], acc[ct][j][3] + bias[ct][3]);
+      }
+      __builtin_amdgcn_raw_buffer_store_b64(st, ro, o + ct * 32, soff(j), 0);
+    }
+  }
+}
+
+template <bool STAMP = false>
+__global__ __launch_bounds__(NTP, 2) void conv_pp128_kernel(Args a) {
+  // STAMP: as conv_pair_pp64_kernel; slots: commit / MFMA of chunk 0, of chunks 1..3 together, epilogue;
+  // work cycles of slot i at i, the wait at its closing barrier at 8 + i, iterations at 15
+  unsigned long long ph_work[5] = {0, 0, 0, 0, 0}, ph_wait[5] = {0, 0, 0, 0, 0};
+  unsigned long long tstamp = STAMP ? __builtin_amdgcn_s_memtime() : 0;
+  auto pre = [&](int i) {
+    if constexpr (STAMP) {
+      const unsigned long long tn = __builtin_amdgcn_s_memtime();
+      ph_work[i] += tn - tstamp;
+      tstamp = tn;
+    }
+  };
+  auto post = [&](int i) {
+    if constexpr (STAMP) {
+      const unsigned long long tn = __builtin_amdgcn_s_memtime();
+      ph_wait[i] += tn - tstamp;
+      tstamp = tn;
+    }
+  };
+  auto slot = [](int c) { return c > 0 ? 2 : 0; };
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int tid0 = threadIdx.x;
+  const int total = a.N * a.tiles_x * a.tiles_y;
+  const int t0 = (int)(((long long)blockIdx.x * total) / gridDim.x);
+  const int t1 = (int)(((long long)(blockIdx.x + 1) * total) / gridDim.x);
+  if (t0 >= t1) return;  // workgroup-uniform
+  const int grp = __builtin_amdgcn_readfirstlane(tid0 / GT);  // waves w and w + 4 share a SIMD
+  const int gt0 = tid0 & (GT - 1);
+  unsigned char* reg = smem + grp * IN_B;
+  Halo halo;
+  issue_halo(a, tile_of(a, min(t0 + grp, t1 - 1)), 0, gt0, halo);
+  if (grp == 1) __builtin_amdgcn_s_barrier();  // the stagger: group 1 runs one phase behind
+  const int iters = (t1 - t0 + 1) >> 1;
+  for (int k = 0; k < iters; ++k) {
+    int gt = gt0;
+    asm volatile("" : "+v"(gt));  // per-iteration opaque copy: no addresses hoisted out of the tile loop
+    const int cp = __builtin_amdgcn_readfirstlane(gt >> 6), lane = gt & 63, lrow = lane & 15, kq = lane >> 4;
+    const int t = t0 + 2 * k + grp;
+    // a group without a tile in the last iteration (odd range) recomputes the range's last tile and
+    // stores nothing
+    const bool act = t < t1;
+    const TileXY cur = tile_of(a, act ? t : t1 - 1);
+    const bf16_t* wl = w_lane(a.wf, cp, lane);
+    int A0[3];
+#pragma unroll
+    for (int dx = 0; dx < 3; ++dx) {
+      const int x = (lrow & 3) + dx;
+      A0[dx] = ((lrow >> 2) * IW + x) * 64 + ((kq ^ (((x >> 1) & 1) << 1)) << 4);
+    }
+    f32x4 acc[2][NF];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int j = 0; j < NF; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    WPre wpre;
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+      // P1: input chunk c -> activated image.  Behind it the next chunk's halo (or the group's next
+      // tile's first) and then the first weight fragments of this chunk's MFMA phase.  Loads return in
+      // issue order: a halo issued inside the MFMA phase held every later weight fragment back until
+      // the halo had arrived from HBM (MFMA phases of 5.8-8k cycles for 4k of MFMAs).  Issued here, it
+      // travels while the group waits at the barrier for the other group's MFMA phase to end.
+      int gc = gt0;
+      asm volatile("" : "+v"(gc));
+      commit(a, cur, gc, halo, reg);
+      __builtin_amdgcn_sched_barrier(0);
+      if (c + 1 < NCH)
+        issue_halo(a, cur, c + 1, gc, halo);
+      else
+        issue_halo(a, tile_of(a, min(t + 2, t1 - 1)), 0, gc, halo);
+      issue_w(wl + c * 9 * WSTEP, wpre);
+      pre(slot(c));
+      __syncthreads();
+      post(slot(c));
+      // P2: the chunk's MFMAs
+      __builtin_amdgcn_s_setprio(1);
+      mma_chunk(acc, reg, wl + c * 9 * WSTEP, wpre, A0);
+      __builtin_amdgcn_s_setprio(0);
+      pre(slot(c) + 1);
+      __syncthreads();
+      post(slot(c) + 1);
+    }
+    // P3: output epilogue
+    int g3 = gt0;
+    asm volatile("" : "+v"(g3));
+    const bool full = cur.ty0 + TH <= a.H && cur.tx0 + TW <= a.W;  // workgroup-uniform, as a.res is
+    if (a.res != nullptr) {
+      if (full)
+        epilogue<true, true>(a, cur, acc, cp, g3 & 15, (g3 & 63) >> 4, act);
+      else
+        epilogue<true, false>(a, cur, acc, cp, g3 & 15, (g3 & 63) >> 4, act);
+    } else {
+      if (full)
+        epilogue<false, true>(a, cur, acc, cp, g3 & 15, (g3 & 63) >> 4, act);
+      else
+        epilogue<false, false>(a, cur, acc, cp, g3 & 15, (g3 & 63) >> 4, act);
+    }
+    pre(4);
+    __syncthreads();
+    post(4);
+  }
+  if (grp == 0) __builtin_amdgcn_s_barrier();  // balance the stagger
+  if constexpr (STAMP) {
+    if ((tid0 & (GT - 1)) < 16) {  // wave 0 of each group: lane k stores slot k
+      const int k = tid0 & 15;
+      unsigned long long v = 0;
+#pragma unroll
+      for (int i = 0; i < 5; ++i) {
+        if (k == i) v = ph_work[i];
+        if (k == 8 + i) v = ph_wait[i];
+      }
+      if (k == 15) v = (unsigned long long)iters;
+      a.stamps[((size_t)blockIdx.x * 2 + grp) * 16 + k] = v;
+    }
+  }
+}
+}  // namespace pp128
+
+// BE_CONV_PP128 (default 1, A/B): 0 keeps every call on conv2d_nhwc_kernel
+int g_pp128 = [] {
+  const char* e = getenv("BE_CONV_PP128");
+  return e ? atoi(e) : 1;
+}();
+
+int g_pp128_grid = 0;      // be_conv_pp128_set_grid (0 = one workgroup per CU)
+int g_pp128_launches = 0;  // be_conv_pp128_launches
+unsigned long long* g_pp128_stamps = nullptr;  // diagnostics: be_conv_pp128_set_stamps
+int g_pp128_stamps_cap = 0;                    // workgroups the stamp buffer holds
+
+}  // namespace
+
+extern "C" {
+
+int be_conv2d_nhwc(const void* x, const void* x2, const float* pscale, const float* pshift, int pshift_ns, int pscale_ns,
+                   int prelu, const void* w, const float* bias, const void* res, void* out, int N, int H, int W,
+                   int Hs, int Ws, int Cin, int Cout, int cout_valid, int ks, int ck, int tco, int inmode,
+                   int out_f32_nchw, int nw, const float* qscale, const float* qshift, int qshift_ns,
+                   hipStream_t stream);
+
+// Tests / tuning: the ping-pong kernel's grid (0 = 256, one workgroup per CU, and the tile-count
+// rule of be_conv2d_nhwc_frag).  A positive value forces every eligible call onto the kernel with
+// at most that many workgroups, however few tiles it has: uneven ranges, idle groups' dummy tiles.
+int be_conv_pp128_set_grid(int blocks) {
+  g_pp128_grid = blocks;
+  return 0;
+}
+
+// Diagnostics: eligible calls run the phase-stamped build, which writes [workgroup][group][16] u64
+// cycle counts into `buf` (device, >= cap_workgroups * 256 bytes); nullptr switches back.  Not for
+// production launches.
+int be_conv_pp128_set_stamps(void* buf, int cap_workgroups) {
+  g_pp128_stamps = static_cast<unsigned long long*>(buf);
+  g_pp128_stamps_cap = buf ? cap_workgroups : 0;
+  return 0;
+}
+
+// Launches of conv_pp128_kernel by this process so far (tests: which kernel did a call take).
+int be_conv_pp128_launches() { return g_pp128_launches; }
+
+// be_conv2d_nhwc with the weights once more in MFMA-fragment order (ops/conv.py pack_frag; wfrag may be
+// null).  A 3x3, Cin = Cout = 128, INMODE 0, no-x2, bf16-NHWC-output call without an output
+// activation runs on conv_pp128_kernel when every group of every workgroup gets at least two 8 x 28
+// tiles (as pp64_ok: batch-1 latency calls would only recompute dummy tiles) or the grid is forced
+// (be_conv_pp128_set_grid); every other call goes to be_conv2d_nhwc unchanged.
+int be_conv2d_nhwc_frag(const void* x, const void* x2, const float* pscale, const float* pshift, int pshift_ns,
+                        int pscale_ns, int prelu, const void* w, const float* bias, const void* res, void* out, int N,
+                        int H, int W, int Hs, int Ws, int Cin, int Cout, int cout_valid, int ks, int ck, int tco,
+                        int inmode, int out_f32_nchw, int nw, const float* qscale, const float* qshift, int qshift_ns,
+                        const void* wfrag, hipStream_t stream) {
+  const bool shape_ok = wfrag && g_pp128 && ks == 3 && ck == 32 && inmode == 0 && !x2 && !out_f32_nchw && Cin == 128 &&
+                        Cout == 128 && Hs == H && Ws == W && !(prelu & 2) && !qscale && !qshift && x && out && N > 0 &&
+                        H > 0 && W > 0 && (long long)H * W * 256 < (1LL << 31) - 64;
+  if (shape_ok) {
+    pp128::Args a;
+    a.tiles_x = (W + pp128::TW - 1) / pp128::TW;
+    a.tiles_y = (H + pp128::TH - 1) / pp128::TH;
+    const long long tiles = (long long)N * a.tiles_x * a.tiles_y;
+    const bool forced = g_pp128_grid > 0;
+    const int g = forced ? (int)(tiles < g_pp128_grid ? tiles : g_pp128_grid) : 256;
+    if ((forced || tiles >= 2LL * g) && tiles < (1LL << 30)) {
+      a.x = (const bf16_t*)x; a.sa = pscale; a.ta = pshift; a.sa_ns = pscale_ns; a.ta_ns = pshift_ns;
+      a.wf = (const bf16_t*)wfrag; a.bias = bias; a.res = (const bf16_t*)res; a.out = (bf16_t*)out;
+      a.N = N; a.H = H; a.W = W; a.relu = prelu & 1;
+      a.stamps = g_pp128_stamps;
+      ++g_pp128_launches;
+      if (g_pp128_stamps != nullptr) {
+        if (g > g_pp128_stamps_cap) return -30;
+        hipLaunchKernelGGL(pp128::conv_pp128_kernel<true>, dim3(g), dim3(pp128::NTP), pp128::LDS, stream, a);
+        return BE_CHECK_LAUNCH();
+      }
+      hipLaunchKernelGGL(pp128::conv_pp128_kernel<false>, dim3(g), dim3(pp128::NTP), pp128::LDS, stream, a);
+      return BE_CHECK_LAUNCH();
+    }
+  }
+  return be_conv2d_nhwc(x, x2, pscale, pshift, pshift_ns, pscale_ns, prelu, w, bias, res, out, N, H, W, Hs, Ws, Cin, Cout,
+                        cout_valid, ks, ck, tco, inmode, out_f32_nchw, nw, qscale, qshift, qshift_ns, stream);
+}
+
+}  // extern "C"

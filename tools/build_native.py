@@ -61,7 +61,8 @@ HIP_FLAGS = [
 # MFMAs is slow on CDNA4; the ping-pong half-blocks run their VALU phases exactly there
 # (profiles/r05/conv/pp_noslp_ab: stem -18 %, 32->32 -7.5 %, 64->32 up -9 %, headline +1.5 %)
 PER_SOURCE_FLAGS = {"clahe": ["-ffp-contract=off"], "attention": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
-                    "gemm_mt": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"], "conv_pair": ["-fno-slp-vectorize"]}
+                    "gemm_mt": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"], "conv_pair": ["-fno-slp-vectorize"],
+                    "conv_pp128": ["-fno-slp-vectorize"]}  # conv_pp128: the same phase scheme as conv_pair
 CXX_FLAGS = ["-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-pthread", "-I", str(CSRC / "runtime")]
 
 
