@@ -45,6 +45,7 @@ from bioengine_worker_amd.cellpose.datasets import (  # noqa: F401  (re-exported
     HubArtifact,
     create_dataset_split,
     decode_image,
+    decode_labels,
     list_artifact_files,
     list_artifact_files_recursive,
     list_matching_artifact_paths,
@@ -52,6 +53,7 @@ from bioengine_worker_amd.cellpose.datasets import (  # noqa: F401  (re-exported
     make_training_pairs_from_metadata,
     match_image_annotation_pairs,
     read_image,
+    read_labels,
 )
 from bioengine_worker_amd.cellpose.model_store import BUILTIN_MODELS
 from bioengine_worker_amd.profiling import trace
@@ -446,14 +448,14 @@ class CellposeFinetune:
             x = host.to(dev, non_blocking=True)
             return x.permute(0, 3, 1, 2).contiguous() if hwc else x
 
-    async def _images_from_artifact(self, artifact: str, paths: list[str]) -> list[np.ndarray]:
+    async def _images_from_artifact(self, artifact: str, paths: list[str], reader=read_image) -> list[np.ndarray]:
         server = await self._hub()
         try:
             art = HubArtifact(await server.get_service("public/artifact-manager"), artifact)
             d = self.cache_dir / artifact.replace("/", "--")
             loc = [str(d / p.lstrip("/")) for p in paths]
             await art.get([p for p in paths], loc)
-            return [read_image(p) for p in loc]
+            return [reader(p) for p in loc]
         finally:
             await server.disconnect()
 
@@ -605,6 +607,104 @@ class CellposeFinetune:
                     fl = [np.stack([flow_rgb(y[:2]) for y in f]), f[:, :2], f[:, 2]]
                 item["flows"] = [x.tolist() for x in fl] if json_safe else fl
             out.append(item)
+        return out
+
+    # ------------------------------------------------------------------ evaluation
+    @schema_method
+    async def evaluate(
+        self,
+        artifact: str | None = Field(None, description="Artifact 'workspace/alias' containing images and annotations."),
+        image_paths: list | None = Field(None, description="Artifact-relative image paths to segment."),
+        annotation_paths: list | None = Field(None, description="Artifact-relative label images, one per image."),
+        input_arrays: list | None = Field(None, description="Images as arrays ([H,W], [H,W,C] or [C,H,W])."),
+        label_arrays: list | None = Field(None, description="Ground-truth label images [H,W], one per input array."),
+        model: str = Field("cpsam", description="Built-in model ('cpsam', 'cyto3'), a session id of a fine-tuned "
+                                                "model, or a published model artifact id."),
+        diameter: float | None = Field(None, description="Approximate object diameter (rescale to the model's 30 px)."),
+        flow_threshold: float = Field(0.4, description="Flow error threshold (QC)."),
+        cellprob_threshold: float = Field(0.0, description="Cell probability threshold."),
+        niter: int | None = Field(None, description="Flow-dynamics iterations (default 200)."),
+        enable_clahe: bool = Field(False, description="CLAHE pre-processing (brightfield / phase contrast)."),
+        thresholds: list | None = Field(None, description="IoU thresholds of the average precision "
+                                                          "(default [0.5, 0.75, 0.9]; at most 8, each in (0, 1])."),
+    ) -> dict:
+        """Segment labelled images and score the masks against their annotations: average precision
+        at each IoU threshold (``cellpose.metrics.average_precision``).  Returns ``per_image``, one
+        {input_path, ap, tp, fp, fn, n_true, n_pred} per image (lists over the thresholds; ``ap`` is
+        None where both images are empty), and ``instance_metrics``, the image-mean document a
+        training session reports.  Images of one shape are evaluated together, in chunks of 32; the
+        predicted masks are scored on the device and not returned.  2-D images only."""
+        if isinstance(artifact, dict):
+            w = artifact
+            artifact = w.get("artifact", w.get("artifact_id", w.get("id")))
+            image_paths, annotation_paths = w.get("image_paths", image_paths), w.get("annotation_paths", annotation_paths)
+            input_arrays, label_arrays = w.get("input_arrays", input_arrays), w.get("label_arrays", label_arrays)
+            model, diameter = w.get("model", model), w.get("diameter", diameter)
+            flow_threshold = w.get("flow_threshold", flow_threshold)
+            cellprob_threshold = w.get("cellprob_threshold", cellprob_threshold)
+            niter, enable_clahe = w.get("niter", niter), w.get("enable_clahe", enable_clahe)
+            thresholds = w.get("thresholds", thresholds)
+        from bioengine_worker_amd.cellpose.metrics import DEFAULT_THRESHOLDS, metrics_document
+
+        ths = [float(t) for t in (_opt(thresholds) or DEFAULT_THRESHOLDS)]
+        if len(ths) > 8 or not all(0.0 < t <= 1.0 for t in ths):
+            raise ValueError(f"thresholds must be at most 8 values in (0, 1], got {ths}")
+        model = _opt(model) or self.default_model
+        model_id = await self.resolve_model_id(model)
+        if _opt(input_arrays) is not None:
+            images = [np.asarray(a) for a in input_arrays]
+            labels = [decode_labels(np.asarray(a)) for a in (_opt(label_arrays) or [])]
+            names = [f"input_arrays[{i}]" for i in range(len(images))]
+        elif _opt(artifact) is not None:
+            names = list(image_paths or [])
+            if len(names) != len(annotation_paths or []):
+                raise ValueError(f"{len(names)} image_paths but {len(annotation_paths or [])} annotation_paths")
+            images = await self._images_from_artifact(artifact, names)
+            labels = await self._images_from_artifact(artifact, list(annotation_paths), reader=read_labels)
+        else:
+            raise ValueError("Provide input_arrays + label_arrays or artifact + image_paths + annotation_paths")
+        if len(images) != len(labels):
+            raise ValueError(f"{len(images)} images but {len(labels)} label images")
+        if _opt(enable_clahe):
+            images = [clahe_image(im, self._device()) for im in images]
+        runner = await self._runner(model_id)
+        prm = {"diameter": _opt(diameter), "flow_threshold": float(flow_threshold),
+               "cellprob_threshold": float(cellprob_threshold), "niter": int(_opt(niter) or 200)}
+        chw = [image_chw(im, runner.nchan) for im in images]
+        groups: dict = {}
+        for i, (name, c, lab) in enumerate(zip(names, chw, labels)):
+            if lab.ndim != 2 or tuple(lab.shape) != tuple(c.shape[1:]):
+                raise ValueError(f"{name}: label image of shape {tuple(lab.shape)} does not fit the image's "
+                                 f"{tuple(c.shape[1:])}")
+            groups.setdefault((c.shape, c.dtype.str), []).append(i)
+        K = len(ths)
+        ap = np.full((len(chw), K), np.nan, np.float32)
+        cnt = {k: np.zeros((len(chw), K), np.int64) for k in ("tp", "fp", "fn")}
+        n_true, n_pred = np.zeros(len(chw), np.int64), np.zeros(len(chw), np.int64)
+        for idx in groups.values():
+            for c0 in range(0, len(idx), 32):
+                part = idx[c0: c0 + 32]
+
+                def run(part=part):
+                    with self._gpu_lock:
+                        res = runner.evaluate(np.stack([chw[i] for i in part]), np.stack([labels[i] for i in part]),
+                                              thresholds=ths, **prm)
+                    res.pop("masks")
+                    return res
+
+                with trace.span("app.evaluate", images=len(part)):
+                    res = await offload(run)
+                ap[part] = res["ap"]
+                for k in cnt:
+                    cnt[k][part] = res[k]
+                n_true[part], n_pred[part] = res["n_true"], res["n_pred"]
+        per_image = [{"input_path": name,
+                      "ap": [float(a) if np.isfinite(a) else None for a in ap[i]],
+                      "tp": cnt["tp"][i].tolist(), "fp": cnt["fp"][i].tolist(), "fn": cnt["fn"][i].tolist(),
+                      "n_true": int(n_true[i]), "n_pred": int(n_pred[i])} for i, name in enumerate(names)]
+        out = {"per_image": per_image, "instance_metrics": metrics_document(ap, ths, n_true.sum(), n_pred.sum())}
+        if self._weights.get(model_id) == "random":
+            out["weights"] = "random"
         return out
 
     # ------------------------------------------------------------------ training

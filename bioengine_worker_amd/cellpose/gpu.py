@@ -1,6 +1,6 @@
 """GPU (HIP) implementation of Cellpose pre/post-processing on batches of images.
 
-Every heavy step is a kernel in ``csrc/kernels/{tiles,cellpose_dynamics,cellpose_dynamics3d,cellpose_masks,cellpose_stitch,cellpose_measure}.hip``;
+Every heavy step is a kernel in ``csrc/kernels/{tiles,cellpose_dynamics,cellpose_dynamics3d,cellpose_masks,cellpose_stitch,cellpose_measure,cellpose_ap}.hip``;
 torch is only used for tiny bookkeeping (sorting the seed keys, prefix sums over labels, building
 per-mask job lists).  The semantics are those of :mod:`bioengine_worker_amd.cellpose.reference`
 (the CPU oracle), which the GPU tests compare against.
@@ -1019,3 +1019,151 @@ def measure_masks_gpu(M: torch.Tensor, img: torch.Tensor | None = None, nlab: in
     if outlines:
         res["outlines"] = edge.bool()
     return res
+
+
+# ------------------------------------------------------------------ evaluation: average precision
+
+AP_MAX_THRESHOLDS = 8  # MAX_THR of cellpose_ap.hip
+_ap_thr: dict = {}  # (ascending thresholds, device) -> their fp64 device array
+
+
+def _ap_capacity(nt: int, np_: int, N: int) -> int:
+    """Hash slots per image pair.  The table holds every distinct (true, predicted) pair of an image,
+    background sides included: each label meets the background and a handful of labels of the other
+    image, so 8 slots per possible label keep the load factor under ~1/2; never below 1024, never
+    above the first power of two >= 2 * N (an image has at most N distinct pairs)."""
+    cap = 1 << max(10, (8 * max(nt + np_, 1) - 1).bit_length())
+    return min(cap, 1 << max(1, (2 * N - 1).bit_length()))
+
+
+def _ap_thresholds(thresholds) -> list:
+    ths = [thresholds] if np.isscalar(thresholds) else list(thresholds)
+    if len(ths) > AP_MAX_THRESHOLDS:
+        raise ValueError(f"average_precision_gpu takes at most {AP_MAX_THRESHOLDS} thresholds, got {len(ths)}")
+    for th in ths:
+        if not 0.0 < float(th) <= 1.0:
+            raise ValueError(f"average_precision_gpu: thresholds must be in (0, 1], got {th}")
+    return ths
+
+
+def _ap_host_match(t: np.ndarray, p: np.ndarray, nt: int, np_: int) -> int:
+    """Maximum-cardinality matching of the edge list (t, p): the oracle's true positives."""
+    from scipy.sparse import csr_matrix
+    from scipy.sparse.csgraph import maximum_bipartite_matching
+
+    if t.size == 0:
+        return 0
+    g = csr_matrix((np.ones(t.size, np.int8), (t, p)), shape=(nt, np_))
+    return int((maximum_bipartite_matching(g, perm_type="column") >= 0).sum())
+
+
+def average_precision_gpu(T: torch.Tensor, P: torch.Tensor, thresholds=(0.5, 0.75, 0.9), nt: int | None = None,
+                          np_: int | None = None, capacity: int | None = None, info: dict | None = None):
+    """Average precision of predicted labels ``P`` against true labels ``T`` ([B, ...] integer label
+    images or volumes of one shape): HIP implementation of :func:`metrics.average_precision`
+    (``csrc/kernels/cellpose_ap.hip``), exactly equal to it.  Returns ``(ap, tp, fp, fn)`` as numpy
+    arrays [B, K] (float32, int64, int64, int64).
+
+    The oracle's true positives are the maximum matching of the graph ``{(t, p): iou >= th}``; where
+    no label has two edges that is the edge count, which the device returns.  Only a conflicted
+    (image, threshold) cell sends that image's compact edge list to the host for
+    ``scipy.sparse.csgraph.maximum_bipartite_matching`` (possible at ``th <= 0.5`` only).
+
+    ``nt`` / ``np_``: optional upper bounds on the labels + 1 of ``T`` / ``P`` (save the ``max()`` sync;
+    they must be true bounds: a label outside them raises ``ValueError``); ``capacity``: hash slots per
+    image, a power of two (default :func:`_ap_capacity`; an overflowing table is retried at twice the
+    size).  One host read per call when bounds are given and there is no overflow or conflict.
+    ``info`` (a dict) receives ``host_matched``, the number of (image, threshold) cells solved on the
+    host, and the final ``capacity``.  Thresholds are sorted for the device and the results put back
+    in the caller's order.  CPU tensors run the oracle."""
+    from . import metrics
+
+    if not (torch.is_tensor(T) and torch.is_tensor(P)):
+        raise TypeError("average_precision_gpu expects tensors")
+    if tuple(T.shape) != tuple(P.shape):
+        raise ValueError(f"average_precision_gpu: shapes differ, {tuple(T.shape)} and {tuple(P.shape)}")
+    if T.dim() < 2:
+        raise ValueError(f"average_precision_gpu expects [B, ...] labels, got shape {tuple(T.shape)}")
+    ths = _ap_thresholds(thresholds)
+    for m in (T, P):
+        if m.dtype.is_floating_point or m.dtype.is_complex or m.dtype == torch.bool:
+            raise TypeError(f"average_precision_gpu expects integer labels, got {m.dtype}")
+    B, K = T.shape[0], len(ths)
+    if info is not None:
+        info.update(host_matched=0, capacity=0)
+    if T.device.type != "cuda" or P.device.type != "cuda":
+        ap, tp, fp, fn = metrics.average_precision([m.cpu().numpy() for m in T], [m.cpu().numpy() for m in P], ths)
+        return ap, tp, fp, fn
+    dev = T.device
+    N = T[0].numel() if B else 0
+    if N >= 2 ** 31:
+        raise ValueError("average_precision_gpu: images of 2^31 pixels or more are not supported")
+    if B > 65535:
+        raise ValueError("average_precision_gpu: at most 65535 images per call")
+    order = np.argsort(np.asarray(ths, np.float64), kind="stable")
+    sorted_ths = [float(ths[j]) for j in order]
+    tp_s = np.zeros((B, K), np.int64)
+    n_true = np.zeros(B, np.int64)
+    n_pred = np.zeros(B, np.int64)
+    if B > 0 and N > 0 and K > 0:
+        Tc = T.reshape(B, N).to(torch.int32).contiguous()
+        Pc = P.reshape(B, N).to(torch.int32).contiguous()
+        missing = [m for m, bound in ((Tc, nt), (Pc, np_)) if bound is None]
+        if missing:
+            mx = torch.stack([m.max() for m in missing]).tolist()  # one sync for the bounds not given
+            nt = mx.pop(0) + 1 if nt is None else nt
+            np_ = mx.pop(0) + 1 if np_ is None else np_
+        nt, np_ = max(int(nt), 1), max(int(np_), 1)
+        max_cap = 1 << max(1, (2 * N - 1).bit_length())
+        cap = _ap_capacity(nt, np_, N) if capacity is None else int(capacity)
+        if cap < 1 or cap & (cap - 1):
+            raise ValueError("capacity must be a power of two")
+        st = _native.stream(dev)
+        thr = _ap_thr.get((tuple(sorted_ths), dev))  # the same few threshold sets come again and again
+        if thr is None:
+            if len(_ap_thr) >= 64:
+                _ap_thr.clear()
+            thr = _ap_thr[(tuple(sorted_ths), dev)] = torch.tensor(sorted_ths, dtype=torch.float64, device=dev)
+        M = AP_MAX_THRESHOLDS
+        nwords = 2 + 2 * B * M + 2 * B  # flags, edges, conflict, n_true, n_pred: read back in one copy
+        while True:
+            # one zero-filled block: keys (64-bit), then the result words, vals, level, areas, degrees
+            sizes = [nwords, B * cap, B * cap, B * nt, B * np_, B * K * nt, B * K * np_]
+            ws = torch.zeros(B * cap + (sum(sizes) + 1) // 2, dtype=torch.int64, device=dev)
+            keys = ws[: B * cap]
+            words, vals, level, area_t, area_p, deg_t, deg_p = ws[B * cap:].view(torch.int32)[: sum(sizes)].split(sizes)
+            flags, edges, conflict, ntrue, npred = words.split([2, B * M, B * M, B, B])
+            _native.call("be_cp_ap_overlap", _native.ptr(Tc), _native.ptr(Pc), B, N, nt, np_, _native.ptr(keys),
+                         _native.ptr(vals), cap, _native.ptr(flags), st)
+            _native.call("be_cp_ap_match", _native.ptr(keys), _native.ptr(vals), B, cap, nt, np_, _native.ptr(thr), K,
+                         _native.ptr(area_t), _native.ptr(area_p), _native.ptr(edges), _native.ptr(conflict),
+                         _native.ptr(deg_t), _native.ptr(deg_p), _native.ptr(ntrue), _native.ptr(npred),
+                         _native.ptr(level), st)
+            host = words.cpu().numpy()  # the host read: every small result word in one copy
+            if host[1]:
+                raise ValueError(f"average_precision_gpu: a label lies outside its bound (nt={nt}, np_={np_})")
+            if host[0] == 0:
+                break
+            if cap >= max_cap:
+                raise RuntimeError("average_precision_gpu: overlap table overflowed at its maximum size")
+            cap *= 2  # sizing retry of launches that completed normally; bounded by the pixel count
+        h_edges = host[2: 2 + B * M].reshape(B, M)[:, :K]
+        h_conf = host[2 + B * M: 2 + 2 * B * M].reshape(B, M)[:, :K]
+        n_true[:] = host[2 + 2 * B * M: 2 + 2 * B * M + B]
+        n_pred[:] = host[2 + 2 * B * M + B:]
+        tp_s[:] = h_edges
+        hosted = 0
+        for b in np.nonzero(h_conf.any(1))[0]:
+            # this image's edge list (t, p, level), compacted on the device
+            slot = torch.nonzero(level[b * cap: (b + 1) * cap]).reshape(-1)
+            kb = keys[b * cap: (b + 1) * cap][slot]
+            el = torch.stack([kb >> 32, kb & 0xFFFFFFFF, level[b * cap: (b + 1) * cap][slot].long()]).cpu().numpy()
+            for k in np.nonzero(h_conf[b])[0]:
+                sel = el[2] > k
+                tp_s[b, k] = _ap_host_match(el[0][sel], el[1][sel], nt, np_)
+                hosted += 1
+        if info is not None:
+            info.update(host_matched=hosted, capacity=cap)
+    tp = np.zeros((B, K), np.int64)
+    tp[:, order] = tp_s
+    return metrics.ap_from_counts(tp, n_true, n_pred)

@@ -55,12 +55,64 @@ def true_positive(iou: np.ndarray, th: float) -> int:
     return int((iou[ti, pi] >= th).sum())
 
 
+def ap_from_counts(tp: np.ndarray, n_true: np.ndarray, n_pred: np.ndarray):
+    """(ap, tp, fp, fn) [n_images, n_thresholds] from the true positives and the label maxima, row
+    by row with the expressions of :func:`average_precision` (so ``ap`` is bit-identical to it)."""
+    tp = np.asarray(tp, np.int64)
+    ap = np.zeros(tp.shape, np.float32)
+    fp = np.zeros(tp.shape, np.int64)
+    fn = np.zeros(tp.shape, np.int64)
+    for i in range(tp.shape[0]):
+        fp[i] = int(n_pred[i]) - tp[i]
+        fn[i] = int(n_true[i]) - tp[i]
+        with np.errstate(invalid="ignore", divide="ignore"):
+            ap[i] = tp[i] / (tp[i] + fp[i] + fn[i]).astype(np.float32)
+    return ap, tp, fp, fn
+
+
+def _device_labels(m) -> bool:
+    return (isinstance(m, torch.Tensor) and m.device.type == "cuda" and m.dim() >= 1 and m.numel() > 0
+            and not (m.dtype.is_floating_point or m.dtype.is_complex or m.dtype == torch.bool))
+
+
+def _on_device(masks_true, masks_pred) -> bool:
+    """Every item of both lists is a CUDA integer tensor, pairwise of one shape: the GPU scorer takes them."""
+    return (len(masks_true) > 0 and len(masks_true) == len(masks_pred)
+            and all(_device_labels(t) and _device_labels(p) and t.shape == p.shape and t.device == p.device
+                    for t, p in zip(masks_true, masks_pred)))
+
+
+def _average_precision_device(masks_true, masks_pred, ths):
+    """Device tensors: items of one shape are one batch of :func:`gpu.average_precision_gpu`."""
+    from .gpu import AP_MAX_THRESHOLDS, average_precision_gpu
+
+    n = len(masks_true)
+    tp = np.zeros((n, len(ths)), np.int64)
+    n_true, n_pred = np.zeros(n, np.int64), np.zeros(n, np.int64)
+    groups: dict = {}
+    for i, t in enumerate(masks_true):
+        groups.setdefault((tuple(t.shape), t.device), []).append(i)
+    for idx in groups.values():
+        T = torch.stack([masks_true[i] for i in idx])
+        P = torch.stack([masks_pred[i] for i in idx])
+        for k0 in range(0, len(ths), AP_MAX_THRESHOLDS):
+            _, g_tp, g_fp, g_fn = average_precision_gpu(T, P, ths[k0: k0 + AP_MAX_THRESHOLDS])
+            tp[idx, k0: k0 + g_tp.shape[1]] = g_tp
+            n_true[idx], n_pred[idx] = (g_tp + g_fn)[:, 0], (g_tp + g_fp)[:, 0]
+    return ap_from_counts(tp, n_true, n_pred)
+
+
 def average_precision(masks_true, masks_pred, threshold=DEFAULT_THRESHOLDS):
-    """Returns (ap, tp, fp, fn) each [n_images, n_thresholds] (single arrays -> [n_thresholds])."""
+    """Returns (ap, tp, fp, fn) each [n_images, n_thresholds] (single arrays -> [n_thresholds]).
+    CUDA integer tensors are scored on the device (:func:`gpu.average_precision_gpu`, exactly equal);
+    every other input takes the numpy path below."""
     single = not isinstance(masks_true, (list, tuple))
     if single:
         masks_true, masks_pred = [masks_true], [masks_pred]
     ths = [threshold] if np.isscalar(threshold) else list(threshold)
+    if ths and all(0.0 < float(th) <= 1.0 for th in ths) and _on_device(masks_true, masks_pred):
+        res = _average_precision_device(list(masks_true), list(masks_pred), ths)
+        return tuple(r[0] for r in res) if single else res
     n = len(masks_true)
     ap = np.zeros((n, len(ths)), np.float32)
     tp = np.zeros((n, len(ths)), np.int64)
@@ -84,11 +136,20 @@ def average_precision(masks_true, masks_pred, threshold=DEFAULT_THRESHOLDS):
 
 def instance_metrics(masks_true, masks_pred, threshold=DEFAULT_THRESHOLDS) -> dict:
     """The reference's InstanceMetrics document (image-mean AP at 0.5 / 0.75 / 0.9 + label counts)."""
-    ap, _, _, _ = average_precision(list(masks_true), list(masks_pred), threshold)
+    masks_true, masks_pred = list(masks_true), list(masks_pred)
+    ap, tp, fp, fn = average_precision(masks_true, masks_pred, threshold)
+    if tp.shape[1] > 0 and _on_device(masks_true, masks_pred):  # scored on the device: tp + fn is the label maximum
+        return metrics_document(ap, threshold, (tp + fn)[:, 0].sum(), (tp + fp)[:, 0].sum())
+    return metrics_document(ap, threshold, sum(int(torch.as_tensor(m).max().item()) for m in masks_true),
+                            sum(int(torch.as_tensor(m).max().item()) for m in masks_pred))
+
+
+def metrics_document(ap: np.ndarray, threshold, n_true, n_pred) -> dict:
+    """The InstanceMetrics document from per-image ``ap`` [n_images, n_thresholds] and the label totals."""
     with np.errstate(all="ignore"):
         mean_ap = np.nanmean(ap, axis=0) if len(ap) else np.full(len(threshold), np.nan)
     out = {f"ap_{str(t).replace('.', '_')}": (round(float(m), 4) if np.isfinite(m) else None)
            for t, m in zip(threshold, mean_ap)}
-    out["n_true"] = int(sum(int(torch.as_tensor(m).max().item()) for m in masks_true))
-    out["n_pred"] = int(sum(int(torch.as_tensor(m).max().item()) for m in masks_pred))
+    out["n_true"] = int(n_true)
+    out["n_pred"] = int(n_pred)
     return out

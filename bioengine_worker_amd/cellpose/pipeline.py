@@ -625,6 +625,49 @@ class CellposeRunner:
         raws = measure_launch(m, img, volume=volume)
         return measure_tables(raws, volume)
 
+    # ---------------------------------------------------------------- evaluation
+    def score(self, masks_true, masks_pred, thresholds=(0.5, 0.75, 0.9), volume: bool = False) -> dict:
+        """Average precision of predicted labels against ground truth (:func:`metrics.average_precision`).
+
+        ``masks_pred``: [B, H, W] (or one [H, W] image), as :meth:`eval` returns them; with
+        ``volume=True`` one [Z, H, W] volume scored as one image.  ``masks_true``: the same shape,
+        numpy or torch; it is moved to the prediction's device.  Returns ``ap`` (float32), ``tp``,
+        ``fp``, ``fn`` as numpy arrays [B, K], ``n_true`` and ``n_pred`` [B] (the label maxima), and
+        under ``summary`` the :func:`metrics.instance_metrics` document.  Predictions on the GPU are
+        scored by the HIP kernels (:func:`gpu.average_precision_gpu`; a ``label_bound`` on the
+        prediction saves its ``max()`` sync), everything else by the numpy oracle."""
+        from . import metrics
+        from .gpu import average_precision_gpu
+
+        mp = masks_pred if torch.is_tensor(masks_pred) else torch.as_tensor(np.asarray(masks_pred))
+        mt = masks_true if torch.is_tensor(masks_true) else torch.as_tensor(np.asarray(masks_true))
+        if tuple(mt.shape) != tuple(mp.shape):
+            raise ValueError(f"score: true masks {tuple(mt.shape)} do not fit predicted masks {tuple(mp.shape)}")
+        if volume:
+            if mp.dim() != 3:
+                raise ValueError(f"score(volume=True) expects one [Z, H, W] volume, got shape {tuple(mp.shape)}")
+            mt, mp = mt[None], mp[None]
+        elif mp.dim() == 2:
+            mt, mp = mt[None], mp[None]
+        if mp.dim() < 3:
+            raise ValueError(f"score expects [B, H, W] masks or one [Z, H, W] volume, got shape {tuple(mp.shape)}")
+        ths = [thresholds] if np.isscalar(thresholds) else list(thresholds)
+        bound = getattr(masks_pred, "label_bound", None)
+        ap, tp, fp, fn = average_precision_gpu(mt.to(mp.device), mp, ths, np_=bound)
+        n_true, n_pred = (tp + fn)[:, 0], (tp + fp)[:, 0]
+        return {"ap": ap, "tp": tp, "fp": fp, "fn": fn, "n_true": n_true, "n_pred": n_pred,
+                "summary": metrics.metrics_document(ap, ths, n_true.sum(), n_pred.sum())}
+
+    @torch.no_grad()
+    def evaluate(self, images, masks_true, p: EvalParams | None = None, thresholds=(0.5, 0.75, 0.9), **kw) -> dict:
+        """:meth:`eval` with the given parameters, then :meth:`score` of its masks against
+        ``masks_true`` on the device they were computed on.  Returns :meth:`score`'s dict plus
+        ``masks`` (the [B, H, W] int32 tensor of :meth:`eval`, not copied to the host)."""
+        masks, _, _ = self.eval(images, p, **kw)
+        res = self.score(masks_true, masks, thresholds)
+        res["masks"] = masks
+        return res
+
 
 def _planes_first(stack) -> torch.Tensor:
     """[Z, H, W], [Z, C, H, W] or [Z, H, W, C] -> [Z, C, H, W], as eval_stack reads a z-stack."""

@@ -327,13 +327,19 @@ def train_session_rank(rank: int, world: int, session_dir: str, params: dict, cp
 
 def instance_metrics(net, test_imgs, test_labs, device) -> dict:
     """Full Cellpose eval of the fine-tuned net on every test image, then AP at IoU 0.5/0.75/0.9
-    (reference main.py:1977-2029)."""
+    (reference main.py:1977-2029).  Images are segmented one at a time (the kernel choice depends on
+    the batch size, so the masks stay what they were); on a GPU the masks stay there and are scored
+    there, images of one shape as one batch."""
     from ..cellpose.metrics import instance_metrics as im
     from ..cellpose.pipeline import CellposeRunner
 
     runner = CellposeRunner(net=net.eval(), device=device)
+    on_gpu = runner.device.type == "cuda"
     preds = []
     for img in test_imgs:
         masks, _, _ = runner.eval(np.asarray(img)[None])
-        preds.append(masks[0].cpu().numpy())
-    return im([np.asarray(l, np.int32) for l in test_labs], preds)
+        preds.append(masks[0] if on_gpu else masks[0].cpu().numpy())
+    labs = [np.asarray(l, np.int32) for l in test_labs]
+    if on_gpu:
+        labs = [torch.from_numpy(np.ascontiguousarray(l)).to(runner.device) for l in labs]
+    return im(labs, preds)
