@@ -222,10 +222,11 @@ class _FConv:
         self.shift = _pad_vec(t, self.pc.cin_pad, 0.0)
         self.relu = relu
 
-    def __call__(self, x, *, x2=None, shift=None, residual=None, inmode="none", out_nchw_f32=False, cout_valid=None):
+    def __call__(self, x, *, x2=None, shift=None, residual=None, inmode="none", out_nchw_f32=False, cout_valid=None,
+                 residual_mode="full"):
         return convops.fused_conv2d(x, self.pc, x2=x2, scale=self.scale, shift=self.shift if shift is None else shift,
                                     relu=self.relu, residual=residual, inmode=inmode, out_nchw_f32=out_nchw_f32,
-                                    cout_valid=cout_valid)
+                                    cout_valid=cout_valid, residual_mode=residual_mode)
 
 
 class _PPConv:
@@ -326,20 +327,26 @@ class CPnetEngine:
             return {}
         pairs = {}
 
-        def spec(a: _FConv, b: _FConv, inmode="none", proj: _FConv | None = None, style_b=False):
+        def spec(a: _FConv, b: _FConv, inmode="none", proj: _FConv | None = None, style_b=False, proj_rounded=False):
+            # proj_rounded (pairops.PROJ_CONFIGS): the projection is rounded to bf16 before it is added,
+            # as when it is a tensor of its own, so its bias stays apart from convB's
             bias = b.pc.bias if b.pc.bias is not None else torch.zeros(b.pc.cout, device=self.device)
-            if proj is not None and proj.pc.bias is not None:
+            bias_p = None
+            if proj is not None and proj_rounded:
+                pb_ = proj.pc.bias if proj.pc.bias is not None else torch.zeros(proj.pc.cout, device=self.device)
+                bias_p = pb_.float().contiguous()
+            elif proj is not None and proj.pc.bias is not None:
                 bias = bias + proj.pc.bias
             tb = None if style_b else pairops.fold_bias(b.shift, b.scale, a.pc.bias).contiguous()
             return pairops.PairSpec(pa=a.pc, pb=b.pc, sa=a.scale, ta=a.shift, sb=b.scale, tb=tb,
                                     bias=bias.float().contiguous(), inmode=inmode,
                                     pp=None if proj is None else proj.pc, sp=None if proj is None else proj.scale,
-                                    tp=None if proj is None else proj.shift)
+                                    tp=None if proj is None else proj.shift, bias_p=bias_p)
 
         d0, d1 = self.down[0], self.down[1]
         pairs[("down", 0, 0)] = spec(d0["c0"], d0["c1"], "none", proj=d0["proj"])
         pairs[("down", 0, 1)] = spec(d0["c2"], d0["c3"])
-        pairs[("down", 1, 0)] = spec(d1["c0"], d1["c1"], "pool2")
+        pairs[("down", 1, 0)] = spec(d1["c0"], d1["c1"], "pool2", proj=d1["proj"], proj_rounded=True)
         pairs[("down", 1, 1)] = spec(d1["c2"], d1["c3"])
         nup = len(self.up)
         for i in (0, 1):
@@ -361,12 +368,14 @@ class CPnetEngine:
         pairs = {k: v for k, v in pairs.items() if k[1] in keep}
         for key, sp in pairs.items():
             has_x2 = key[0] == "up" and key[2] == 0
-            res = "none" if key == ("down", 0, 0) else ("up2" if has_x2 else "full")
+            res = "none" if sp.pp is not None else ("up2" if has_x2 else "full")
             assert sp.supports(has_x2, res), key
             # fragment-order weights of the level-1 ping-pong kernel: packed here, not in the first forward
-            if (sp.cin, sp.cm, sp.inmode, has_x2, sp.pp is not None, res) in pairops.FRAG_CONFIGS \
-                    and torch.device(self.device).type == "cuda":
+            cfg = (sp.cin, sp.cm, sp.inmode, has_x2, sp.pp is not None, res)
+            if cfg in pairops.FRAG_CONFIGS | pairops.PROJ_CONFIGS and torch.device(self.device).type == "cuda":
                 sp.frag(sp.pa.wp.device)
+                if cfg in pairops.PROJ_CONFIGS:
+                    sp.frag_proj(sp.pa.wp.device)
         return pairs
 
     def _build_igemm(self, net: CPnet) -> dict:
@@ -487,6 +496,10 @@ class CPnetEngine:
             if ("down", n, 0) in P:
                 if n == 0:  # stem: projection computed inside the fused kernel (K concatenation)
                     x1 = pairops.conv_pair(src, P[("down", 0, 0)])
+                elif P[("down", n, 0)].pp is not None:
+                    # level 1: the spec carries the projection; large calls compute it inside the
+                    # ping-pong kernel, small ones as today's two launches (ops/conv_pair.py decides)
+                    x1 = pairops.conv_pair(src, P[("down", n, 0)])
                 else:
                     x1 = pairops.conv_pair(src, P[("down", n, 0)], res=e["proj"](src, inmode=im), res_mode="full")
                 xd.append(pairops.conv_pair(x1, P[("down", n, 1)], res=x1, res_mode="full"))
@@ -521,11 +534,17 @@ class CPnetEngine:
                 xcur = pairops.conv_pair(x1, P[("up", i, 1)], ta=shifts[(i, 2)], tb=shifts[(i, 3)], res=x1,
                                          res_mode="full")
                 continue
-            proj = e["proj"](xcur, inmode=im)
             # the skip add (conv1's input is c0(x) + y) runs in c0's residual epilogue, so conv1
             # reads one tensor instead of two (the two-input variant was ~1.7x slower per layer)
             h0 = e["c0"](xcur, inmode=im, residual=y)
-            x1 = e["c1"](h0, shift=shifts[(i, 1)], residual=proj)
+            # as on the pair levels, the projection runs at half resolution where conv1's kernel can
+            # read it through an up2 residual (the 128-channel ping-pong kernel at 56^2: a quarter of
+            # the projection's work and of the bytes written and read back); asked of the native side
+            # per call, so small batches keep the full-resolution projection on the per-layer kernel
+            if im == "up2" and xcur.is_cuda and convops.pp128_takes_res_up2(e["c1"].pc, h0):
+                x1 = e["c1"](h0, shift=shifts[(i, 1)], residual=e["proj"](xcur), residual_mode="up2")
+            else:
+                x1 = e["c1"](h0, shift=shifts[(i, 1)], residual=e["proj"](xcur, inmode=im))
             h2 = e["c2"](x1, shift=shifts[(i, 2)])
             xcur = e["c3"](h2, shift=shifts[(i, 3)], residual=x1)
         y = self.out(xcur, out_nchw_f32=True, cout_valid=self.nout)

@@ -265,12 +265,27 @@ def _affine_stride(t: torch.Tensor | None, N: int, C: int) -> int:
     return 0
 
 
+def pp128_takes_res_up2(pc: PackedConv, x: torch.Tensor) -> bool:
+    """Whether ``fused_conv2d(x, pc, residual=r, residual_mode="up2")`` may be called: the conv has its
+    fragment-order weights and the native side (``be_conv_pp128_takes_res_up2``, the ping-pong
+    kernel's own size rule and switches) takes a call of ``x``'s geometry.  Always true on the CPU."""
+    if not x.is_cuda:
+        return True
+    if not frag_eligible(pc) or pc.frag_built() is None:
+        return False
+    N, H, W, _ = x.shape
+    return bool(_native.hip().be_conv_pp128_takes_res_up2(N, H, W))
+
+
 def fused_conv2d(x: torch.Tensor, pc: PackedConv, *, x2=None, scale=None, shift=None, relu=False, residual=None,
                  inmode: str = "none", out_nchw_f32: bool = False, cout_valid: int | None = None,
                  nw: int | None = None, post_relu: bool = False, out: torch.Tensor | None = None,
-                 no_bias: bool = False, post_scale=None, post_shift=None) -> torch.Tensor:
+                 no_bias: bool = False, post_scale=None, post_shift=None, residual_mode: str = "full") -> torch.Tensor:
     """Fused conv on NHWC activations.  ``x`` is [N, Hs, Ws, Cin_pad] bf16 (GPU) or any float (CPU).
     ``relu`` applies to the pre-activation input, ``post_relu`` to the output (after bias/residual).
+    ``residual_mode="up2"``: ``residual`` is [N, H/2, W/2, Cout] and is added through nearest 2x
+    up-sampling (a 1x1 projection of an up-sampled map, computed before the up-sampling).  On the GPU
+    only the 128-channel ping-pong kernel reads it that way: ask :func:`pp128_takes_res_up2` first.
     ``out`` (bf16 NHWC, contiguous) receives the result in place of a new tensor; it may be the
     ``residual`` itself (every output element reads its residual before it is stored).
     ``no_bias`` skips ``pc.bias`` (partial sums of a depth-decomposed 3-D conv).
@@ -284,7 +299,13 @@ def fused_conv2d(x: torch.Tensor, pc: PackedConv, *, x2=None, scale=None, shift=
         H, W = Hs // 2, Ws // 2
     else:
         H, W = Hs, Ws
+    assert residual_mode in ("full", "up2")
+    up2 = residual is not None and residual_mode == "up2"
+    if up2:
+        assert H % 2 == 0 and W % 2 == 0 and residual.shape == (N, H // 2, W // 2, pc.cout)
     if not x.is_cuda:
+        if up2:
+            residual = residual.repeat_interleave(2, dim=1).repeat_interleave(2, dim=2)
         y = fused_conv2d_ref(x, pc, x2, scale, shift, relu, residual, inmode, out_nchw_f32, cout_valid,
                              act_dtype=torch.bfloat16 if x.dtype == torch.bfloat16 else None,
                              post_relu=post_relu and post_scale is None and post_shift is None, no_bias=no_bias)
@@ -321,7 +342,8 @@ def fused_conv2d(x: torch.Tensor, pc: PackedConv, *, x2=None, scale=None, shift=
     if x2 is not None:
         assert x2.shape == (N, H, W, Cin) and x2.dtype == torch.bfloat16 and x2.is_contiguous()
     if residual is not None:
-        assert residual.shape == (N, H, W, pc.cout) and residual.dtype == torch.bfloat16 and residual.is_contiguous()
+        assert residual.shape == ((N, H // 2, W // 2, pc.cout) if up2 else (N, H, W, pc.cout))
+        assert residual.dtype == torch.bfloat16 and residual.is_contiguous()
     # per-image affines ([N, Cin], GroupNorm scale / style shift) may be row-strided views (e.g. column
     # slices of one stacked style GEMM output): rows are read as float4 runs at n * row_stride + c
     pscale_ns = _affine_stride(scale, N, Cin)
@@ -332,15 +354,18 @@ def fused_conv2d(x: torch.Tensor, pc: PackedConv, *, x2=None, scale=None, shift=
     # the layers with a ping-pong build also pass their fragment-order weights; the entry point picks
     # the kernel (csrc/kernels/conv_pp128.hip, be_conv2d_nhwc_frag)
     wf = pc.frag_built() if frag_eligible(pc) else None
-    _native.call(
-        "be_conv2d_nhwc_frag",
+    args = (
         _native.ptr(x), _native.ptr(x2), _native.ptr(scale), _native.ptr(shift), pshift_ns, pscale_ns,
         int(bool(relu)) | (2 if post_relu else 0),
         _native.ptr(pc.wp), _native.ptr(None if no_bias else pc.bias), _native.ptr(residual), _native.ptr(out),
         N, H, W, Hs, Ws, Cin, cout_store, cout_valid, pc.ks, pc.ck, pc.tco, INMODES[inmode], int(out_nchw_f32),
         int(nw or choose_nw(pc, H, W, inmode, x2 is not None)), _native.ptr(post_scale), _native.ptr(post_shift),
-        qshift_ns, _native.ptr(wf), _native.stream(x.device),
+        qshift_ns, _native.ptr(wf),
     )
+    if up2:  # an error, not a fallback, when the ping-pong kernel does not take the call
+        _native.call("be_conv2d_nhwc_frag_res", *args, 1, _native.stream(x.device))
+    else:
+        _native.call("be_conv2d_nhwc_frag", *args, _native.stream(x.device))
     return out
 
 

@@ -22,7 +22,7 @@ import torch
 import torch.nn.functional as F
 
 from . import _native
-from .conv import INMODES, PackedConv, _act_ref, _affine_stride
+from .conv import INMODES, PackedConv, _act_ref, _affine_stride, fused_conv2d, fused_conv2d_ref
 
 #: (Cin, CM, inmode, x2, proj, res) combinations the kernel is instantiated for (CPnet levels 0/1)
 SUPPORTED = {
@@ -41,6 +41,29 @@ FRAG_CONFIGS = {
     (32, 64, "pool2", False, False, "full"),
     (128, 64, "up2", True, False, "up2"),
 }
+#: configurations whose projection is ROUNDED to bf16 before it is added (``PairSpec.bias_p`` apart
+#: from ``bias``): the result of the per-layer 1x1 projection followed by the pair with that tensor
+#: as its residual, which is also how they run (two launches) unless the native side takes the call
+#: on the ping-pong build with the projection inside (``be_conv_pair_proj``)
+PROJ_CONFIGS = {
+    (32, 64, "pool2", False, True, "none"),
+}
+SUPPORTED |= PROJ_CONFIGS
+
+
+def pack_proj_frag(wp: torch.Tensor) -> torch.Tensor:
+    """A 1x1 projection's ``PackedConv.wp`` ``[64, 1, 32]`` in MFMA-A-fragment order
+    ``[1, 4 channel tiles, 64 lanes, 8]``: lane ``kq * 16 + lrow`` of channel tile ``ct`` holds
+    ``wp[ct * 16 + lrow, 0, kq * 8 : kq * 8 + 8]`` (one K-step of :func:`pack_frag`'s layout)."""
+    cout, nchunk, kp = wp.shape
+    assert cout == 64 and nchunk == 1 and kp == 32, "projection fragments: 32 -> 64 channels, 1x1"
+    t = wp.reshape(4, 16, 4, 8)                      # ct, lrow, kq, e
+    return t.permute(0, 2, 1, 3).contiguous().reshape(1, 4, 64, 8)
+
+
+def unpack_proj_frag(wf: torch.Tensor) -> torch.Tensor:
+    """Inverse of :func:`pack_proj_frag`."""
+    return wf.reshape(4, 4, 16, 8).permute(0, 2, 1, 3).contiguous().reshape(64, 1, 32)
 
 
 def pack_frag(wp: torch.Tensor) -> torch.Tensor:
@@ -67,7 +90,8 @@ class PairSpec:
 
     ``tb`` is actB's shift with convA's bias folded in (``tB + sB * biasA``) when it is shared; for a
     per-image shift the caller folds it into the style GEMM constants instead (``tb`` then None).
-    ``bias`` is convB's bias plus the projection's bias."""
+    ``bias`` is convB's bias plus the projection's bias, except in ``PROJ_CONFIGS``, where the
+    projection is rounded to bf16 on its own and keeps its bias in ``bias_p``."""
 
     pa: PackedConv
     pb: PackedConv
@@ -82,13 +106,30 @@ class PairSpec:
     tp: torch.Tensor | None = None
     #: fragment-order copies of ``pa.wp`` / ``pb.wp`` per device, built on first use (:meth:`frag`)
     frag_cache: dict | None = None
+    #: ``PROJ_CONFIGS`` only: the projection's bias [CM] (zeros without one), NOT folded into ``bias``
+    bias_p: torch.Tensor | None = None
+    proj_frag_cache: dict | None = None
+    plain: "PairSpec | None" = None
+
+    def proj_rounded(self, has_x2: bool, res: str) -> bool:
+        """The call is one of ``PROJ_CONFIGS``: projection rounded to bf16, its bias in ``bias_p``."""
+        return self.bias_p is not None and (self.cin, self.cm, self.inmode, has_x2, self.pp is not None, res) in PROJ_CONFIGS
+
+    def frag_proj(self, device: torch.device) -> torch.Tensor:
+        """``pack_proj_frag(pp.wp)`` on ``device``; packed once and kept with the spec, as :meth:`frag`."""
+        key = (str(device), self.pp.wp.data_ptr())
+        if self.proj_frag_cache is None or self.proj_frag_cache.get("key") != key:
+            self.proj_frag_cache = {"key": key, "w": pack_proj_frag(self.pp.wp.to(device))}
+        return self.proj_frag_cache["w"]
 
     def frag(self, device: torch.device) -> tuple[torch.Tensor, torch.Tensor]:
         """``(pack_frag(pa.wp), pack_frag(pb.wp))`` on ``device``; packed once and kept with the spec
         (repacked if the packed weights were replaced)."""
         key = (str(device), self.pa.wp.data_ptr(), self.pb.wp.data_ptr())
-        if self.frag_cache is None or self.frag_cache.get("key") != key:
-            self.frag_cache = {"key": key, "w": (pack_frag(self.pa.wp.to(device)), pack_frag(self.pb.wp.to(device)))}
+        if self.frag_cache is None:
+            self.frag_cache = {}
+        if self.frag_cache.get("key") != key:  # updated in place: without_proj() shares the dict
+            self.frag_cache.update(key=key, w=(pack_frag(self.pa.wp.to(device)), pack_frag(self.pb.wp.to(device))))
         return self.frag_cache["w"]
 
     @property
@@ -100,7 +141,18 @@ class PairSpec:
         return self.pa.cin_pad
 
     def supports(self, has_x2: bool, res: str) -> bool:
-        return (self.cin, self.cm, self.inmode, has_x2, self.pp is not None, res) in SUPPORTED
+        cfg = (self.cin, self.cm, self.inmode, has_x2, self.pp is not None, res)
+        return cfg in SUPPORTED and (cfg in PROJ_CONFIGS) == (self.bias_p is not None)
+
+    def without_proj(self) -> "PairSpec":
+        """The same half-block taking its projection as a residual: shares every tensor, made once (its
+        fragment cache is this spec's, so neither route packs twice)."""
+        if self.frag_cache is None:
+            self.frag_cache = {}
+        if self.plain is None:
+            self.plain = PairSpec(pa=self.pa, pb=self.pb, sa=self.sa, ta=self.ta, sb=self.sb, tb=self.tb,
+                                  bias=self.bias, inmode=self.inmode, frag_cache=self.frag_cache)
+        return self.plain
 
 
 def fold_bias(shift: torch.Tensor, scale: torch.Tensor, bias: torch.Tensor | None) -> torch.Tensor:
@@ -126,6 +178,10 @@ def conv_pair_ref(x, spec: PairSpec, *, ta=None, tb=None, x2=None, res=None, res
     """fp32 PyTorch oracle with the kernel's two bf16 rounding points (activated input, h)."""
     ta = spec.ta if ta is None else ta
     tb = spec.tb if tb is None else tb
+    if spec.proj_rounded(x2 is not None, "none" if res is None else res_mode):
+        # the composition of the two existing references: the per-layer projection, then the pair
+        proj = fused_conv2d_ref(x, spec.pp, scale=spec.sp, shift=spec.tp, inmode=spec.inmode)
+        return conv_pair_ref(x, spec.without_proj(), ta=ta, tb=tb, res=proj, res_mode="full")
     xf = x.float()
     a = _act_ref(xf, None, spec.sa, ta, True, spec.inmode).to(torch.bfloat16).float()
     wa = spec.pa.w.to(a.device)
@@ -176,6 +232,8 @@ def conv_pair(x: torch.Tensor, spec: PairSpec, *, ta=None, tb=None, x2=None, res
     CM = spec.cm
     assert x.dtype == torch.bfloat16 and x.is_contiguous(), "conv_pair expects contiguous NHWC bf16"
     assert Cin == spec.cin, f"input channels {Cin} != packed {spec.cin}"
+    if spec.proj_rounded(x2 is not None, res_mode):
+        return _conv_pair_proj(x, spec, ta, tb, out)
     if not spec.supports(x2 is not None, res_mode):
         raise ValueError(f"conv_pair: unsupported configuration {(Cin, CM, spec.inmode, x2 is not None, spec.pp is not None, res_mode)}")
     if x2 is not None:
@@ -202,6 +260,39 @@ def conv_pair(x: torch.Tensor, spec: PairSpec, *, ta=None, tb=None, x2=None, res
         _native.ptr(spec.pb.wp), _native.ptr(None if pp is None else pp.wp), _native.ptr(spec.bias),
         _native.ptr(res), _native.ptr(out), N, H, W, Hs, Ws, Cin, CM, INMODES[spec.inmode], int(pp is not None),
         RESMODES[res_mode], _native.ptr(waf), _native.ptr(wbf), _native.stream(x.device),
+    )
+    return out
+
+
+def proj_fused(x: torch.Tensor, spec: PairSpec) -> bool:
+    """Whether a ``PROJ_CONFIGS`` call on ``x`` runs as ONE launch with the projection inside the
+    ping-pong kernel.  The native side decides (``be_conv_pair_proj_takes``: the ping-pong kernel's own
+    size rule, ``BE_PAIR_PP64``, the forced grid and the fusion's switch ``BE_PAIR_PP64_PROJ``)
+    before anything is launched."""
+    H, W = _out_hw(x, spec.inmode)
+    return x.is_cuda and bool(_native.hip().be_conv_pair_proj_takes(x.shape[0], H, W))
+
+
+def _conv_pair_proj(x, spec: PairSpec, ta, tb, out):
+    N, Hs, Ws, Cin = x.shape
+    H, W = _out_hw(x, spec.inmode)
+    if not proj_fused(x, spec):
+        # small calls (batch-1 latency, default-grid tests): the per-layer projection, then the pair
+        proj = fused_conv2d(x, spec.pp, scale=spec.sp, shift=spec.tp, inmode=spec.inmode)
+        return conv_pair(x, spec.without_proj(), ta=ta, tb=tb, res=proj, res_mode="full", out=out)
+    CM = spec.cm
+    if out is None:
+        out = torch.empty(N, H, W, CM, device=x.device, dtype=torch.bfloat16)
+    else:
+        assert out.shape == (N, H, W, CM) and out.dtype == torch.bfloat16 and out.is_contiguous()
+        assert out.data_ptr() != x.data_ptr(), "conv_pair cannot run in place"
+    waf, wbf = spec.frag(x.device)
+    _native.call(
+        "be_conv_pair_proj",
+        _native.ptr(x), _native.ptr(spec.sa), _native.ptr(ta), _affine_stride(ta, N, Cin), _native.ptr(spec.sb),
+        _native.ptr(tb), _affine_stride(tb, N, CM), _native.ptr(spec.sp), _native.ptr(spec.tp), _native.ptr(spec.pa.wp),
+        _native.ptr(spec.pb.wp), _native.ptr(spec.bias), _native.ptr(spec.bias_p), _native.ptr(out), N, H, W, Hs, Ws,
+        Cin, CM, _native.ptr(waf), _native.ptr(wbf), _native.ptr(spec.frag_proj(x.device)), _native.stream(x.device),
     )
     return out
 

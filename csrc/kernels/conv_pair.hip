@@ -34,6 +34,8 @@
 //    for CM = 32 (16 x 32 tiles, weights resident in LDS), conv_pair_pp64.inc for CM = 64
 //    (16 x 16 tiles, weights fetched from L2 in MFMA-fragment order, 81 KB of LDS).  The
 //    one-group kernel keeps the small calls (batch-1 latency).  All three give the same bits.
+//    The level-1 pool2 half-block's CM = 64 ping-pong build also computes the block's 1x1 projection
+//    (be_conv_pair_proj); small calls keep it as a launch of its own and read it as `res`.
 //  * pixel strides are 8 (mod 16) dwords, so ds_read_b128 fragment reads are conflict-free for any
 //    tap offset (same rule as conv2d_nhwc.hip).
 #include <cstdlib>
@@ -53,6 +55,9 @@ struct PairArgs {
   const bf16_t* wp;                             // [CM][1][32]
   const float* bias;                            // [CM] convB bias (+ projection bias)
   const bf16_t* waf; const bf16_t* wbf;         // wa / wb in MFMA-fragment order (conv_pair_pp64.inc), or null
+  // pp64 PROJ build only: the projection in fragment order [4 ct][64 lanes][8] and its own bias [CM]
+  // (the projection is rounded to bf16 before it is added, so its bias cannot ride in `bias`)
+  const bf16_t* wpf; const float* biasp;
   const bf16_t* res;                            // [N, H, W, CM] or [N, H/2, W/2, CM] (RES = 2)
   bf16_t* out;                                  // [N, H, W, CM]
   // HEAD (final up half-block only): the network's output conv fused into the epilogue,
@@ -954,8 +959,9 @@ int launch_pair_pp(PairArgs a, int grid_cap, hipStream_t s) {
 
 #include "conv_pair_pp64.inc"
 
-template <int NCA, int INMODE, bool X2, int RES>
+template <int NCA, int INMODE, bool X2, int RES, bool PROJ = false>
 int launch_pair_pp64(PairArgs a, int grid_cap, hipStream_t s) {
+  constexpr int lds = PROJ ? pp64::LDS_PROJ : pp64::LDS;
   a.tiles_x = (a.W + pp64::TS - 1) / pp64::TS;
   a.tiles_y = (a.H + pp64::TS - 1) / pp64::TS;
   const int tiles = a.N * a.tiles_x * a.tiles_y;
@@ -965,19 +971,19 @@ int launch_pair_pp64(PairArgs a, int grid_cap, hipStream_t s) {
   a.stamps = nullptr;
   static bool attr_set[BE_MAX_DEV] = {};
   if (!attr_set[be_cur_dev()]) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&pp64::conv_pair_pp64_kernel<NCA, INMODE, X2, RES>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, pp64::LDS);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&pp64::conv_pair_pp64_kernel<NCA, INMODE, X2, RES, true>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, pp64::LDS);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&pp64::conv_pair_pp64_kernel<NCA, INMODE, X2, RES, false, PROJ>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&pp64::conv_pair_pp64_kernel<NCA, INMODE, X2, RES, true, PROJ>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     attr_set[be_cur_dev()] = true;
   }
   if (g_pp_stamps != nullptr) {  // diagnostics: be_conv_pair_pp_set_stamps
     if (g > g_pp_stamps_cap) return -30;
     a.stamps = g_pp_stamps;
-    hipLaunchKernelGGL((pp64::conv_pair_pp64_kernel<NCA, INMODE, X2, RES, true>), dim3(g), dim3(pp64::NTP), pp64::LDS, s, a);
+    hipLaunchKernelGGL((pp64::conv_pair_pp64_kernel<NCA, INMODE, X2, RES, true, PROJ>), dim3(g), dim3(pp64::NTP), lds, s, a);
     return BE_CHECK_LAUNCH();
   }
-  hipLaunchKernelGGL((pp64::conv_pair_pp64_kernel<NCA, INMODE, X2, RES>), dim3(g), dim3(pp64::NTP), pp64::LDS, s, a);
+  hipLaunchKernelGGL((pp64::conv_pair_pp64_kernel<NCA, INMODE, X2, RES, false, PROJ>), dim3(g), dim3(pp64::NTP), lds, s, a);
   return BE_CHECK_LAUNCH();
 }
 }  // namespace
@@ -1018,14 +1024,38 @@ static int g_pair_pp64 = [] {
   return e ? atoi(e) : 1;
 }();
 
-static bool pp64_ok(const PairArgs& a, int grid_cap) {
-  if (!g_pair_pp64 || g_pair_stamps != nullptr || !a.waf || !a.wbf) return false;
-  const long long tiles = (long long)a.N * ((a.W + pp64::TS - 1) / pp64::TS) * ((a.H + pp64::TS - 1) / pp64::TS);
+// the size rule by itself: N images of H x W outputs
+static bool pp64_size_ok(int N, int H, int W, int grid_cap) {
+  if (!g_pair_pp64 || g_pair_stamps != nullptr) return false;
+  const long long tiles = (long long)N * ((W + pp64::TS - 1) / pp64::TS) * ((H + pp64::TS - 1) / pp64::TS);
   const int g = grid_cap > 0 ? grid_cap : 256;
   return tiles >= 2LL * g;
 }
 
+static bool pp64_ok(const PairArgs& a, int grid_cap) { return a.waf && a.wbf && pp64_size_ok(a.N, a.H, a.W, grid_cap); }
+
+// BE_PAIR_PP64_PROJ (default 1, A/B; be_conv_pair_set_proj_fusion at run time): the level-1 pool2
+// half-block computes the block's 1x1 projection inside the ping-pong kernel (be_conv_pair_proj)
+// instead of reading it as a residual that a launch of its own wrote
+static int g_pair_pp64_proj = [] {
+  const char* e = getenv("BE_PAIR_PP64_PROJ");
+  return e ? atoi(e) : 1;
+}();
+
 extern "C" {
+
+// 1 if a CM = 64 half-block call with fragment-order weights and N images of H x W outputs runs on
+// the ping-pong kernel now (pp64_ok's rule under BE_PAIR_PP64 and be_conv_pair_set_grid).
+int be_conv_pair_pp64_takes(int N, int H, int W) { return pp64_size_ok(N, H, W, g_pair_grid) ? 1 : 0; }
+
+// 1 if be_conv_pair_proj takes such a call: the same rule and the fusion's own switch.  Callers ask
+// before launching anything; when it says 0 they run the projection and the pair as two launches.
+int be_conv_pair_proj_takes(int N, int H, int W) { return g_pair_pp64_proj && be_conv_pair_pp64_takes(N, H, W); }
+
+int be_conv_pair_set_proj_fusion(int on) {
+  g_pair_pp64_proj = on;
+  return 0;
+}
 
 int be_conv_pair_set_grid(int blocks) {
   g_pair_grid = blocks;
@@ -1073,7 +1103,7 @@ int be_conv_pair_frag(const void* x, const void* x2, const float* sa, const floa
                       int Ws, int Cin, int CM, int inmode, int proj, int resmode, const void* waf, const void* wbf,
                       hipStream_t stream) {
   PairArgs a;
-  a.waf = (const bf16_t*)waf; a.wbf = (const bf16_t*)wbf;
+  a.waf = (const bf16_t*)waf; a.wbf = (const bf16_t*)wbf; a.wpf = nullptr; a.biasp = nullptr;
   a.x = (const bf16_t*)x; a.x2 = (const bf16_t*)x2;
   a.sa = sa; a.ta = ta; a.ta_ns = ta_ns; a.sb = sb; a.tb = tb; a.tb_ns = tb_ns; a.sp = sp; a.tp = tp;
   a.wa = (const bf16_t*)wa; a.wb = (const bf16_t*)wb; a.wp = (const bf16_t*)wp; a.bias = bias;
@@ -1114,6 +1144,31 @@ int be_conv_pair_frag(const void* x, const void* x2, const float* sa, const floa
   return -23;
 }
 
+// The level-1 pool2 half-block (32 -> 64 channels, x at [N, 2H, 2W, 32]) with the block's 1x1
+// projection inside:
+//   out = bf16( convB(h) + bias + float( bf16( convP( bf16(pool(x) * sp + tp) ) + biasp ) ) )
+// i.e. what be_conv2d_nhwc (1x1, pool2) followed by be_conv_pair_frag with that tensor as the full
+// residual computes, bit for bit, in one launch on the ping-pong kernel.  Only that kernel has the
+// build: a call that be_conv_pair_proj_takes does not accept is an error (-25), not a fallback.
+int be_conv_pair_proj(const void* x, const float* sa, const float* ta, int ta_ns, const float* sb, const float* tb,
+                      int tb_ns, const float* sp, const float* tp, const void* wa, const void* wb, const float* bias,
+                      const float* biasp, void* out, int N, int H, int W, int Hs, int Ws, int Cin, int CM,
+                      const void* waf, const void* wbf, const void* wpf, hipStream_t stream) {
+  if (!x || !sa || !ta || !sb || !tb || !wa || !wb || !bias || !out) return -20;
+  if (!sp || !tp || !wpf || !biasp || !waf || !wbf) return -22;
+  if (CM != 64 || Cin != 32 || Hs != 2 * H || Ws != 2 * W) return -23;
+  if (!be_conv_pair_proj_takes(N, H, W)) return -25;
+  PairArgs a;
+  a.waf = (const bf16_t*)waf; a.wbf = (const bf16_t*)wbf; a.wpf = (const bf16_t*)wpf; a.biasp = biasp;
+  a.x = (const bf16_t*)x; a.x2 = nullptr;
+  a.sa = sa; a.ta = ta; a.ta_ns = ta_ns; a.sb = sb; a.tb = tb; a.tb_ns = tb_ns; a.sp = sp; a.tp = tp;
+  a.wa = (const bf16_t*)wa; a.wb = (const bf16_t*)wb; a.wp = nullptr; a.bias = bias;
+  a.res = nullptr; a.out = (bf16_t*)out;
+  a.N = N; a.H = H; a.W = W; a.Hs = Hs; a.Ws = Ws; a.Cin = Cin;
+  a.sh = a.th = a.bh = nullptr; a.wh = nullptr; a.hout = nullptr; a.nh = 0;
+  return launch_pair_pp64<1, 2, false, 0, true>(a, g_pair_grid, stream);
+}
+
 int be_conv_pair(const void* x, const void* x2, const float* sa, const float* ta, int ta_ns, const float* sb,
                  const float* tb, int tb_ns, const float* sp, const float* tp, const void* wa, const void* wb,
                  const void* wp, const float* bias, const void* res, void* out, int N, int H, int W, int Hs, int Ws,
@@ -1134,7 +1189,7 @@ int be_conv_pair_head(const void* x, const float* sa, const float* ta, int ta_ns
   a.x = (const bf16_t*)x; a.x2 = nullptr;
   a.sa = sa; a.ta = ta; a.ta_ns = ta_ns; a.sb = sb; a.tb = tb; a.tb_ns = tb_ns; a.sp = nullptr; a.tp = nullptr;
   a.wa = (const bf16_t*)wa; a.wb = (const bf16_t*)wb; a.wp = nullptr; a.bias = bias;
-  a.res = (const bf16_t*)res; a.out = nullptr; a.waf = a.wbf = nullptr;
+  a.res = (const bf16_t*)res; a.out = nullptr; a.waf = a.wbf = nullptr; a.wpf = nullptr; a.biasp = nullptr;
   a.sh = sh; a.th = th; a.wh = (const bf16_t*)wh; a.bh = bh; a.hout = hout; a.nh = nh;
   a.N = N; a.H = H; a.W = W; a.Hs = H; a.Ws = W; a.Cin = 32;
   if (pp_ok(a, g_pair_grid)) return launch_pair_pp<1, 0, false, 1, true>(a, g_pair_grid, stream);

@@ -49,8 +49,14 @@ constexpr int APT = 11, BPT = 8;            // pixel-tile slots per wave
 constexpr int HU = IPIX * 4, HUPT = (HU + GT - 1) / GT;  // 16-byte halo units per chunk, per thread
 constexpr int WD = 3;                       // weight fragments are fetched WD K-steps ahead
 constexpr int WSTEP = 4 * 64 * 8;           // elements per K-step of the fragment layout (4 ct)
+// PROJ build (pool2 + c0 + c1 with the block's 1x1 projection inside): per group a second image,
+// actP(pool(x)) at the 16 x 16 output pixels, 64-byte pixels, outside the region that h overlays.
+// Written by the commit, read in P3 as stage-B style 16-pixel row fragments; the input image's
+// swizzle c ^ 2 * (((x >> 2) ^ y) & 1) is conflict-free for it too (16 = 0 mod 4, as IW).
+constexpr int P_B = TS * TS * 64;           // 16384
+constexpr int LDS_PROJ = 2 * (RB + P_B);    // 115712; 82944 already means one workgroup per CU
 static_assert(IN_B <= RB && GW * OUTW_B <= RB, "region overlays");
-static_assert(LDS <= 128 * 1024, "LDS budget of the ping-pong kernels");
+static_assert(LDS_PROJ <= 128 * 1024, "LDS budget of the ping-pong kernels");
 
 __device__ __forceinline__ TileXY tile16(const PairArgs& a, int t) {
   const int tpi = a.tiles_x * a.tiles_y;
@@ -109,11 +115,33 @@ __device__ __forceinline__ void issue_halo(const PairArgs& a, TileXY t, int ch, 
 
 // P1: actA -> bf16 -> the swizzled input image (zero outside the image: conv padding applies after
 // the activation).  Chunks 1.. read their affine here (L2-hot), not carried across the MFMA phase.
-template <int INMODE>
+//
+// PROJ: the same (pooled) values through actP (no ReLU) -> bf16 -> the projection's image `preg`, for
+// the 16 x 16 pixels of the output tile; paff is actP's scale / shift of this thread's 8 channels.
+struct PAff {
+  float4 f[4];
+};
+
+__device__ __forceinline__ void issue_paff(const PairArgs& a, int gt, PAff& p) {
+  const int c = (gt & 3) * 8;
+  p.f[0] = *reinterpret_cast<const float4*>(a.sp + c);
+  p.f[1] = *reinterpret_cast<const float4*>(a.sp + c + 4);
+  p.f[2] = *reinterpret_cast<const float4*>(a.tp + c);
+  p.f[3] = *reinterpret_cast<const float4*>(a.tp + c + 4);
+}
+
+// byte offset of 16-byte unit c of pixel (oy, ox) of the projection's 16 x 16 image
+__device__ __forceinline__ int p_off(int oy, int ox, int c) {
+  return (oy * TS + ox) * 64 + ((c ^ ((((ox >> 2) ^ oy) & 1) << 1)) << 4);
+}
+
+template <int INMODE, bool PROJ = false>
 __device__ __forceinline__ void commit(const PairArgs& a, TileXY t, int ch, int gt, bool inner, const Halo<INMODE>& hr,
-                                       unsigned char* rin) {
+                                       unsigned char* rin, const PAff* paff = nullptr, unsigned char* preg = nullptr) {
   const int c = gt & 3, cc = ch * 32 + c * 8;
   float sc[8], sh[8];
+  float ps[8], pt[8];
+  if constexpr (PROJ) unpack_aff(paff->f, ps, pt);
   if (ch == 0) {
     unpack_aff(hr.aff, sc, sh);
   } else {
@@ -132,7 +160,7 @@ __device__ __forceinline__ void commit(const PairArgs& a, TileXY t, int ch, int 
     const int pi = u >> 2;
     const int y = pi / IW, x = pi - y * IW;
     const int gy = t.ty0 - 2 + y, gx = t.tx0 - 2 + x;
-    u32x4 pk = (u32x4){0u, 0u, 0u, 0u};
+    u32x4 pk = (u32x4){0u, 0u, 0u, 0u}, pp = (u32x4){0u, 0u, 0u, 0u};
     if (inner || (gy >= 0 && gy < a.H && gx >= 0 && gx < a.W)) {
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
@@ -142,9 +170,13 @@ __device__ __forceinline__ void commit(const PairArgs& a, TileXY t, int ch, int 
           hi = fmaxf(fmaxf(hi, hi_bf(hr.h[i][1][j])), fmaxf(hi_bf(hr.h[i][2][j]), hi_bf(hr.h[i][3][j])));
         }
         pk[j] = relu_bf16x2(pack2bf(fmaf(lo, sc[2 * j], sh[2 * j]), fmaf(hi, sc[2 * j + 1], sh[2 * j + 1])));
+        if constexpr (PROJ) pp[j] = pack2bf(fmaf(lo, ps[2 * j], pt[2 * j]), fmaf(hi, ps[2 * j + 1], pt[2 * j + 1]));
       }
     }
     *reinterpret_cast<u32x4*>(rin + pi * 64 + ((c ^ ((((x >> 2) ^ y) & 1) << 1)) << 4)) = pk;
+    if constexpr (PROJ) {
+      if (y >= 2 && y < TS + 2 && x >= 2 && x < TS + 2) *reinterpret_cast<u32x4*>(preg + p_off(y - 2, x - 2, c)) = pp;
+    }
   }
 }
 
@@ -315,6 +347,44 @@ __device__ __forceinline__ void issue_res(const PairArgs& a, TileXY t, int cp, i
   for (int ct = 0; ct < 2; ++ct) r.bias[ct] = *reinterpret_cast<const float4*>(a.bias + (2 * cp + ct) * 16 + kq * 4);
 }
 
+// PROJ: the residual is the block's 1x1 projection of the commit's actP image, computed where the
+// other builds fetch theirs: per (ct, output row) ONE 32-deep MFMA from a zero accumulator (lane kq:
+// channels 8 kq .. 8 kq + 7), then (acc + biasP) + 0.0f rounded to bf16 -- conv2d_nhwc_kernel's 1x1
+// at CK = 32 with no residual, operation for operation (the + 0.0f turns a -0.0 sum into +0.0 as its
+// zero residual does), so the packed result is the tensor that kernel would have written and epi_b
+// adds it as any residual.  wp / bp: the wave's two weight fragments and biases, fetched a phase early.
+struct ProjW {
+  bf16x8 w[2];
+  float4 b[2];
+};
+
+__device__ __forceinline__ void issue_projw(const PairArgs& a, int cp, int lane, ProjW& p) {
+#pragma unroll
+  for (int ct = 0; ct < 2; ++ct) {
+    p.w[ct] = *reinterpret_cast<const bf16x8*>(a.wpf + (2 * cp + ct) * 512 + lane * 8);
+    p.b[ct] = *reinterpret_cast<const float4*>(a.biasp + (2 * cp + ct) * 16 + (lane >> 4) * 4);
+  }
+}
+
+__device__ __forceinline__ void proj_res(const PairArgs& a, const unsigned char* preg, const ProjW& p, int cp, int ph,
+                                         int lrow, int kq, Res& r) {
+  const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+  // p_off(8 ph + pt, lrow, kq): 8 ph is even, so the row's parity is pt's
+  const int P0 = ((8 * ph * TS + lrow) * 64 + kq * 16) ^ (((lrow >> 2) & 1) << 5);
+#pragma unroll
+  for (int pt = 0; pt < BPT; ++pt) {
+    const bf16x8 b = *reinterpret_cast<const bf16x8*>(preg + ((P0 + pt * TS * 64) ^ ((pt & 1) << 5)));
+#pragma unroll
+    for (int ct = 0; ct < 2; ++ct) {
+      const f32x4 v = __builtin_amdgcn_mfma_f32_16x16x32_bf16(p.w[ct], b, zero, 0, 0, 0);
+      r.rv[pt][ct][0] = pack2bf(v[0] + p.b[ct].x + 0.0f, v[1] + p.b[ct].y + 0.0f);
+      r.rv[pt][ct][1] = pack2bf(v[2] + p.b[ct].z + 0.0f, v[3] + p.b[ct].w + 0.0f);
+    }
+  }
+#pragma unroll
+  for (int ct = 0; ct < 2; ++ct) r.bias[ct] = *reinterpret_cast<const float4*>(a.bias + (2 * cp + ct) * 16 + kq * 4);
+}
+
 // P5: bias + residual -> wave-private staging (64-byte half pixels, swizzled like the level-0 h)
 // -> 16-byte buffer stores; pixels outside the image and tiles that are not this group's get an
 // out-of-range offset, which the descriptor's range check drops
@@ -353,9 +423,11 @@ __device__ __forceinline__ void epi_b(const PairArgs& a, TileXY t, const f32x4 (
 
 // NCA input chunks of 32 channels (Cin = 32 NCA), INMODE / X2 / RES as above.  The level-1
 // half-blocks: (2, 0, false, 1) c2 + c3 + x1, (1, 2, false, 1) pool2 + c0 + c1 + proj,
-// (4, 1, true, 2) up2 + c0 + c1 + skip + up2(proj).
-template <int NCA, int INMODE, bool X2, int RES, bool STAMP = false>
+// (4, 1, true, 2) up2 + c0 + c1 + skip + up2(proj).  PROJ: (1, 2, false, 0) with the projection computed
+// inside (commit / proj_res) instead of read as a residual.
+template <int NCA, int INMODE, bool X2, int RES, bool STAMP = false, bool PROJ = false>
 __global__ __launch_bounds__(NTP, 2) void conv_pair_pp64_kernel(PairArgs a) {
+  static_assert(PROJ ? (NCA == 1 && RES == 0 && !X2) : RES != 0, "the residual is read or projected");
   constexpr int CIN = 32 * NCA;
   // STAMP (diagnostics, tools/pp_phase_profile.py): as conv_pair_pp_kernel, [grid][2 groups][16];
   // slots: commit / stage A of chunk 0, of the later chunks together, epi A, stage B, epi B
@@ -385,8 +457,11 @@ __global__ __launch_bounds__(NTP, 2) void conv_pair_pp64_kernel(PairArgs a) {
   const int grp = __builtin_amdgcn_readfirstlane(tid0 / GT);  // waves w and w + 4 share a SIMD
   const int gt0 = tid0 & (GT - 1);
   unsigned char* reg = smem + grp * RB;
+  unsigned char* preg = smem + 2 * RB + grp * P_B;  // PROJ builds only
   Halo<INMODE> halo;
+  PAff paff;  // PROJ: rides with chunk 0's halo like its actA affine
   issue_halo<CIN, INMODE>(a, tile16(a, min(t0 + grp, t1 - 1)), 0, gt0, halo);
+  if constexpr (PROJ) issue_paff(a, gt0, paff);
   if (grp == 1) __builtin_amdgcn_s_barrier();  // the stagger: group 1 runs one phase behind
   const int iters = (t1 - t0 + 1) >> 1;
   for (int k = 0; k < iters; ++k) {
@@ -414,12 +489,17 @@ __global__ __launch_bounds__(NTP, 2) void conv_pair_pp64_kernel(PairArgs a) {
       // P1: input chunk c -> activated image; then the first weight fragments of its stage A
       int gc = gt0;
       asm volatile("" : "+v"(gc));
-      commit<INMODE>(a, cur, c, gc, inner, halo, reg);
+      if constexpr (PROJ)
+        commit<INMODE, true>(a, cur, c, gc, inner, halo, reg, &paff, preg);
+      else
+        commit<INMODE>(a, cur, c, gc, inner, halo, reg);
       issue_w(wla + c * 9 * WSTEP, wpre);
       pre(slot(c));
       __syncthreads();
       post(slot(c));
-      // P2: stage A over chunk c, the next chunk's halo in flight
+      // P2: stage A over chunk c, the next chunk's halo in flight.  (Issued at the end of the commit
+      // instead, as conv_pp128.hip does, it gained nothing here: 64 -> 64 unchanged, 128 -> 64 up2
+      // 1-4 % slower per call; profiles/proj/README.md.)
       if (c + 1 < NCA) issue_halo<CIN, INMODE>(a, cur, c + 1, gt, halo);
       if (c == NCA - 1) {
 #pragma unroll
@@ -438,10 +518,17 @@ __global__ __launch_bounds__(NTP, 2) void conv_pair_pp64_kernel(PairArgs a) {
     // P3: epilogue A -> h; this tile's residual and stage B's first weight fragments issued behind it
     int g3 = gt0;
     asm volatile("" : "+v"(g3));
+    ProjW pw;
+    if constexpr (PROJ) issue_projw(a, cp, g3 & 63, pw);  // back from L2 by the end of epi_a
     epi_a<X2>(a, cur, inner, acc_a, reg, sbp, tbp, cp, ph, g3 & 15, (g3 & 63) >> 4);
     Res res;
-    issue_res<RES>(a, cur, cp, ph, g3 & 15, (g3 & 63) >> 4, res);
-    issue_w(wlb, wpre);
+    if constexpr (PROJ) {
+      issue_w(wlb, wpre);
+      proj_res(a, preg, pw, cp, ph, g3 & 15, (g3 & 63) >> 4, res);
+    } else {
+      issue_res<RES>(a, cur, cp, ph, g3 & 15, (g3 & 63) >> 4, res);
+      issue_w(wlb, wpre);
+    }
     pre(4);
     __syncthreads();
     post(4);
@@ -469,6 +556,7 @@ __global__ __launch_bounds__(NTP, 2) void conv_pair_pp64_kernel(PairArgs a) {
     epi_b(a, cur, acc_b, res, reg + gw * OUTW_B, cp, ph, g5 & 15, (g5 & 63) >> 4, act);
     __builtin_amdgcn_sched_barrier(0);
     if constexpr (INMODE == 2) issue_halo<CIN, INMODE>(a, tile16(a, min(t + 2, t1 - 1)), 0, g5, halo);
+    if constexpr (PROJ) issue_paff(a, g5, paff);
     pre(6);
     __syncthreads();
     post(6);

@@ -72,11 +72,12 @@ struct Args {
   const float* ta;     // shift likewise, or null (0)
   const bf16_t* wf;    // fragment-order weights
   const float* bias;   // [128] or null
-  const bf16_t* res;   // [N, H, W, 128] or null; may be `out`
+  const bf16_t* res;   // [N, H, W, 128] (may be `out`), [N, H/2, W/2, 128] (res_up2), or null
   bf16_t* out;         // [N, H, W, 128]
   int N, H, W;
   int sa_ns, ta_ns;
   int relu;
+  int res_up2;         // the residual is at half resolution, read through nearest 2x up-sampling (even H, W)
   int tiles_x, tiles_y;
   // diagnostics (STAMP instantiation only, tools/pp128_phase_profile.py): [grid][2 groups][16] cycle
   // counts of wave 0 of each group
@@ -219,16 +220,21 @@ __device__ __forceinline__ void mma_chunk(f32x4 (&acc)[2][NF], const unsigned ch
 // 56^2), so one per-lane offset serves all 28 accesses and the fragment's offset is scalar; otherwise
 // pixels outside the image get an out-of-range offset, which the descriptor's range check drops, as do
 // tiles that are not this group's.  Every residual is loaded before the first store: `out` may be the
-// residual.
-template <bool RES, bool FULL>
+// residual.  RES 2: the residual is [N, H/2, W/2, 128] and pixel (py, px) reads (py >> 1, px >> 1)
+// through a descriptor of that image's size (a 1x1 projection of an up-sampled map, computed before
+// the up-sampling: a quarter of the bytes).  Tile and patch origins are even (8, 28, 4), so
+// (origin + y) >> 1 = origin / 2 + (y >> 1) and the FULL form keeps its scalar fragment offsets.
+template <int RES, bool FULL>
 __device__ __forceinline__ void epilogue(const Args& a, TileXY t, const f32x4 (&acc)[2][NF], int cp, int lrow, int kq,
                                          bool act) {
   const int ly = lrow >> 2, lx = lrow & 3;
   const int co = cp * 32 + kq * 4;
   const int img_b = a.H * a.W * C * 2;  // host-checked: < 2^31
   const size_t img = (size_t)t.n * a.H * a.W * C;
+  const int Wr = a.W >> 1;
   const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<bf16_t*>(RES ? a.res + img : a.x), (short)0, RES ? img_b : 0, 0x00020000);
+      const_cast<bf16_t*>(RES == 2 ? a.res + (size_t)t.n * (a.H >> 1) * Wr * C : (RES ? a.res + img : a.x)), (short)0,
+      RES == 2 ? (a.H >> 1) * Wr * C * 2 : (RES ? img_b : 0), 0x00020000);
   const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc(a.out + img, (short)0, img_b, 0x00020000);
   const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<float*>(a.bias ? a.bias : a.sa), (short)0, a.bias ? C * 4 : 0, 0x00020000);  // null: loads give 0
@@ -239,17 +245,25 @@ __device__ __forceinline__ void epilogue(const Args& a, TileXY t, const f32x4 (&
     return (py < a.H && px < a.W) ? ((py * a.W + px) * C + co) * 2 : 0x7ffffff0;
   };
   auto soff = [&](int j) { return FULL ? ((j / FC) * 4 * a.W + (j % FC) * 4) * C * 2 : 0; };
+  // the same pair for the half-resolution residual
+  auto voff_r = [&](int j, int y, int x) {
+    if constexpr (FULL) return ((((t.ty0 + y) >> 1) * Wr + ((t.tx0 + x) >> 1)) * C + co) * 2;
+    const int py = t.ty0 + 4 * (j / FC) + y, px = t.tx0 + 4 * (j % FC) + x;
+    return (py < a.H && px < a.W) ? (((py >> 1) * Wr + (px >> 1)) * C + co) * 2 : 0x7ffffff0;
+  };
+  auto soff_r = [&](int j) { return FULL ? ((j / FC) * 2 * Wr + (j % FC) * 2) * C * 2 : 0; };
   u32x2 rv[RES ? NF : 1][2];
   f32x4 bias[2];
 #pragma unroll
   for (int ct = 0; ct < 2; ++ct)
     bias[ct] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rb, (co + ct * 16) * 4, 0, 0));
-  if constexpr (RES) {
+  if constexpr (RES != 0) {
 #pragma unroll
     for (int j = 0; j < NF; ++j) {
-      const int o = voff(j, ly, lx);
+      const int o = RES == 2 ? voff_r(j, ly, lx) : voff(j, ly, lx);
+      const int so = RES == 2 ? soff_r(j) : soff(j);
 #pragma unroll
-      for (int ct = 0; ct < 2; ++ct) rv[j][ct] = __builtin_amdgcn_raw_buffer_load_b64(rr, o + ct * 32, soff(j), 0);
+      for (int ct = 0; ct < 2; ++ct) rv[j][ct] = __builtin_amdgcn_raw_buffer_load_b64(rr, o + ct * 32, so, 0);
     }
   } else {
 #pragma unroll
@@ -264,7 +278,7 @@ __device__ __forceinline__ void epilogue(const Args& a, TileXY t, const f32x4 (&
 #pragma unroll
     for (int ct = 0; ct < 2; ++ct) {
       u32x2 st;
-      if constexpr (RES) {
+      if constexpr (RES != 0) {
         const u32x2 r = rv[j][ct];
         st[0] = pack2bf(acc[ct][j][0] + bias[ct][0] + lo_bf(r[0]), acc[ct][j][1] + bias[ct][1] + hi_bf(r[0]));
         st[1] = pack2bf(acc[ct][j][2] + bias[ct][2] + lo_bf(r[1]), acc[ct][j][3] + bias[ct][3] + hi_bf(r[1]));
@@ -364,16 +378,21 @@ __global__ __launch_bounds__(NTP, 2) void conv_pp128_kernel(Args a) {
     int g3 = gt0;
     asm volatile("" : "+v"(g3));
     const bool full = cur.ty0 + TH <= a.H && cur.tx0 + TW <= a.W;  // workgroup-uniform, as a.res is
-    if (a.res != nullptr) {
+    if (a.res != nullptr && a.res_up2) {
       if (full)
-        epilogue<true, true>(a, cur, acc, cp, g3 & 15, (g3 & 63) >> 4, act);
+        epilogue<2, true>(a, cur, acc, cp, g3 & 15, (g3 & 63) >> 4, act);
       else
-        epilogue<true, false>(a, cur, acc, cp, g3 & 15, (g3 & 63) >> 4, act);
+        epilogue<2, false>(a, cur, acc, cp, g3 & 15, (g3 & 63) >> 4, act);
+    } else if (a.res != nullptr) {
+      if (full)
+        epilogue<1, true>(a, cur, acc, cp, g3 & 15, (g3 & 63) >> 4, act);
+      else
+        epilogue<1, false>(a, cur, acc, cp, g3 & 15, (g3 & 63) >> 4, act);
     } else {
       if (full)
-        epilogue<false, true>(a, cur, acc, cp, g3 & 15, (g3 & 63) >> 4, act);
+        epilogue<0, true>(a, cur, acc, cp, g3 & 15, (g3 & 63) >> 4, act);
       else
-        epilogue<false, false>(a, cur, acc, cp, g3 & 15, (g3 & 63) >> 4, act);
+        epilogue<0, false>(a, cur, acc, cp, g3 & 15, (g3 & 63) >> 4, act);
     }
     pre(4);
     __syncthreads();
@@ -402,10 +421,32 @@ int g_pp128 = [] {
   return e ? atoi(e) : 1;
 }();
 
+// BE_CONV_PP128_RES_UP2 (default 1, A/B): 0 makes be_conv_pp128_takes_res_up2 answer 0, so callers
+// keep a full-resolution residual
+int g_pp128_res_up2 = [] {
+  const char* e = getenv("BE_CONV_PP128_RES_UP2");
+  return e ? atoi(e) : 1;
+}();
+
 int g_pp128_grid = 0;      // be_conv_pp128_set_grid (0 = one workgroup per CU)
 int g_pp128_launches = 0;  // be_conv_pp128_launches
 unsigned long long* g_pp128_stamps = nullptr;  // diagnostics: be_conv_pp128_set_stamps
 int g_pp128_stamps_cap = 0;                    // workgroups the stamp buffer holds
+
+// The size rule, in one place: the grid on which a 3x3 128 -> 128 call of N images of H x W runs on
+// conv_pp128_kernel, or 0 when it stays on the per-layer kernel (switched off, too few tiles for the
+// grid that is not forced, or too large for 32-bit offsets).
+int pp128_grid_for(int N, int H, int W, int* tiles_x, int* tiles_y) {
+  if (!g_pp128 || N <= 0 || H <= 0 || W <= 0 || (long long)H * W * 256 >= (1LL << 31) - 64) return 0;
+  const int tx = (W + pp128::TW - 1) / pp128::TW, ty = (H + pp128::TH - 1) / pp128::TH;
+  const long long tiles = (long long)N * tx * ty;
+  const bool forced = g_pp128_grid > 0;
+  const int g = forced ? (int)(tiles < g_pp128_grid ? tiles : g_pp128_grid) : 256;
+  if (!(forced || tiles >= 2LL * g) || tiles >= (1LL << 30)) return 0;
+  if (tiles_x) *tiles_x = tx;
+  if (tiles_y) *tiles_y = ty;
+  return g;
+}
 
 }  // namespace
 
@@ -442,25 +483,26 @@ int be_conv_pp128_launches() { return g_pp128_launches; }
 // activation runs on conv_pp128_kernel when every group of every workgroup gets at least two 8 x 28
 // tiles (as pp64_ok: batch-1 latency calls would only recompute dummy tiles) or the grid is forced
 // (be_conv_pp128_set_grid); every other call goes to be_conv2d_nhwc unchanged.
-int be_conv2d_nhwc_frag(const void* x, const void* x2, const float* pscale, const float* pshift, int pshift_ns,
-                        int pscale_ns, int prelu, const void* w, const float* bias, const void* res, void* out, int N,
-                        int H, int W, int Hs, int Ws, int Cin, int Cout, int cout_valid, int ks, int ck, int tco,
-                        int inmode, int out_f32_nchw, int nw, const float* qscale, const float* qshift, int qshift_ns,
-                        const void* wfrag, hipStream_t stream) {
-  const bool shape_ok = wfrag && g_pp128 && ks == 3 && ck == 32 && inmode == 0 && !x2 && !out_f32_nchw && Cin == 128 &&
-                        Cout == 128 && Hs == H && Ws == W && !(prelu & 2) && !qscale && !qshift && x && out && N > 0 &&
-                        H > 0 && W > 0 && (long long)H * W * 256 < (1LL << 31) - 64;
+//
+// res_up2 != 0: `res` is [N, H/2, W/2, 128] and is read through nearest 2x up-sampling.  Only the
+// ping-pong kernel has that epilogue: the caller asks be_conv_pp128_takes_res_up2 first, and a call
+// that the kernel does not take is an error (-31), not a fallback.
+int be_conv2d_nhwc_frag_res(const void* x, const void* x2, const float* pscale, const float* pshift, int pshift_ns,
+                            int pscale_ns, int prelu, const void* w, const float* bias, const void* res, void* out,
+                            int N, int H, int W, int Hs, int Ws, int Cin, int Cout, int cout_valid, int ks, int ck,
+                            int tco, int inmode, int out_f32_nchw, int nw, const float* qscale, const float* qshift,
+                            int qshift_ns, const void* wfrag, int res_up2, hipStream_t stream) {
+  const bool shape_ok = wfrag && ks == 3 && ck == 32 && inmode == 0 && !x2 && !out_f32_nchw && Cin == 128 &&
+                        Cout == 128 && Hs == H && Ws == W && !(prelu & 2) && !qscale && !qshift && x && out;
+  if (res_up2 && !(shape_ok && res && H % 2 == 0 && W % 2 == 0)) return -31;
   if (shape_ok) {
     pp128::Args a;
-    a.tiles_x = (W + pp128::TW - 1) / pp128::TW;
-    a.tiles_y = (H + pp128::TH - 1) / pp128::TH;
-    const long long tiles = (long long)N * a.tiles_x * a.tiles_y;
-    const bool forced = g_pp128_grid > 0;
-    const int g = forced ? (int)(tiles < g_pp128_grid ? tiles : g_pp128_grid) : 256;
-    if ((forced || tiles >= 2LL * g) && tiles < (1LL << 30)) {
+    const int g = pp128_grid_for(N, H, W, &a.tiles_x, &a.tiles_y);
+    if (g > 0) {
       a.x = (const bf16_t*)x; a.sa = pscale; a.ta = pshift; a.sa_ns = pscale_ns; a.ta_ns = pshift_ns;
       a.wf = (const bf16_t*)wfrag; a.bias = bias; a.res = (const bf16_t*)res; a.out = (bf16_t*)out;
       a.N = N; a.H = H; a.W = W; a.relu = prelu & 1;
+      a.res_up2 = res_up2 ? 1 : 0;
       a.stamps = g_pp128_stamps;
       ++g_pp128_launches;
       if (g_pp128_stamps != nullptr) {
@@ -472,8 +514,29 @@ int be_conv2d_nhwc_frag(const void* x, const void* x2, const float* pscale, cons
       return BE_CHECK_LAUNCH();
     }
   }
+  if (res_up2) return -31;
   return be_conv2d_nhwc(x, x2, pscale, pshift, pshift_ns, pscale_ns, prelu, w, bias, res, out, N, H, W, Hs, Ws, Cin, Cout,
                         cout_valid, ks, ck, tco, inmode, out_f32_nchw, nw, qscale, qshift, qshift_ns, stream);
+}
+
+int be_conv2d_nhwc_frag(const void* x, const void* x2, const float* pscale, const float* pshift, int pshift_ns,
+                        int pscale_ns, int prelu, const void* w, const float* bias, const void* res, void* out, int N,
+                        int H, int W, int Hs, int Ws, int Cin, int Cout, int cout_valid, int ks, int ck, int tco,
+                        int inmode, int out_f32_nchw, int nw, const float* qscale, const float* qshift, int qshift_ns,
+                        const void* wfrag, hipStream_t stream) {
+  return be_conv2d_nhwc_frag_res(x, x2, pscale, pshift, pshift_ns, pscale_ns, prelu, w, bias, res, out, N, H, W, Hs, Ws,
+                                 Cin, Cout, cout_valid, ks, ck, tco, inmode, out_f32_nchw, nw, qscale, qshift,
+                                 qshift_ns, wfrag, 0, stream);
+}
+
+// 1 if a be_conv2d_nhwc_frag call of the kernel's shape (3x3, 128 -> 128, fragment-order weights, no
+// input transform, bf16 NHWC output) with N images of H x W runs on conv_pp128_kernel now: the size
+// rule above under the present BE_CONV_PP128 and be_conv_pp128_set_grid.
+int be_conv_pp128_takes(int N, int H, int W) { return pp128_grid_for(N, H, W, nullptr, nullptr) > 0 ? 1 : 0; }
+
+// 1 if such a call may also hand its residual over at half resolution (be_conv2d_nhwc_frag_res).
+int be_conv_pp128_takes_res_up2(int N, int H, int W) {
+  return g_pp128_res_up2 && H % 2 == 0 && W % 2 == 0 && be_conv_pp128_takes(N, H, W);
 }
 
 }  // extern "C"

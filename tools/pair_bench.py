@@ -73,7 +73,7 @@ def main():
     N = args.tiles
     P = eng_pair.pair
     shp = {("down", 0, 0): (224, 8, None, None), ("down", 0, 1): (224, 32, None, "full"),
-           ("down", 1, 0): (224, 32, None, "full"), ("down", 1, 1): (112, 64, None, "full"),
+           ("down", 1, 0): (224, 32, None, None), ("down", 1, 1): (112, 64, None, "full"),
            ("up", 1, 0): (56, 128, True, "up2"), ("up", 1, 1): (112, 64, None, "full"),
            ("up", 0, 0): (112, 64, True, "up2"), ("up", 0, 1): (224, 32, None, "full")}
     for key, (hs, cin, hx2, res) in shp.items():
