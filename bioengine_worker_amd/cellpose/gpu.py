@@ -31,6 +31,30 @@ def _launch_cfg(n: int):
 
 _pct_ws: dict = {}
 
+#: element type codes of ``be_tiles_gather_norm`` (csrc/kernels/percentile.h)
+RAW_DTYPES = {torch.float32: 0, torch.uint16: 1, torch.uint8: 2}
+
+#: ``BE_CELLPOSE_FUSED_FRONT=0`` (A/B): convert to fp32, normalise into an fp32 image and gather
+#: that, instead of the percentile select on the raw pixels + normalising gather
+FUSED_FRONT = os.environ.get("BE_CELLPOSE_FUSED_FRONT", "1") != "0"
+
+
+def _pct_workspace(device, sptr, rows: int) -> torch.Tensor:
+    """The percentile kernels' workspace for ``rows`` rows on stream ``sptr``."""
+    key = (device, getattr(sptr, "value", sptr))  # one workspace per stream: concurrent streams never share histograms
+    ws = _pct_ws.get(key)
+    need = rows * 6 * 258 * 4
+    if ws is None or ws.numel() < need:  # hist part must start zeroed; every call leaves it zeroed
+        ws = _pct_ws[key] = torch.zeros(max(need, 64 * 6 * 258 * 4), dtype=torch.uint8, device=device)
+    return ws
+
+
+def takes_fused_front(x) -> bool:
+    """Whether ``x`` can go to :meth:`TilePlan.gather_normalized` as it is: a contiguous
+    [B, C, H, W] device tensor of uint8, uint16 or float32."""
+    return (FUSED_FRONT and torch.is_tensor(x) and x.is_cuda and x.dim() == 4 and x.dtype in RAW_DTYPES
+            and x.is_contiguous())
+
 
 def normalize99(x: torch.Tensor, lower: float = 1.0, upper: float = 99.0) -> torch.Tensor:
     """x [B, C, H, W] -> float32 normalised per (image, channel) with np.percentile 'linear' semantics.
@@ -44,11 +68,7 @@ def normalize99(x: torch.Tensor, lower: float = 1.0, upper: float = 99.0) -> tor
     xf = x.float().contiguous()
     rows = B * C
     sptr = _native.stream(x.device)
-    key = (x.device, getattr(sptr, "value", sptr))  # one workspace per stream: concurrent streams never share histograms
-    ws = _pct_ws.get(key)
-    need = rows * 6 * 258 * 4
-    if ws is None or ws.numel() < need:  # hist part must start zeroed; every call leaves it zeroed
-        ws = _pct_ws[key] = torch.zeros(max(need, 64 * 6 * 258 * 4), dtype=torch.uint8, device=x.device)
+    ws = _pct_workspace(x.device, sptr, rows)
     out = torch.empty_like(xf)
     _native.call("be_pct_normalize", _native.ptr(xf), rows, H * W, float(lower), float(upper), _native.ptr(out),
                  _native.ptr(ws), ws.numel() // 4 * 4, sptr)
@@ -110,6 +130,23 @@ class TilePlan:
         _native.call("be_tiles_gather", _native.ptr(img), B, C, H, W, self.pad_y, self.pad_x, _native.ptr(self.ys_t),
                      _native.ptr(self.xs_t), len(self.ys), len(self.xs), self.by, self.bx, cpad, _native.ptr(out),
                      _native.stream(img.device))
+        return out
+
+    def gather_normalized(self, x_raw: torch.Tensor, cpad: int, c_use: int | None = None, lower: float = 1.0,
+                          upper: float = 99.0) -> torch.Tensor:
+        """``gather(normalize99(x_raw[:, :c_use].float(), lower, upper), cpad)`` bit for bit, from
+        the raw pixels in one native call: ``x_raw`` is a contiguous [B, C, H, W] uint8, uint16 or
+        float32 device tensor (:func:`takes_fused_front`); channels from ``c_use`` on are ignored."""
+        B, C, H, W = x_raw.shape
+        if x_raw.dtype not in RAW_DTYPES or not x_raw.is_contiguous():
+            raise ValueError(f"gather_normalized takes a contiguous uint8, uint16 or float32 tensor, got {x_raw.dtype}")
+        c_use = C if c_use is None else min(int(c_use), C)
+        out = torch.empty(B * self.nt, self.by, self.bx, cpad, dtype=torch.bfloat16, device=x_raw.device)
+        sptr = _native.stream(x_raw.device)
+        ws = _pct_workspace(x_raw.device, sptr, B * c_use)
+        _native.call("be_tiles_gather_norm", _native.ptr(x_raw), RAW_DTYPES[x_raw.dtype], B, C, c_use, H, W, float(lower),
+                     float(upper), self.pad_y, self.pad_x, _native.ptr(self.ys_t), _native.ptr(self.xs_t), len(self.ys),
+                     len(self.xs), self.by, self.bx, cpad, _native.ptr(out), _native.ptr(ws), ws.numel() // 4 * 4, sptr)
         return out
 
     def blend(self, yt: torch.Tensor, B: int) -> torch.Tensor:

@@ -58,9 +58,15 @@ class EvalParams:
     anisotropy: float | None = None
 
 
-def as_batch(images, nchan: int, device=None) -> torch.Tensor:
+def as_batch(images, nchan: int, device=None, keep_raw: bool = False):
     """Accept [H,W], [H,W,C], [C,H,W], [B,C,H,W] numpy/torch -> float tensor [B, nchan, H, W] on
-    ``device`` (copied in the input's own dtype, e.g. uint16, and converted there)."""
+    ``device`` (copied in the input's own dtype, e.g. uint16, and converted there).
+
+    ``keep_raw``: return ``(x, raw)`` instead.  An input the fused front end reads as it is
+    (:func:`gpu.takes_fused_front`: a contiguous [B, C >= nchan, H, W] uint8 / uint16 / float32
+    device tensor) comes back unconverted, in its own dtype and with all its channels, and ``raw``
+    is True; :meth:`CellposeRunner._front` decides what becomes of it.  Every other input is
+    converted as without the flag and ``raw`` is False."""
     x = torch.as_tensor(np.asarray(images) if not torch.is_tensor(images) else images)
     if device is not None:
         x = x.to(device)
@@ -71,13 +77,18 @@ def as_batch(images, nchan: int, device=None) -> torch.Tensor:
         if x.shape[-1] <= 4 and x.shape[0] > 4:
             x = x.permute(2, 0, 1)
         x = x[None]
+    if keep_raw and x.dim() == 4 and x.shape[1] >= nchan:
+        from .gpu import takes_fused_front
+
+        if takes_fused_front(x):
+            return x, True
     x = x.float()
     B, C, H, W = x.shape
     if C < nchan:
         x = torch.cat([x, torch.zeros(B, nchan - C, H, W, dtype=x.dtype, device=x.device)], 1)
     elif C > nchan:
         x = x[:, :nchan]
-    return x
+    return (x, False) if keep_raw else x
 
 
 class CellposeRunner:
@@ -165,14 +176,19 @@ class CellposeRunner:
         return y[:, :, :by, :bx].contiguous()
 
     @torch.no_grad()
-    def run_net(self, x: torch.Tensor, p: EvalParams) -> tuple[torch.Tensor, torch.Tensor]:
-        """x: normalised [B, nchan, H, W] on device -> (y [B, 3, H, W] fp32, style [B, S])."""
+    def run_net(self, x: torch.Tensor, p: EvalParams, raw: bool = False) -> tuple[torch.Tensor, torch.Tensor]:
+        """x: normalised [B, nchan, H, W] on device -> (y [B, 3, H, W] fp32, style [B, S]).
+
+        ``raw`` (tiled GPU path only): ``x`` is the un-normalised batch in the form :meth:`_front`
+        passes on, and the tile gather normalises it (1st / 99th percentile) as it reads."""
         B, C, H, W = x.shape
+        if raw and not (self.device.type == "cuda" and p.tile):
+            raise ValueError("run_net(raw=True) needs the tiled GPU path")
         if self.device.type == "cuda":
             if p.tile:
                 plan = self._plan(H, W, p)
                 with trace.span("cellpose.tiles_gather", cuda=True, tiles=B * plan.nt):
-                    tiles = plan.gather(x, self.cin_pad)
+                    tiles = plan.gather_normalized(x, self.cin_pad, self.nchan) if raw else plan.gather(x, self.cin_pad)
                 with trace.span("cellpose.net", cuda=True, tiles=B * plan.nt):
                     if self.is_sam:
                         yt = self._sam_tiles(tiles)
@@ -228,12 +244,12 @@ class CellposeRunner:
         p = p or EvalParams()
         for k, v in kw.items():
             setattr(p, k, v)
-        x = as_batch(self._stage(images), self.nchan, self.device)
+        x, raw = as_batch(self._stage(images), self.nchan, self.device, keep_raw=True)
         B, C, H, W = x.shape
         nch = min(p.pipeline_chunks, B // max(1, p.pipeline_min_chunk))
         if self.device.type == "cuda" and p.compute_masks and nch >= 2:
-            return self._eval_pipelined(x, p, nch)
-        return self._eval_one(x, p)
+            return self._eval_pipelined(x, p, nch, raw)
+        return self._eval_one(x, p, raw)
 
     @torch.no_grad()
     def eval_stack(self, stack, p: EvalParams | None = None, **kw):
@@ -443,7 +459,25 @@ class CellposeRunner:
         g.replay()
         return y.clone(), style.clone()
 
-    def _eval_one(self, x, p: EvalParams):
+    def _front(self, x, p: EvalParams, raw: bool):
+        """Decide the front end of one network stage for a batch that :func:`as_batch` kept ``raw``
+        (own dtype, all channels).  Returns ``(x, raw)``: still raw, ``x`` goes to ``run_net(...,
+        raw=True)``, whose gather takes the percentiles on the raw pixels and normalises as it reads
+        (:meth:`gpu.TilePlan.gather_normalized`).  That needs the tiled GPU path with normalisation
+        on, no diameter rescale (the resize reads the normalised image) and no HIP-graph replay;
+        otherwise ``x`` comes back as float32 [B, nchan, H, W] for the unfused sequence."""
+        if not raw:
+            return x, False
+        from .gpu import takes_fused_front
+
+        rescaled = p.diameter is not None and p.diameter > 0 and abs(self.diam_mean / float(p.diameter) - 1.0) > 1e-3
+        if (self.device.type == "cuda" and p.normalize and p.tile and not rescaled and x.shape[0] > self.GRAPH_NET_MAX_B
+                and takes_fused_front(x)):
+            return x, True
+        return x.float()[:, : self.nchan], False
+
+    def _eval_one(self, x, p: EvalParams, raw: bool = False):
+        x, raw = self._front(x, p, raw)
         B, C, H, W = x.shape
         if not (p.diameter is not None and p.diameter > 0 and abs(self.diam_mean / float(p.diameter) - 1.0) > 1e-3):
             r = self._net_graphed(x, p)
@@ -454,7 +488,7 @@ class CellposeRunner:
                 with trace.span("cellpose.masks", cuda=True, images=B):
                     masks = self.compute_masks(y, p, 1.0)
                 return masks, y, style
-        if p.normalize:
+        if p.normalize and not raw:
             with trace.span("cellpose.normalize99", cuda=True, images=B):
                 x = self._normalize(x)
         rescale = 1.0
@@ -466,20 +500,21 @@ class CellposeRunner:
             y, style = self.run_net(xs, p)
             y = resize_bilinear(y, (H, W))
         else:
-            y, style = self.run_net(x, p)
+            y, style = self.run_net(x, p, raw=True) if raw else self.run_net(x, p)
         if not p.compute_masks:
             return None, y, style
         with trace.span("cellpose.masks", cuda=True, images=B):
             masks = self.compute_masks(y, p, rescale)
         return masks, y, style
 
-    def _net_stage(self, x, p: EvalParams):
+    def _net_stage(self, x, p: EvalParams, raw: bool = False):
+        x, raw = self._front(x, p, raw)
         B, C, H, W = x.shape
         if not (p.diameter is not None and p.diameter > 0 and abs(self.diam_mean / float(p.diameter) - 1.0) > 1e-3):
             r = self._net_graphed(x, p)
             if r is not None:
                 return r[0], r[1], 1.0
-        if p.normalize:
+        if p.normalize and not raw:
             with trace.span("cellpose.normalize99", cuda=True, images=B):
                 x = self._normalize(x)
         rescale = 1.0
@@ -491,10 +526,10 @@ class CellposeRunner:
             y, style = self.run_net(xs, p)
             y = resize_bilinear(y, (H, W))
         else:
-            y, style = self.run_net(x, p)
+            y, style = self.run_net(x, p, raw=True) if raw else self.run_net(x, p)
         return y, style, rescale
 
-    def _eval_pipelined(self, x, p: EvalParams, nch: int):
+    def _eval_pipelined(self, x, p: EvalParams, nch: int, raw: bool = False):
         """Two-stream software pipeline over micro-batches: net(i+1) on the current stream is queued
         before mask recovery of micro-batch i (which syncs the host on its own stream) starts."""
         main = torch.cuda.current_stream(self.device)
@@ -515,7 +550,7 @@ class CellposeRunner:
             masks.append(m)
 
         for part in parts:
-            y, style, rescale = self._net_stage(part, p)
+            y, style, rescale = self._net_stage(part, p, raw)
             ys.append(y)
             styles.append(style)
             ev = torch.cuda.Event()
@@ -551,8 +586,8 @@ class CellposeRunner:
                 return m, y, st, ev
         with net_lock:
             # no shared pinned staging buffer here: the previous batch's H2D may still be reading it
-            x = as_batch(images, self.nchan, self.device)
-            y, style, rescale = self._net_stage(x, p)
+            x, raw = as_batch(images, self.nchan, self.device, keep_raw=True)
+            y, style, rescale = self._net_stage(x, p, raw)
             main = torch.cuda.current_stream(self.device)
             ev = torch.cuda.Event()
             ev.record(main)
@@ -786,8 +821,8 @@ class _EvalStream:
     def submit(self, images):
         if not self.cuda:
             return self.r.eval(images, self.p)
-        x = as_batch(images, self.r.nchan, self.r.device)  # device tensors only: no shared pinned staging
-        y, style, rescale = self.r._net_stage(x, self.p)
+        x, raw = as_batch(images, self.r.nchan, self.r.device, keep_raw=True)  # device tensors only: no shared pinned staging
+        y, style, rescale = self.r._net_stage(x, self.p, raw)
         ev = torch.cuda.Event()
         ev.record(torch.cuda.current_stream(self.r.device))
         prev, self.pending = self.pending, (y, style, rescale, ev)

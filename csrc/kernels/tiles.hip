@@ -9,38 +9,98 @@
 //   taper mask wy[ty] * wx[tx] (cellpose _taper_mask), normalised by the summed weights.  Output-
 //   centric gather (each output pixel walks only the tiles that cover it), so there are no atomics
 //   and the result is bit-deterministic.
-#include "common.h"
+// be_tiles_gather_norm: the same gather straight from the RAW image (float32, uint16 or uint8) with
+//   the percentile normalisation of percentile.hip applied in the load: the select passes run on the
+//   raw pixels, then each pixel is read once, normalised with its row's constants and stored as
+//   bf16 -- neither an fp32 copy of the input nor a normalised fp32 image ever exists.
+#include "percentile.h"
 
 namespace {
 
-__global__ __launch_bounds__(256) void tiles_gather_kernel(const float* __restrict__ img, int B, int C, int H, int W,
-                                                           int pad_y, int pad_x, const int* __restrict__ ys,
+#ifndef TILES_GATHER_ROWS
+#define TILES_GATHER_ROWS 4
+#endif
+constexpr int kRows = TILES_GATHER_ROWS;  // tile rows per block: independent loads in flight per lane
+constexpr int kMaxGridYZ = 65535;
+
+// One kernel for both gathers.  Grid (x-blocks, row groups, tiles): the tile, its image b and its
+// ys / xs entries are per block, so the only division left is the split of a lane's index into
+// (pixel, 8-channel group), by a small 32-bit number.  A lane owns one pixel's 8-channel group
+// (one 16-byte store) in kRows consecutive tile rows; consecutive lanes take consecutive groups of
+// consecutive pixels, so the loads from an image row and the stores are contiguous.
+// NORM: img holds raw pixels and row b * C_use + c of `state` that row's selected keys
+// (percentile.h); channels >= C_use of a wider image (C_src) are ignored.
+template <typename T, bool NORM>
+__global__ __launch_bounds__(256) void tiles_gather_kernel(const T* __restrict__ img, int tile0, int C_src, int C_use, int H,
+                                                           int W, int pad_y, int pad_x, const int* __restrict__ ys,
                                                            const int* __restrict__ xs, int nty, int ntx, int by, int bx,
-                                                           int cpad, bf16_t* __restrict__ out) {
-  const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  const long long npix = (long long)B * nty * ntx * by * bx;
-  if (gid >= npix) return;
-  const int tx = (int)(gid % bx);
-  long long r = gid / bx;
-  const int ty = (int)(r % by);
-  r /= by;
-  const int t = (int)(r % (nty * ntx));
-  const int b = (int)(r / (nty * ntx));
-  const int yy = ys[t / ntx] + ty - pad_y;
-  const int xx = xs[t % ntx] + tx - pad_x;
-  const bool in = (yy >= 0 && yy < H && xx >= 0 && xx < W);
-  bf16_t* o = out + gid * cpad;
-  for (int c0 = 0; c0 < cpad; c0 += 8) {
-    u32x4 v = (u32x4){0u, 0u, 0u, 0u};
+                                                           int cpad, const be_pct::Coef cf,
+                                                           const uint32_t* __restrict__ state, bf16_t* __restrict__ out) {
+  const int ngrp = cpad >> 3;
+  const int q = blockIdx.x * 256 + threadIdx.x;
+  const int tx = ngrp == 1 ? q : q / ngrp;
+  const int g = ngrp == 1 ? 0 : q - tx * ngrp;
+  if (tx >= bx) return;
+  const int tile = tile0 + blockIdx.z;
+  const int nt = nty * ntx;
+  const int b = tile / nt, t = tile - b * nt;
+  const int ti = t / ntx;
+  const int ty0 = blockIdx.y * kRows;
+  const int yy0 = ys[ti] + ty0 - pad_y;
+  const int xx = xs[t - ti * ntx] + tx - pad_x;
+  const bool inx = xx >= 0 && xx < W;
+  float f[kRows][8];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int ca = c0 + 2 * j, cb = ca + 1;
-      const float fa = (in && ca < C) ? img[(((size_t)b * C + ca) * H + yy) * W + xx] : 0.f;
-      const float fb = (in && cb < C) ? img[(((size_t)b * C + cb) * H + yy) * W + xx] : 0.f;
-      v[j] = pack2bf(fa, fb);
+  for (int r = 0; r < kRows; ++r)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) f[r][j] = 0.f;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const int c = 8 * g + j;
+    if (c < C_use) {
+      float p1 = 0.f, scale = 1.f;
+      bool cst = false;
+      if (NORM) be_pct::row_consts<T>(state + ((size_t)b * C_use + c) * be_pct::kT * 2, cf, p1, scale, cst);
+      const T* plane = img + ((size_t)b * C_src + c) * H * W;
+#pragma unroll
+      for (int r = 0; r < kRows; ++r) {
+        const int yy = yy0 + r;
+        if (inx && yy >= 0 && yy < H && ty0 + r < by) {
+          const float v = (float)plane[(size_t)yy * W + xx];
+          f[r][j] = NORM ? (cst ? 0.f : (v - p1) * scale) : v;
+        }
+      }
     }
-    *reinterpret_cast<u32x4*>(o + c0) = v;
   }
+#pragma unroll
+  for (int r = 0; r < kRows; ++r) {
+    if (ty0 + r < by) {
+      u32x4 v;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) v[j] = pack2bf(f[r][2 * j], f[r][2 * j + 1]);
+      *reinterpret_cast<u32x4*>(out + (((size_t)tile * by + ty0 + r) * bx + tx) * cpad + 8 * g) = v;
+    }
+  }
+}
+
+template <typename T, bool NORM>
+int gather_launch(const void* img, int B, int C_src, int C_use, int H, int W, int pad_y, int pad_x, const int* ys,
+                  const int* xs, int nty, int ntx, int by, int bx, int cpad, be_pct::Coef cf, const uint32_t* state,
+                  void* out, hipStream_t s) {
+  const long long tiles = (long long)B * nty * ntx;
+  const unsigned gx = (unsigned)(((long long)bx * (cpad >> 3) + 255) / 256), gy = (unsigned)((by + kRows - 1) / kRows);
+  for (long long t0 = 0; t0 < tiles; t0 += kMaxGridYZ) {  // one launch unless a call has more tiles than grid.z holds
+    const unsigned gz = (unsigned)(tiles - t0 < kMaxGridYZ ? tiles - t0 : kMaxGridYZ);
+    hipLaunchKernelGGL((tiles_gather_kernel<T, NORM>), dim3(gx, gy, gz), dim3(256), 0, s, static_cast<const T*>(img), (int)t0,
+                       C_src, C_use, H, W, pad_y, pad_x, ys, xs, nty, ntx, by, bx, cpad, cf, state, (bf16_t*)out);
+  }
+  return BE_CHECK_LAUNCH();
+}
+
+bool gather_args_ok(int B, int C, int H, int W, int nty, int ntx, int by, int bx, int cpad) {
+  return B > 0 && C > 0 && H > 0 && W > 0 && nty > 0 && ntx > 0 && by > 0 && bx > 0 && cpad > 0 && cpad % 8 == 0 &&
+         (by + kRows - 1) / kRows <= kMaxGridYZ && (long long)B * nty * ntx <= 0x7fffffffLL &&
+         (long long)bx * (cpad >> 3) <= 0x7fffffffLL - 256;
 }
 
 __global__ __launch_bounds__(256) void tiles_blend_kernel(const float* __restrict__ yt, int B, int nout, int H, int W,
@@ -79,11 +139,29 @@ extern "C" {
 
 int be_tiles_gather(const float* img, int B, int C, int H, int W, int pad_y, int pad_x, const int* ys, const int* xs,
                     int nty, int ntx, int by, int bx, int cpad, void* out, hipStream_t s) {
-  if (cpad % 8) return -1;
-  const long long n = (long long)B * nty * ntx * by * bx;
-  hipLaunchKernelGGL(tiles_gather_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, img, B, C, H, W, pad_y, pad_x, ys,
-                     xs, nty, ntx, by, bx, cpad, (bf16_t*)out);
-  return BE_CHECK_LAUNCH();
+  if (!gather_args_ok(B, C, H, W, nty, ntx, by, bx, cpad)) return -1;
+  return gather_launch<float, false>(img, B, C, C, H, W, pad_y, pad_x, ys, xs, nty, ntx, by, bx, cpad, be_pct::Coef{},
+                                     nullptr, out, s);
+}
+
+// x: raw image [B, C_src, H, W] of element type `dtype` (0 float32, 1 uint16, 2 uint8).  The first
+// C_use channels are normalised per (image, channel) between the `lower` / `upper` percentiles
+// (exactly be_pct_normalize on the pixels converted to fp32) and gathered like be_tiles_gather;
+// channels >= C_use of `out` are zero.  ws: a be_pct_workspace_bytes(B * C_use) workspace, same
+// rules as be_pct_normalize.  Non-zero return: nothing was launched.
+int be_tiles_gather_norm(const void* x, int dtype, int B, int C_src, int C_use, int H, int W, float lower, float upper,
+                         int pad_y, int pad_x, const int* ys, const int* xs, int nty, int ntx, int by, int bx, int cpad,
+                         void* out, void* ws, long long ws_bytes, hipStream_t s) {
+  if (!gather_args_ok(B, C_src, H, W, nty, ntx, by, bx, cpad)) return -1;
+  be_pct::Coef cf;
+  const uint32_t* state;
+  const int rc = be_pct::select_run(x, dtype, B, C_src, C_use, (long long)H * W, lower, upper, ws, ws_bytes, s, &cf, &state);
+  if (rc) return rc;
+  if (dtype == be_pct::kF32)
+    return gather_launch<float, true>(x, B, C_src, C_use, H, W, pad_y, pad_x, ys, xs, nty, ntx, by, bx, cpad, cf, state, out, s);
+  if (dtype == be_pct::kU16)
+    return gather_launch<uint16_t, true>(x, B, C_src, C_use, H, W, pad_y, pad_x, ys, xs, nty, ntx, by, bx, cpad, cf, state, out, s);
+  return gather_launch<uint8_t, true>(x, B, C_src, C_use, H, W, pad_y, pad_x, ys, xs, nty, ntx, by, bx, cpad, cf, state, out, s);
 }
 
 int be_tiles_blend(const float* yt, int B, int nout, int H, int W, int pad_y, int pad_x, const int* ys, const int* xs, int nty,
