@@ -486,6 +486,8 @@ class CellposeFinetune:
         return_measurements: bool = Field(False, description="Also return per-cell measurements (area, centroid, "
                                                              "box, shape, per-channel intensity) and the median "
                                                              "cell diameter in pixels."),
+        augment: bool = Field(False, description="Test-time augmentation: half-overlapping tiles, each mirrored by "
+                                                 "its grid position, outputs mirrored back and averaged (slower)."),
     ) -> list:
         """Segment images; returns one {input_path, output(, flows)(, measurements, diameter_px)} per image.  With ``z_axis``,
         ``stitch_threshold > 0`` or ``do_3D`` every input array is one z-stack and ``output`` is
@@ -493,7 +495,9 @@ class CellposeFinetune:
         [3, Z', H, W] (dZ, dY, dX), cellprob [Z', H, W]], ``Z'`` the depth after ``anisotropy``.
         ``return_measurements``: ``measurements`` is the table of ``reference.derive_measurements`` (one
         row per label of ``output``; a z-stack is measured as one volume against the stack as given)
-        and ``diameter_px`` the median cell diameter, the value ``diameter`` expects."""
+        and ``diameter_px`` the median cell diameter, the value ``diameter`` expects.  ``augment``
+        (allowed in every mode, stacks and ``do_3D`` included) is part of the batching group key:
+        requests that differ in it never share a batch."""
         if isinstance(artifact, dict):
             w = artifact
             artifact = w.get("artifact", w.get("artifact_id", w.get("id")))
@@ -506,6 +510,7 @@ class CellposeFinetune:
             stitch_threshold, z_axis = w.get("stitch_threshold", stitch_threshold), w.get("z_axis", z_axis)
             do_3D, anisotropy = w.get("do_3D", do_3D), w.get("anisotropy", anisotropy)
             return_measurements = w.get("return_measurements", return_measurements)
+            augment = w.get("augment", augment)
         return_measurements = bool(_opt(return_measurements) or False)
         stitch_threshold = float(_opt(stitch_threshold) or 0.0)
         z_axis = _opt(z_axis)
@@ -536,7 +541,8 @@ class CellposeFinetune:
             images = [clahe_image(im, self._device()) for im in images]
         runner = await self._runner(model_id)
         prm = {"diameter": _opt(diameter), "flow_threshold": float(flow_threshold),
-               "cellprob_threshold": float(cellprob_threshold), "niter": int(_opt(niter) or 200)}
+               "cellprob_threshold": float(cellprob_threshold), "niter": int(_opt(niter) or 200),
+               "augment": bool(_opt(augment) or False)}
         if stack_mode:
             out = await self._infer_stacks(runner, names, images, prm, stitch_threshold, int(z_axis or 0),
                                            bool(return_flows), bool(json_safe), do_3D, anisotropy, return_measurements)
@@ -627,6 +633,8 @@ class CellposeFinetune:
         enable_clahe: bool = Field(False, description="CLAHE pre-processing (brightfield / phase contrast)."),
         thresholds: list | None = Field(None, description="IoU thresholds of the average precision "
                                                           "(default [0.5, 0.75, 0.9]; at most 8, each in (0, 1])."),
+        augment: bool = Field(False, description="Test-time augmentation: half-overlapping tiles, each mirrored by "
+                                                 "its grid position, outputs mirrored back and averaged (slower)."),
     ) -> dict:
         """Segment labelled images and score the masks against their annotations: average precision
         at each IoU threshold (``cellpose.metrics.average_precision``).  Returns ``per_image``, one
@@ -643,7 +651,7 @@ class CellposeFinetune:
             flow_threshold = w.get("flow_threshold", flow_threshold)
             cellprob_threshold = w.get("cellprob_threshold", cellprob_threshold)
             niter, enable_clahe = w.get("niter", niter), w.get("enable_clahe", enable_clahe)
-            thresholds = w.get("thresholds", thresholds)
+            thresholds, augment = w.get("thresholds", thresholds), w.get("augment", augment)
         from bioengine_worker_amd.cellpose.metrics import DEFAULT_THRESHOLDS, metrics_document
 
         ths = [float(t) for t in (_opt(thresholds) or DEFAULT_THRESHOLDS)]
@@ -669,7 +677,8 @@ class CellposeFinetune:
             images = [clahe_image(im, self._device()) for im in images]
         runner = await self._runner(model_id)
         prm = {"diameter": _opt(diameter), "flow_threshold": float(flow_threshold),
-               "cellprob_threshold": float(cellprob_threshold), "niter": int(_opt(niter) or 200)}
+               "cellprob_threshold": float(cellprob_threshold), "niter": int(_opt(niter) or 200),
+               "augment": bool(_opt(augment) or False)}
         chw = [image_chw(im, runner.nchan) for im in images]
         groups: dict = {}
         for i, (name, c, lab) in enumerate(zip(names, chw, labels)):

@@ -100,17 +100,32 @@ def normalize99_sort(x: torch.Tensor, lower: float = 1.0, upper: float = 99.0) -
 
 
 class TilePlan:
-    """Cellpose tiling of an (H, W) image: pad to a multiple of 16 (+8 margin), 224 tiles, 10 % overlap."""
+    """Cellpose tiling of an (H, W) image: pad to a multiple of 16 (+8 margin), 224 tiles, 10 % overlap.
 
-    def __init__(self, H: int, W: int, bsize: int = 224, overlap: float = 0.1, device="cpu"):
+    ``augment`` (test-time augmentation, :func:`reference.make_tiles` with ``augment=True``): tiles
+    are always ``bsize x bsize`` and overlap by half (``overlap`` is ignored), an axis shorter than
+    the tile is zero-padded at its end (canvas ``Ly x Lx``), and tile ``(j, i)`` of the grid goes to
+    the network mirrored in y when ``i`` is odd and in x when ``j`` is odd.  The gathers write the
+    mirrored tiles and :meth:`blend` takes the network's outputs as they come and mirrors them back
+    (:func:`reference.unaugment_tiles`) as it reads: the ``*_aug`` entry points of ``tiles.hip``."""
+
+    def __init__(self, H: int, W: int, bsize: int = 224, overlap: float = 0.1, device="cpu", augment: bool = False):
         self.H, self.W = H, W
+        self.augment = bool(augment)
         ya, yb = ref.pad_amounts(H)
         xa, xb = ref.pad_amounts(W)
         self.pad_y, self.pad_x = ya, xa
         self.Hp, self.Wp = H + ya + yb, W + xa + xb
-        self.ys = ref.tile_starts(self.Hp, bsize, overlap)
-        self.xs = ref.tile_starts(self.Wp, bsize, overlap)
-        self.by, self.bx = min(bsize, self.Hp), min(bsize, self.Wp)
+        if self.augment:
+            self.ys = ref.tile_starts_augment(self.Hp, bsize)
+            self.xs = ref.tile_starts_augment(self.Wp, bsize)
+            self.by = self.bx = int(bsize)
+        else:
+            self.ys = ref.tile_starts(self.Hp, bsize, overlap)
+            self.xs = ref.tile_starts(self.Wp, bsize, overlap)
+            self.by, self.bx = min(bsize, self.Hp), min(bsize, self.Wp)
+        self.Ly, self.Lx = max(self.Hp, self.by), max(self.Wp, self.bx)  # the canvas the tiles cover
+        self._sfx = "_aug" if self.augment else ""
         self.nt = len(self.ys) * len(self.xs)
         m = ref.taper_mask(self.by, self.bx)
         # the 2-D taper is separable: recover the 1-D factors from its centre row/col
@@ -127,7 +142,7 @@ class TilePlan:
         B, C, H, W = img.shape
         out = torch.empty(B * self.nt, self.by, self.bx, cpad, dtype=torch.bfloat16, device=img.device)
         img = img.float().contiguous()
-        _native.call("be_tiles_gather", _native.ptr(img), B, C, H, W, self.pad_y, self.pad_x, _native.ptr(self.ys_t),
+        _native.call("be_tiles_gather" + self._sfx, _native.ptr(img), B, C, H, W, self.pad_y, self.pad_x, _native.ptr(self.ys_t),
                      _native.ptr(self.xs_t), len(self.ys), len(self.xs), self.by, self.bx, cpad, _native.ptr(out),
                      _native.stream(img.device))
         return out
@@ -144,7 +159,7 @@ class TilePlan:
         out = torch.empty(B * self.nt, self.by, self.bx, cpad, dtype=torch.bfloat16, device=x_raw.device)
         sptr = _native.stream(x_raw.device)
         ws = _pct_workspace(x_raw.device, sptr, B * c_use)
-        _native.call("be_tiles_gather_norm", _native.ptr(x_raw), RAW_DTYPES[x_raw.dtype], B, C, c_use, H, W, float(lower),
+        _native.call("be_tiles_gather_norm" + self._sfx, _native.ptr(x_raw), RAW_DTYPES[x_raw.dtype], B, C, c_use, H, W, float(lower),
                      float(upper), self.pad_y, self.pad_x, _native.ptr(self.ys_t), _native.ptr(self.xs_t), len(self.ys),
                      len(self.xs), self.by, self.bx, cpad, _native.ptr(out), _native.ptr(ws), ws.numel() // 4 * 4, sptr)
         return out
@@ -152,7 +167,7 @@ class TilePlan:
     def blend(self, yt: torch.Tensor, B: int) -> torch.Tensor:
         nout = yt.shape[1]
         out = torch.empty(B, nout, self.H, self.W, dtype=torch.float32, device=yt.device)
-        _native.call("be_tiles_blend", _native.ptr(yt), B, nout, self.H, self.W, self.pad_y, self.pad_x,
+        _native.call("be_tiles_blend" + self._sfx, _native.ptr(yt), B, nout, self.H, self.W, self.pad_y, self.pad_x,
                      _native.ptr(self.ys_t), _native.ptr(self.xs_t), len(self.ys), len(self.xs), self.by, self.bx,
                      _native.ptr(self.wy), _native.ptr(self.wx), _native.ptr(out), _native.stream(yt.device))
         return out

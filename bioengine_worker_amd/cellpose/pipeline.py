@@ -38,6 +38,10 @@ class EvalParams:
     tile: bool = True
     bsize: int | None = None  # None: the network's native tile (224 CPnet, 256 Cellpose-SAM)
     tile_overlap: float = 0.1
+    #: test-time augmentation (cellpose ``augment=True``): tiles overlapping by half, each mirrored by
+    #: its position in the tile grid, outputs mirrored back and averaged (reference.make_tiles /
+    #: unaugment_tiles).  Needs ``tile=True``; ``tile_overlap`` is ignored.
+    augment: bool = False
     compute_masks: bool = True
     #: GPU: split a batch into this many micro-batches and run mask recovery of micro-batch i on a
     #: second HIP stream while the network runs micro-batch i+1 (the mask stage is a chain of
@@ -123,9 +127,9 @@ class CellposeRunner:
         from .gpu import TilePlan
 
         bs = p.bsize or self.bsize
-        key = (H, W, bs, p.tile_overlap)
+        key = (H, W, bs, p.tile_overlap, bool(p.augment))
         if key not in self._plans:
-            self._plans[key] = TilePlan(H, W, bs, p.tile_overlap, device=self.device)
+            self._plans[key] = TilePlan(H, W, bs, p.tile_overlap, device=self.device, augment=bool(p.augment))
         return self._plans[key]
 
     #: HBM bytes one 224^2 CPnet tile keeps live at the forward's peak (measured on MI355X: 23.0-23.4
@@ -182,6 +186,8 @@ class CellposeRunner:
         ``raw`` (tiled GPU path only): ``x`` is the un-normalised batch in the form :meth:`_front`
         passes on, and the tile gather normalises it (1st / 99th percentile) as it reads."""
         B, C, H, W = x.shape
+        if p.augment and not p.tile:
+            raise ValueError("augment=True needs tile=True: the augmentation mirrors tiles")
         if raw and not (self.device.type == "cuda" and p.tile):
             raise ValueError("run_net(raw=True) needs the tiled GPU path")
         if self.device.type == "cuda":
@@ -217,7 +223,11 @@ class CellposeRunner:
                 ya, yb = ref.pad_amounts(H)
                 xa, xb = ref.pad_amounts(W)
                 imgp = np.pad(img, ((0, 0), (ya, yb), (xa, xb)))
-                tiles, tys, txs = ref.make_tiles(imgp, bs, p.tile_overlap)
+                Lyc, Lxc = imgp.shape[1:]
+                if p.augment:
+                    tiles, tys, txs, Lyc, Lxc = ref.make_tiles(imgp, bs, augment=True)
+                else:
+                    tiles, tys, txs = ref.make_tiles(imgp, bs, p.tile_overlap)
                 tt = torch.from_numpy(tiles).float()
                 if self.is_sam:
                     T, _, by, bx = tt.shape
@@ -227,7 +237,8 @@ class CellposeRunner:
                     st = torch.zeros(T, 256)
                 else:
                     yt, st, _ = self.net(tt)
-                yf = ref.average_tiles(yt.numpy(), tys, txs, imgp.shape[1], imgp.shape[2])
+                yt = ref.unaugment_tiles(yt.numpy(), tys, txs) if p.augment else yt.numpy()
+                yf = ref.average_tiles(yt, tys, txs, Lyc, Lxc)
                 ys.append(torch.from_numpy(yf[:, ya: ya + H, xa: xa + W].copy()))
                 styles.append(st.sum(0))
             else:
@@ -430,7 +441,8 @@ class CellposeRunner:
         B = x.shape[0]
         if self.device.type != "cuda" or B > self.GRAPH_NET_MAX_B or not x.is_cuda:
             return None
-        key = (tuple(x.shape), x.dtype, bool(p.normalize), bool(p.tile), p.bsize, p.tile_overlap, p.max_tiles)
+        key = (tuple(x.shape), x.dtype, bool(p.normalize), bool(p.tile), p.bsize, p.tile_overlap, p.max_tiles,
+               bool(p.augment))
         ent = self._net_graphs.get(key)
         if ent is False:
             return None

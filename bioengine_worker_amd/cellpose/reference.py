@@ -11,6 +11,12 @@ Stages
 normalize99      per-channel 1st/99th percentile scaling (linear-interpolated percentiles)
 make_tiles       224x224 tiles with 10 % overlap over an image padded to a multiple of 16 (+8 margin)
 average_tiles    tapered-mask weighted blend of tile outputs
+augment          test-time augmentation (cellpose ``augment=True``, written from memory of cellpose 3's
+                 ``make_tiles`` / ``unaugment_tiles``; not compared with the library):
+                 tile_starts_augment / make_tiles(augment=True): bsize x bsize tiles overlapping by half,
+                 tile (j, i) of the grid mirrored in y when i is odd and in x when j is odd;
+                 unaugment_tiles: outputs mirrored back, dY / dX negated along a mirrored axis; then
+                 average_tiles as usual
 follow_flows     niter Euler steps along dP (bilinear, grid_sample align_corners=False semantics)
 get_masks        histogram of end points -> 5x5 max seeds (count > 10) -> 5x 3x3 dilation in 11x11
                  windows over histogram support (> 2) -> per-pixel label, drop masks > 40 % of image
@@ -70,13 +76,70 @@ def taper_mask(ly: int = 224, lx: int = 224, sig: float = 7.5) -> np.ndarray:
     return mask[bsize // 2 - ly // 2: bsize // 2 - ly // 2 + ly, bsize // 2 - lx // 2: bsize // 2 - lx // 2 + lx].astype(np.float32)
 
 
-def make_tiles(img: np.ndarray, bsize: int = 224, overlap: float = 0.1):
-    """img [C, Ly, Lx] (already padded) -> tiles [nt, C, by, bx], ystart, xstart."""
+def tile_starts_augment(L: int, bsize: int = 224) -> list[int]:
+    """Tile starts along one padded axis under ``augment``: the axis counts as ``L' = max(L, bsize)``
+    long, ``n = max(2, ceil(2 L' / bsize))`` tiles of ``bsize`` overlap by about half, at
+    ``linspace(0, L' - bsize, n)`` truncated.  Equal starts are kept (an axis of at most ``bsize``
+    gives ``[0, 0]``: the same window twice, once of them mirrored)."""
+    Lc = max(int(L), int(bsize))
+    n = max(2, -(-2 * Lc // int(bsize)))
+    return [int(v) for v in np.linspace(0, Lc - bsize, n).astype(int)]
+
+
+def make_tiles(img: np.ndarray, bsize: int = 224, overlap: float = 0.1, augment: bool = False):
+    """img [C, Ly, Lx] (already padded) -> tiles [nt, C, by, bx], ystart, xstart.
+
+    ``augment`` (test-time augmentation; ``overlap`` is ignored): returns ``(tiles [nt, C, bsize,
+    bsize], ystart, xstart, Lyc, Lxc)``.  An axis shorter than ``bsize`` is zero-padded at its end to
+    ``bsize`` (the canvas ``Lyc x Lxc``), the starts are :func:`tile_starts_augment`, and the tile
+    of grid row ``j``, grid column ``i`` (index ``j * len(xstart) + i``) has its rows reversed when
+    ``i`` is odd and its columns reversed when ``j`` is odd."""
     C, Ly, Lx = img.shape
+    if augment:
+        Lyc, Lxc = max(Ly, bsize), max(Lx, bsize)
+        canvas = np.zeros((C, Lyc, Lxc), img.dtype)
+        canvas[:, :Ly, :Lx] = img
+        ys, xs = tile_starts_augment(Ly, bsize), tile_starts_augment(Lx, bsize)
+        tiles = []
+        for j, y in enumerate(ys):
+            for i, x in enumerate(xs):
+                t = canvas[:, y: y + bsize, x: x + bsize]
+                if i % 2:
+                    t = t[:, ::-1]
+                if j % 2:
+                    t = t[:, :, ::-1]
+                tiles.append(t)
+        return np.stack(tiles), ys, xs, Lyc, Lxc
     ys, xs = tile_starts(Ly, bsize, overlap), tile_starts(Lx, bsize, overlap)
     by, bx = min(bsize, Ly), min(bsize, Lx)
     tiles = np.stack([img[:, y: y + by, x: x + bx] for y in ys for x in xs])
     return tiles, ys, xs
+
+
+def unaugment_tiles(y: np.ndarray, ys, xs) -> np.ndarray:
+    """Network outputs ``y`` [nt, nout >= 3, by, bx] (dY, dX, cellprob, ...) of the tiles of
+    ``make_tiles(..., augment=True)`` -> the same outputs mirrored back (a new array): tile
+    ``(j, i)`` gets its rows reversed and channel 0 negated when ``i`` is odd, its columns reversed
+    and channel 1 negated when ``j`` is odd; the other channels keep their sign."""
+    y = np.asarray(y)
+    nx = len(xs)
+    if y.ndim != 4 or y.shape[0] != len(ys) * nx or y.shape[1] < 3:
+        raise ValueError(f"unaugment_tiles expects [{len(ys) * nx}, nout >= 3, by, bx] tile outputs, got shape {y.shape}")
+    out = y.copy()
+    for j in range(len(ys)):
+        for i in range(nx):
+            k = j * nx + i
+            t = y[k]
+            if i % 2:
+                t = t[:, ::-1]
+            if j % 2:
+                t = t[:, :, ::-1]
+            out[k] = t
+            if i % 2:
+                out[k, 0] = -out[k, 0]
+            if j % 2:
+                out[k, 1] = -out[k, 1]
+    return out
 
 
 def average_tiles(y: np.ndarray, ys, xs, Ly: int, Lx: int, dtype=np.float32) -> np.ndarray:

@@ -13,6 +13,11 @@
 //   the percentile normalisation of percentile.hip applied in the load: the select passes run on the
 //   raw pixels, then each pixel is read once, normalised with its row's constants and stored as
 //   bf16 -- neither an fp32 copy of the input nor a normalised fp32 image ever exists.
+// be_tiles_gather_aug / be_tiles_gather_norm_aug / be_tiles_blend_aug: the three calls under test-time
+//   augmentation.  Tile (ti, tj) of the grid reaches the network with its rows reversed when tj is odd
+//   and its columns reversed when ti is odd; the blend reads the tile output back at the reversed
+//   offset and negates dY / dX of a reversed axis.  The mirroring is an index reversal in loads that
+//   happen anyway: no mirrored copy of the tiles or of their outputs exists.
 #include "percentile.h"
 
 namespace {
@@ -30,7 +35,11 @@ constexpr int kMaxGridYZ = 65535;
 // consecutive pixels, so the loads from an image row and the stores are contiguous.
 // NORM: img holds raw pixels and row b * C_use + c of `state` that row's selected keys
 // (percentile.h); channels >= C_use of a wider image (C_src) are ignored.
-template <typename T, bool NORM>
+// AUG (test-time augmentation): the tile of grid row ti, grid column tj is stored with its rows
+// reversed when tj is odd and its columns reversed when ti is odd, i.e. tile row ty holds image row
+// ys[ti] + (by - 1 - ty).  Both flags are per block, the stores stay ascending; only the load index
+// runs backwards.
+template <typename T, bool NORM, bool AUG = false>
 __global__ __launch_bounds__(256) void tiles_gather_kernel(const T* __restrict__ img, int tile0, int C_src, int C_use, int H,
                                                            int W, int pad_y, int pad_x, const int* __restrict__ ys,
                                                            const int* __restrict__ xs, int nty, int ntx, int by, int bx,
@@ -45,9 +54,11 @@ __global__ __launch_bounds__(256) void tiles_gather_kernel(const T* __restrict__
   const int nt = nty * ntx;
   const int b = tile / nt, t = tile - b * nt;
   const int ti = t / ntx;
+  const int tj = t - ti * ntx;
   const int ty0 = blockIdx.y * kRows;
-  const int yy0 = ys[ti] + ty0 - pad_y;
-  const int xx = xs[t - ti * ntx] + tx - pad_x;
+  const bool fy = AUG && (tj & 1), fx = AUG && (ti & 1);
+  const int yy0 = ys[ti] + (fy ? by - 1 - ty0 : ty0) - pad_y;
+  const int xx = xs[tj] + (fx ? bx - 1 - tx : tx) - pad_x;
   const bool inx = xx >= 0 && xx < W;
   float f[kRows][8];
 #pragma unroll
@@ -64,7 +75,7 @@ __global__ __launch_bounds__(256) void tiles_gather_kernel(const T* __restrict__
       const T* plane = img + ((size_t)b * C_src + c) * H * W;
 #pragma unroll
       for (int r = 0; r < kRows; ++r) {
-        const int yy = yy0 + r;
+        const int yy = fy ? yy0 - r : yy0 + r;
         if (inx && yy >= 0 && yy < H && ty0 + r < by) {
           const float v = (float)plane[(size_t)yy * W + xx];
           f[r][j] = NORM ? (cst ? 0.f : (v - p1) * scale) : v;
@@ -83,7 +94,7 @@ __global__ __launch_bounds__(256) void tiles_gather_kernel(const T* __restrict__
   }
 }
 
-template <typename T, bool NORM>
+template <typename T, bool NORM, bool AUG = false>
 int gather_launch(const void* img, int B, int C_src, int C_use, int H, int W, int pad_y, int pad_x, const int* ys,
                   const int* xs, int nty, int ntx, int by, int bx, int cpad, be_pct::Coef cf, const uint32_t* state,
                   void* out, hipStream_t s) {
@@ -91,7 +102,7 @@ int gather_launch(const void* img, int B, int C_src, int C_use, int H, int W, in
   const unsigned gx = (unsigned)(((long long)bx * (cpad >> 3) + 255) / 256), gy = (unsigned)((by + kRows - 1) / kRows);
   for (long long t0 = 0; t0 < tiles; t0 += kMaxGridYZ) {  // one launch unless a call has more tiles than grid.z holds
     const unsigned gz = (unsigned)(tiles - t0 < kMaxGridYZ ? tiles - t0 : kMaxGridYZ);
-    hipLaunchKernelGGL((tiles_gather_kernel<T, NORM>), dim3(gx, gy, gz), dim3(256), 0, s, static_cast<const T*>(img), (int)t0,
+    hipLaunchKernelGGL((tiles_gather_kernel<T, NORM, AUG>), dim3(gx, gy, gz), dim3(256), 0, s, static_cast<const T*>(img), (int)t0,
                        C_src, C_use, H, W, pad_y, pad_x, ys, xs, nty, ntx, by, bx, cpad, cf, state, (bf16_t*)out);
   }
   return BE_CHECK_LAUNCH();
@@ -103,6 +114,11 @@ bool gather_args_ok(int B, int C, int H, int W, int nty, int ntx, int by, int bx
          (long long)bx * (cpad >> 3) <= 0x7fffffffLL - 256;
 }
 
+// AUG: the tile outputs are still mirrored as the gather stored them.  The taper weight is taken at
+// the un-mirrored offset (ty, tx); the value is read at the mirrored one and the flow component along
+// a mirrored axis (channel 0 = dY, channel 1 = dX) changes its sign.  Every (i, j) is one tile, so
+// equal starts contribute once per tile.
+template <bool AUG>
 __global__ __launch_bounds__(256) void tiles_blend_kernel(const float* __restrict__ yt, int B, int nout, int H, int W,
                                                           int pad_y, int pad_x, const int* __restrict__ ys,
                                                           const int* __restrict__ xs, int nty, int ntx, int by, int bx,
@@ -125,8 +141,13 @@ __global__ __launch_bounds__(256) void tiles_blend_kernel(const float* __restric
       if (tx < 0 || tx >= bx) continue;
       const float w = wy[ty] * wx[tx];
       wsum += w;
-      const float* src = yt + (((size_t)b * nty * ntx + i * ntx + j) * nout) * by * bx + (size_t)ty * bx + tx;
-      for (int c = 0; c < nout && c < 4; ++c) acc[c] += w * src[(size_t)c * by * bx];
+      const bool fy = AUG && (j & 1), fx = AUG && (i & 1);
+      const int sy = fy ? by - 1 - ty : ty, sx = fx ? bx - 1 - tx : tx;
+      const float* src = yt + (((size_t)b * nty * ntx + i * ntx + j) * nout) * by * bx + (size_t)sy * bx + sx;
+      for (int c = 0; c < nout && c < 4; ++c) {
+        const float v = src[(size_t)c * by * bx];
+        acc[c] += w * (((c == 0 && fy) || (c == 1 && fx)) ? -v : v);
+      }
     }
   }
   const float inv = wsum > 0.f ? 1.f / wsum : 0.f;
@@ -168,8 +189,43 @@ int be_tiles_blend(const float* yt, int B, int nout, int H, int W, int pad_y, in
                    int ntx, int by, int bx, const float* wy, const float* wx, float* out, hipStream_t s) {
   if (nout > 4) return -1;
   const long long n = (long long)B * H * W;
-  hipLaunchKernelGGL(tiles_blend_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, yt, B, nout, H, W, pad_y, pad_x,
+  hipLaunchKernelGGL(tiles_blend_kernel<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, yt, B, nout, H, W, pad_y, pad_x,
                      ys, xs, nty, ntx, by, bx, wy, wx, out);
+  return BE_CHECK_LAUNCH();
+}
+
+// ---- test-time augmentation (cellpose augment=True): the same three calls on half-overlapping
+// by x bx tiles, every tile mirrored by its grid position (see tiles_gather_kernel / tiles_blend_kernel).
+// Their own instantiations: the entry points above compile exactly as without them.
+
+int be_tiles_gather_aug(const float* img, int B, int C, int H, int W, int pad_y, int pad_x, const int* ys, const int* xs,
+                        int nty, int ntx, int by, int bx, int cpad, void* out, hipStream_t s) {
+  if (!gather_args_ok(B, C, H, W, nty, ntx, by, bx, cpad)) return -1;
+  return gather_launch<float, false, true>(img, B, C, C, H, W, pad_y, pad_x, ys, xs, nty, ntx, by, bx, cpad, be_pct::Coef{},
+                                           nullptr, out, s);
+}
+
+int be_tiles_gather_norm_aug(const void* x, int dtype, int B, int C_src, int C_use, int H, int W, float lower, float upper,
+                             int pad_y, int pad_x, const int* ys, const int* xs, int nty, int ntx, int by, int bx,
+                             int cpad, void* out, void* ws, long long ws_bytes, hipStream_t s) {
+  if (!gather_args_ok(B, C_src, H, W, nty, ntx, by, bx, cpad)) return -1;
+  be_pct::Coef cf;
+  const uint32_t* state;
+  const int rc = be_pct::select_run(x, dtype, B, C_src, C_use, (long long)H * W, lower, upper, ws, ws_bytes, s, &cf, &state);
+  if (rc) return rc;
+  if (dtype == be_pct::kF32)
+    return gather_launch<float, true, true>(x, B, C_src, C_use, H, W, pad_y, pad_x, ys, xs, nty, ntx, by, bx, cpad, cf, state, out, s);
+  if (dtype == be_pct::kU16)
+    return gather_launch<uint16_t, true, true>(x, B, C_src, C_use, H, W, pad_y, pad_x, ys, xs, nty, ntx, by, bx, cpad, cf, state, out, s);
+  return gather_launch<uint8_t, true, true>(x, B, C_src, C_use, H, W, pad_y, pad_x, ys, xs, nty, ntx, by, bx, cpad, cf, state, out, s);
+}
+
+int be_tiles_blend_aug(const float* yt, int B, int nout, int H, int W, int pad_y, int pad_x, const int* ys, const int* xs,
+                       int nty, int ntx, int by, int bx, const float* wy, const float* wx, float* out, hipStream_t s) {
+  if (nout > 4) return -1;
+  const long long n = (long long)B * H * W;
+  hipLaunchKernelGGL(tiles_blend_kernel<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, yt, B, nout, H, W, pad_y,
+                     pad_x, ys, xs, nty, ntx, by, bx, wy, wx, out);
   return BE_CHECK_LAUNCH();
 }
 
