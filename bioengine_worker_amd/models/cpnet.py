@@ -214,8 +214,10 @@ class _FConv:
     def __init__(self, seq: nn.Sequential, relu: bool, device, cin_pad=None, cout_pad_to=None):
         bn, conv = seq[0], seq[-1]
         self.pc = convops.PackedConv.from_weight(conv.weight, conv.bias, cin_pad=cin_pad, cout_pad_to=cout_pad_to).to(device)
-        # fragment-order weights of the 128-channel ping-pong kernel: packed here, not in the first forward
-        if convops.frag_eligible(self.pc) and torch.device(device).type == "cuda":
+        # fragment-order weights of the 128-channel ping-pong kernel (and of its pooled 64 -> 128 build,
+        # the level-2 entry conv with its 1x1 projection): packed here, not in the first forward
+        if (convops.frag_eligible(self.pc) or convops.frag_eligible_pool(self.pc) or
+                convops.frag_eligible_proj(self.pc)) and torch.device(device).type == "cuda":
             self.pc.frag()
         s, t = _bn_fold(bn, device)
         self.scale = _pad_vec(s, self.pc.cin_pad, 0.0)
@@ -504,8 +506,15 @@ class CPnetEngine:
                     x1 = pairops.conv_pair(src, P[("down", n, 0)], res=e["proj"](src, inmode=im), res_mode="full")
                 xd.append(pairops.conv_pair(x1, P[("down", n, 1)], res=x1, res_mode="full"))
                 continue
-            proj = e["proj"](src, inmode=im)
-            h = e["c0"](src, inmode=im)
+            if n > 0 and convops.pp128_takes_pool_proj(e["c0"].pc, e["proj"].pc, src):
+                # level 2 in large calls: the entry conv and the projection of the same pooled pixels
+                # in one launch of the ping-pong kernel's pooled build (the native side decides)
+                c0, pj = e["c0"], e["proj"]
+                h, proj = convops.fused_conv2d_pool_proj(src, c0.pc, pj.pc, scale=c0.scale, shift=c0.shift, relu=c0.relu,
+                                                         proj_scale=pj.scale, proj_shift=pj.shift)
+            else:
+                proj = e["proj"](src, inmode=im)
+                h = e["c0"](src, inmode=im)
             x1 = e["c1"](h, residual=proj)
             h = e["c2"](x1)
             xd.append(e["c3"](h, residual=x1))

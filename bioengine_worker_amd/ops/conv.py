@@ -137,7 +137,7 @@ class PackedConv:
         if ``wp`` was replaced or written since).  An engine calls this when it is built; a conv whose
         fragments were never built, or went stale, runs on the per-layer kernel (:meth:`frag_built`)."""
         if self.frag_built() is None:
-            self.wf = pack_frag(self.wp)
+            self.wf = pack_frag(self.wp) if self.ks == 3 else pack_frag_1x1(self.wp)
             self.wf_key = self._wp_key()
         return self.wf
 
@@ -153,6 +153,54 @@ def frag_eligible(pc: PackedConv) -> bool:
     """The layers with a ping-pong build that reads fragment-order weights
     (``csrc/kernels/conv_pp128.hip``): 3x3, 128 -> 128 channels."""
     return pc.ks == 3 and pc.ck == 32 and pc.cin_pad == 128 and pc.cout == 128 and pc.cout_pad == 128
+
+
+def frag_eligible_pool(pc: PackedConv) -> bool:
+    """The layer with a pooled-input build of that kernel: 3x3, 64 -> 128 channels, read through a
+    2x2 max-pool (CPnet's level-2 entry conv).  Its fragments are ``[2 chunks, 9 taps, 8 channel tiles]``."""
+    return pc.ks == 3 and pc.ck == 32 and pc.cin_pad == 64 and pc.cout == 128 and pc.cout_pad == 128
+
+
+def frag_eligible_proj(pc: PackedConv) -> bool:
+    """The 1x1 projection that the pooled build can compute beside its 3x3 conv: 64 -> 128 channels
+    (CPnet's level-2 residual projection).  Its fragments are :func:`pack_frag_1x1`'s."""
+    return pc.ks == 1 and pc.cin_pad == 64 and pc.cout == 128 and pc.cout_pad == 128
+
+
+def pp128_takes_pool(pc: PackedConv, x: torch.Tensor) -> bool:
+    """Whether ``fused_conv2d(x, pc, inmode="pool2")`` (no residual, no output activation) runs on the
+    ping-pong kernel's pooled build: the conv has its fragment-order weights and the native side
+    (``be_conv_pp128_takes_pool``: even source size, the kernel's size rule, ``BE_CONV_PP128_POOL``)
+    takes a call of ``x``'s geometry."""
+    if not x.is_cuda or not frag_eligible_pool(pc) or pc.frag_built() is None:
+        return False
+    N, Hs, Ws, _ = x.shape
+    return bool(_native.hip().be_conv_pp128_takes_pool(N, Hs, Ws))
+
+
+def pp128_takes_pool_proj(pc: PackedConv, pp: PackedConv, x: torch.Tensor) -> bool:
+    """Whether :func:`fused_conv2d_pool_proj` may be called for the 3x3 conv ``pc`` and the 1x1
+    projection ``pp`` on the source ``x``: both have their fragment-order weights and the native side
+    (``be_conv_pp128_takes_pool_proj``: the pooled build's rule and ``BE_CONV_PP128_POOL_PROJ``) takes a
+    call of ``x``'s geometry.  Asked before anything is launched."""
+    if not x.is_cuda or not frag_eligible_pool(pc) or not frag_eligible_proj(pp):
+        return False
+    if pc.frag_built() is None or pp.frag_built() is None:
+        return False
+    N, Hs, Ws, _ = x.shape
+    return bool(_native.hip().be_conv_pp128_takes_pool_proj(N, Hs, Ws))
+
+
+def pack_frag_1x1(wp: torch.Tensor) -> torch.Tensor:
+    """A 1x1 conv's ``PackedConv.wp`` ``[cout, nchunk, ck]`` with ``nchunk * ck == 64`` (K index = input
+    channel) in MFMA-A-fragment order ``[2 K-steps, cout / 16 channel tiles, 64 lanes, 8]``: lane
+    ``kq * 16 + lrow`` of channel tile ``ct`` holds, for K-step ``s``, input channels
+    ``s * 32 + kq * 8 .. + 7`` of output channel ``ct * 16 + lrow``."""
+    cout, nchunk, kp = wp.shape
+    assert cout % 16 == 0 and nchunk * kp == 64, "fragment packing: a 1x1 conv of 64 input channels, whole channel tiles"
+    nct = cout // 16
+    t = wp.reshape(nct, 16, 2, 4, 8)                # ct, lrow, s, kq, e
+    return t.permute(2, 0, 3, 1, 4).contiguous().reshape(2, nct, 64, 8)
 
 
 def pack_frag(wp: torch.Tensor) -> torch.Tensor:
@@ -353,7 +401,7 @@ def fused_conv2d(x: torch.Tensor, pc: PackedConv, *, x2=None, scale=None, shift=
         assert post_scale.dtype == torch.float32 and post_scale.is_contiguous() and post_scale.numel() == pc.cout
     # the layers with a ping-pong build also pass their fragment-order weights; the entry point picks
     # the kernel (csrc/kernels/conv_pp128.hip, be_conv2d_nhwc_frag)
-    wf = pc.frag_built() if frag_eligible(pc) else None
+    wf = pc.frag_built() if frag_eligible(pc) or (inmode == "pool2" and frag_eligible_pool(pc)) else None
     args = (
         _native.ptr(x), _native.ptr(x2), _native.ptr(scale), _native.ptr(shift), pshift_ns, pscale_ns,
         int(bool(relu)) | (2 if post_relu else 0),
@@ -367,6 +415,30 @@ def fused_conv2d(x: torch.Tensor, pc: PackedConv, *, x2=None, scale=None, shift=
     else:
         _native.call("be_conv2d_nhwc_frag", *args, _native.stream(x.device))
     return out
+
+
+def fused_conv2d_pool_proj(x: torch.Tensor, pc: PackedConv, pp: PackedConv, *, scale, shift, relu: bool, proj_scale,
+                           proj_shift) -> tuple[torch.Tensor, torch.Tensor]:
+    """``(fused_conv2d(x, pc, scale=scale, shift=shift, relu=relu, inmode="pool2"),
+    fused_conv2d(x, pp, scale=proj_scale, shift=proj_shift, inmode="pool2"))`` in one launch of the
+    128-channel ping-pong kernel's pooled build (``be_conv_pp128_pool_proj``), bit for bit.  ``x`` is
+    [N, Hs, Ws, 64] bf16 on the GPU; ``shift`` may be per image, the projection's affine is [64].  Ask
+    :func:`pp128_takes_pool_proj` first: a call the kernel does not take is an error, not a fallback."""
+    N, Hs, Ws, Cin = x.shape
+    assert x.is_cuda and x.dtype == torch.bfloat16 and x.is_contiguous() and Cin == 64 == pc.cin_pad == pp.cin_pad
+    assert frag_eligible_pool(pc) and frag_eligible_proj(pp)
+    wf, wpf = pc.frag_built(), pp.frag_built()
+    assert wf is not None and wpf is not None, "fragment-order weights are packed when the engine is built"
+    assert proj_scale.dtype == proj_shift.dtype == torch.float32 and proj_scale.numel() == proj_shift.numel() == 64
+    assert proj_scale.is_contiguous() and proj_shift.is_contiguous()
+    H, W = Hs // 2, Ws // 2
+    out = torch.empty(N, H, W, 128, device=x.device, dtype=torch.bfloat16)
+    out2 = torch.empty(N, H, W, 128, device=x.device, dtype=torch.bfloat16)
+    _native.call("be_conv_pp128_pool_proj", _native.ptr(x), _native.ptr(scale), _native.ptr(shift),
+                 _affine_stride(shift, N, Cin), _affine_stride(scale, N, Cin), int(bool(relu)), _native.ptr(wf),
+                 _native.ptr(pc.bias), _native.ptr(out), _native.ptr(proj_scale), _native.ptr(proj_shift), _native.ptr(wpf),
+                 _native.ptr(pp.bias), _native.ptr(out2), N, Hs, Ws, _native.stream(x.device))
+    return out, out2
 
 
 def depth_to_space2(y: torch.Tensor, c: int) -> torch.Tensor:

@@ -44,6 +44,15 @@
 // rounded to bf16 before LDS, zero padding after the activation, chunks in order, taps 0..8 within
 // a chunk, 32-deep K-steps with lane group kq holding channels 8 kq..8 kq + 7, (acc + bias) +
 // residual, one rounding), so the output is bit-identical to it.
+//
+// A second build (POOL) is the level-2 entry conv, 64 -> 128 channels from a 2 x 2 max-pooled source
+// (conv2d_nhwc_kernel<3, 32, 64, 2, ...> bit for bit): two chunks per tile, and the four raw values
+// of a halo unit fetched in two halves so that no more than 40 VGPRs of halo cross an MFMA phase
+// (Halo<true>).  Five phases per tile: commit(0), MFMA(0), commit(1), MFMA(1), epilogue.  Its PROJ build
+// also computes the level's residual projection (1x1, 64 -> 128, its own affine, no ReLU;
+// conv2d_nhwc_kernel<1, 64, 64, 2, ...> bit for bit) of the same pooled pixels as a second output: the
+// commits write the projection's input of the tile's centre pixels to a second LDS image per group, and
+// after the epilogue the freed accumulators take two 32-deep K-steps per fragment from zero.
 #include <cstdlib>
 
 #include "common.h"
@@ -63,11 +72,19 @@ constexpr int WD = 3;                       // weight fragments are fetched WD K
 constexpr int WSTEP = 8 * 64 * 8;           // elements per K-step of the fragment layout (8 ct)
 constexpr int BD = 6, BR = 7;               // pixel fragments are read BD MFMA pairs ahead, ring of BR
 static_assert(IW % 4 == 2, "the swizzle derivation needs 30 y = 2 y (mod 4)");
-static_assert(LDS <= 128 * 1024, "LDS budget of the ping-pong kernels");
+// PROJ: a second image per group, the 1x1 projection's input of the tile's 8 x 28 centre pixels, all 64
+// channels (128-byte pixels).  Swizzle: unit u of pixel (y, x) lives at unit u ^ 2 ((x >> 1) & 1) ^
+// 4 (y & 1).  Derivation: the 16-byte bank slot of a unit is 8 (x mod 2) + u (28 y is even); a
+// ds_read_b128 lane group holds patch rows 0 and 3 at unit k and rows 1 and 2 at unit k ^ 1, four pixels
+// per row parity of x: bit 0 separates {0, 3} from {1, 2}, (x >> 1) & 1 in bit 1 the two pixels of one
+// row, y & 1 in bit 2 row 0 from 3 and row 1 from 2 (patch origins are multiples of 4).
+constexpr int PJ_B = TH * TW * 128;         // 28672
+constexpr int LDS_PROJ = LDS + 2 * PJ_B;    // 95744
+static_assert(LDS_PROJ <= 128 * 1024, "LDS budget of the ping-pong kernels");
 static_assert(BD < BR, "ring");
 
 struct Args {
-  const bf16_t* x;     // [N, H, W, 128]
+  const bf16_t* x;     // [N, H, W, 128]; POOL: [N, 2 H, 2 W, 64]
   const float* sa;     // scale [128] (sa_ns 0) or [N, sa_ns], or null (1)
   const float* ta;     // shift likewise, or null (0)
   const bf16_t* wf;    // fragment-order weights
@@ -79,6 +96,12 @@ struct Args {
   int relu;
   int res_up2;         // the residual is at half resolution, read through nearest 2x up-sampling (even H, W)
   int tiles_x, tiles_y;
+  // PROJ build: out2 = conv1x1( pool(x) * sp + tp ) + bias_p, [N, H, W, 128]
+  const float* sp;     // scale [64]
+  const float* tp;     // shift [64]
+  const bf16_t* wpf;   // fragment-order projection weights [2 K-steps][8 ct][64 lanes][8]
+  const float* bias_p; // [128] or null
+  bf16_t* out2;
   // diagnostics (STAMP instantiation only, tools/pp128_phase_profile.py): [grid][2 groups][16] cycle
   // counts of wave 0 of each group
   unsigned long long* stamps;
@@ -98,15 +121,31 @@ __device__ __forceinline__ TileXY tile_of(const Args& a, int t) {
   return r;
 }
 
+template <bool POOL>
 struct Halo {
   u32x4 h[HUPT];
   float4 aff[4];  // scale / shift of this thread's 8 channels ride along with the halo
 };
 
+// POOL: the four raw values of a unit arrive in two halves.  Source row 2 y (h, hb: columns 2 x and
+// 2 x + 1) is issued where the plain build issues its halo and is in flight across the MFMA phase, 40
+// VGPRs in place of 20 + the 16 of the affine; source row 2 y + 1 (q, qb) and the affine follow in a
+// VALU phase, where the weight and pixel-fragment rings of the MFMA phase (60 VGPRs) are dead: before
+// the epilogue for the next tile's chunk 0 (PROJ: behind the projection, which needs the accumulators'
+// registers once more), at the top of the commit for chunk 1, whose 64-byte halves of the 128-byte
+// source pixels chunk 0 has already brought into the cache.
+template <>
+struct Halo<true> {
+  u32x4 h[HUPT], hb[HUPT];
+  u32x4 q[HUPT], qb[HUPT];
+  float4 aff[4];
+  float4 affp[4];  // PROJ: the projection's scale / shift of the same 8 channels
+};
+
 // chunk ch of the tile's 10 x 30 input halo -> registers; clamped, unconditional loads (commit
 // zeroes what lies outside the image and skips units past HU)
-__device__ __forceinline__ void issue_halo(const Args& a, TileXY t, int ch, int gt, Halo& hr) {
-  const int c = ch * 32 + (gt & 3) * 8;  // a thread's channel group is the same for every unit (GT % 4 == 0)
+template <bool POOL>
+__device__ __forceinline__ void issue_aff(const Args& a, TileXY t, int c, Halo<POOL>& hr) {
   hr.aff[0] = hr.aff[1] = make_float4(1.f, 1.f, 1.f, 1.f);
   hr.aff[2] = hr.aff[3] = make_float4(0.f, 0.f, 0.f, 0.f);
   if (a.sa) {
@@ -119,19 +158,85 @@ __device__ __forceinline__ void issue_halo(const Args& a, TileXY t, int ch, int 
     hr.aff[2] = *reinterpret_cast<const float4*>(tr);
     hr.aff[3] = *reinterpret_cast<const float4*>(tr + 4);
   }
+}
+
+// POOL: x is [N, 2 H, 2 W, 64]; element offset of channel c of source pixel (2 gy + row, 2 gx)
+__device__ __forceinline__ size_t pool_src(const Args& a, int n, int gy, int gx, int row, int c) {
+  return (((size_t)n * 2 * a.H + 2 * gy + row) * 2 * a.W + 2 * gx) * 64 + c;
+}
+
+template <bool POOL>
+__device__ __forceinline__ void issue_halo(const Args& a, TileXY t, int ch, int gt, Halo<POOL>& hr) {
+  const int c = ch * 32 + (gt & 3) * 8;  // a thread's channel group is the same for every unit (GT % 4 == 0)
+  if constexpr (!POOL) issue_aff(a, t, c, hr);
 #pragma unroll
   for (int i = 0; i < HUPT; ++i) {
     const int pi = min(gt + i * GT, HU - 1) >> 2;
     const int y = pi / IW, x = pi - y * IW;
     const int gy = min(max(t.ty0 - 1 + y, 0), a.H - 1);
     const int gx = min(max(t.tx0 - 1 + x, 0), a.W - 1);
-    hr.h[i] = *reinterpret_cast<const u32x4*>(a.x + (((size_t)t.n * a.H + gy) * a.W + gx) * C + c);
+    if constexpr (POOL) {
+      const bf16_t* p = a.x + pool_src(a, t.n, gy, gx, 0, c);
+      hr.h[i] = *reinterpret_cast<const u32x4*>(p);
+      hr.hb[i] = *reinterpret_cast<const u32x4*>(p + 64);
+    } else {
+      hr.h[i] = *reinterpret_cast<const u32x4*>(a.x + (((size_t)t.n * a.H + gy) * a.W + gx) * C + c);
+    }
   }
+}
+
+// POOL: the second half of chunk ch's halo (source row 2 y + 1) and the affine
+__device__ __forceinline__ void issue_halo_b(const Args& a, TileXY t, int ch, int gt, Halo<true>& hr) {
+  const int c = ch * 32 + (gt & 3) * 8;
+  issue_aff(a, t, c, hr);
+#pragma unroll
+  for (int i = 0; i < HUPT; ++i) {
+    const int pi = min(gt + i * GT, HU - 1) >> 2;
+    const int y = pi / IW, x = pi - y * IW;
+    const int gy = min(max(t.ty0 - 1 + y, 0), a.H - 1);
+    const int gx = min(max(t.tx0 - 1 + x, 0), a.W - 1);
+    const bf16_t* p = a.x + pool_src(a, t.n, gy, gx, 1, c);
+    hr.q[i] = *reinterpret_cast<const u32x4*>(p);
+    hr.qb[i] = *reinterpret_cast<const u32x4*>(p + 64);
+  }
+}
+
+// PROJ: the projection's scale / shift of chunk ch's channels of this thread
+__device__ __forceinline__ void issue_affp(const Args& a, int ch, int gt, Halo<true>& hr) {
+  const int c = ch * 32 + (gt & 3) * 8;
+  hr.affp[0] = *reinterpret_cast<const float4*>(a.sp + c);
+  hr.affp[1] = *reinterpret_cast<const float4*>(a.sp + c + 4);
+  hr.affp[2] = *reinterpret_cast<const float4*>(a.tp + c);
+  hr.affp[3] = *reinterpret_cast<const float4*>(a.tp + c + 4);
+}
+
+// POOL: the maximum of the four raw values in conv2d_nhwc_kernel's order, max(max(r0, r1), max(q0, q1)),
+// packed again (the max of bf16 values is exact in bf16), in two steps so that a commit never holds all
+// four: reduce_a, h <- max(h, hb), as soon as the first half is in and before the second is issued
+// behind it; reduce_b, h <- max(h, max(q, qb)).  commit() then sees h as the plain build's halo.
+__device__ __forceinline__ uint32_t max_bf16x2(uint32_t p, uint32_t q) {
+  const float lo = fmaxf(lo_bf(p), lo_bf(q)), hi = fmaxf(hi_bf(p), hi_bf(q));
+  return (__float_as_uint(lo) >> 16) | (__float_as_uint(hi) & 0xffff0000u);
+}
+
+__device__ __forceinline__ void reduce_a(Halo<true>& hr) {
+#pragma unroll
+  for (int i = 0; i < HUPT; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) hr.h[i][j] = max_bf16x2(hr.h[i][j], hr.hb[i][j]);
+}
+
+__device__ __forceinline__ void reduce_b(Halo<true>& hr) {
+#pragma unroll
+  for (int i = 0; i < HUPT; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) hr.h[i][j] = max_bf16x2(hr.h[i][j], max_bf16x2(hr.q[i][j], hr.qb[i][j]));
 }
 
 // P1: activation -> bf16 -> the swizzled input image (zero outside the image: conv padding applies
 // after the activation)
-__device__ __forceinline__ void commit(const Args& a, TileXY t, int gt, const Halo& hr, unsigned char* rin) {
+template <bool POOL>
+__device__ __forceinline__ void commit(const Args& a, TileXY t, int gt, const Halo<POOL>& hr, unsigned char* rin) {
   const int c = gt & 3;
   const float sc[8] = {hr.aff[0].x, hr.aff[0].y, hr.aff[0].z, hr.aff[0].w, hr.aff[1].x, hr.aff[1].y, hr.aff[1].z, hr.aff[1].w};
   const float sh[8] = {hr.aff[2].x, hr.aff[2].y, hr.aff[2].z, hr.aff[2].w, hr.aff[3].x, hr.aff[3].y, hr.aff[3].z, hr.aff[3].w};
@@ -153,6 +258,29 @@ __device__ __forceinline__ void commit(const Args& a, TileXY t, int gt, const Ha
       }
     }
     *reinterpret_cast<u32x4*>(rin + pi * 64 + ((c ^ (((x >> 1) & 1) << 1)) << 4)) = pk;
+  }
+}
+
+// PROJ: the pooled values (h after reduce_b) of the tile's centre pixels under the projection's affine,
+// no ReLU, rounded to bf16 -> the group's second image, channel units 4 ch + c.  A 1x1 conv has no
+// padding and pixels outside the image are never stored, so every centre pixel is written as it is.
+__device__ __forceinline__ void commit_proj(int ch, int gt, const Halo<true>& hr, unsigned char* rpj) {
+  const int c = gt & 3;
+  const float sc[8] = {hr.affp[0].x, hr.affp[0].y, hr.affp[0].z, hr.affp[0].w, hr.affp[1].x, hr.affp[1].y, hr.affp[1].z, hr.affp[1].w};
+  const float sh[8] = {hr.affp[2].x, hr.affp[2].y, hr.affp[2].z, hr.affp[2].w, hr.affp[3].x, hr.affp[3].y, hr.affp[3].z, hr.affp[3].w};
+#pragma unroll
+  for (int i = 0; i < HUPT; ++i) {
+    const int u = gt + i * GT;
+    if (u >= HU) continue;
+    const int pi = u >> 2;
+    const int y = pi / IW, x = pi - y * IW;
+    if (y < 1 || y > TH || x < 1 || x > TW) continue;
+    const int py = y - 1, px = x - 1;
+    u32x4 pj;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      pj[j] = pack2bf(fmaf(lo_bf(hr.h[i][j]), sc[2 * j], sh[2 * j]), fmaf(hi_bf(hr.h[i][j]), sc[2 * j + 1], sh[2 * j + 1]));
+    *reinterpret_cast<u32x4*>(rpj + (py * TW + px) * 128 + (((ch * 4 + c) ^ (((px >> 1) & 1) << 1) ^ ((py & 1) << 2)) << 4)) = pj;
   }
 }
 
@@ -208,6 +336,40 @@ __device__ __forceinline__ void mma_chunk(f32x4 (&acc)[2][NF], const unsigned ch
         acc[ct][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[s][ct], bf[f % BR], acc[ct][j], 0, 0, 0);
       __builtin_amdgcn_sched_barrier(0);
     }
+  }
+}
+
+// PROJ: the 1x1 projection of the tile's centre pixels from zero accumulators, conv2d_nhwc_kernel<1, 64,
+// 64, 2, ...>'s two 32-deep K-steps (channels 0-31, then 32-63; lane group kq holds channels 8 kq..8 kq + 7
+// of the step).  wl: w_lane of the projection's fragment-order weights.
+__device__ __forceinline__ void proj_mma(f32x4 (&acc)[2][NF], const unsigned char* rpj, const bf16_t* wl, int lrow, int kq) {
+  bf16x8 w[2][2];
+#pragma unroll
+  for (int s = 0; s < 2; ++s)
+#pragma unroll
+    for (int ct = 0; ct < 2; ++ct) w[s][ct] = *reinterpret_cast<const bf16x8*>(wl + s * WSTEP + ct * 512);
+  const int ly = lrow >> 2, lx = lrow & 3;
+  const int P0 = (ly * TW + lx) * 128 + ((kq ^ (((lx >> 1) & 1) << 1) ^ ((ly & 1) << 2)) << 4);
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < NF; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  auto rd = [&](int f) {
+    const int s = f / NF, j = f % NF;
+    return *reinterpret_cast<const bf16x8*>(rpj + (P0 ^ (s << 6)) + (4 * (j / FC) * TW + 4 * (j % FC)) * 128);
+  };
+  constexpr int PD = 3, PR = 4;  // read PD fragments ahead, ring of PR
+  bf16x8 bf[PR];
+#pragma unroll
+  for (int f = 0; f < PD; ++f) bf[f] = rd(f);
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int f = 0; f < 2 * NF; ++f) {
+    if (f + PD < 2 * NF) bf[(f + PD) % PR] = rd(f + PD);
+#pragma unroll
+    for (int ct = 0; ct < 2; ++ct)
+      acc[ct][f % NF] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[f / NF][ct], bf[f % PR], acc[ct][f % NF], 0, 0, 0);
+    __builtin_amdgcn_sched_barrier(0);
   }
 }
 
@@ -291,8 +453,15 @@ __device__ __forceinline__ void epilogue(const Args& a, TileXY t, const f32x4 (&
   }
 }
 
-template <bool STAMP = false>
+// POOL: the level-2 entry conv, 64 -> 128 channels: x is [N, 2 H, 2 W, 64] and is read through a 2 x 2
+// max-pool (conv2d_nhwc_kernel's INMODE 2), two 32-channel chunks (six phases per tile), weights
+// [2 chunks][9 taps][8 ct] in the same fragment order, no residual.  PROJ (with POOL): the level's 1x1
+// projection of the same pooled pixels as a second output (Args::out2), computed after the epilogue on
+// the freed accumulators.
+template <bool STAMP = false, bool POOL = false, bool PROJ = false>
 __global__ __launch_bounds__(NTP, 2) void conv_pp128_kernel(Args a) {
+  static_assert(POOL || !PROJ, "the projection reads the pooled input");
+  constexpr int NC = POOL ? 2 : NCH;
   // STAMP: as conv_pair_pp64_kernel; slots: commit / MFMA of chunk 0, of chunks 1..3 together, epilogue;
   // work cycles of slot i at i, the wait at its closing barrier at 8 + i, iterations at 15
   unsigned long long ph_work[5] = {0, 0, 0, 0, 0}, ph_wait[5] = {0, 0, 0, 0, 0};
@@ -321,8 +490,11 @@ __global__ __launch_bounds__(NTP, 2) void conv_pp128_kernel(Args a) {
   const int grp = __builtin_amdgcn_readfirstlane(tid0 / GT);  // waves w and w + 4 share a SIMD
   const int gt0 = tid0 & (GT - 1);
   unsigned char* reg = smem + grp * IN_B;
-  Halo halo;
+  unsigned char* rpj = PROJ ? smem + LDS + grp * PJ_B : nullptr;
+  Halo<POOL> halo;
   issue_halo(a, tile_of(a, min(t0 + grp, t1 - 1)), 0, gt0, halo);
+  if constexpr (POOL) issue_halo_b(a, tile_of(a, min(t0 + grp, t1 - 1)), 0, gt0, halo);
+  if constexpr (PROJ) issue_affp(a, 0, gt0, halo);
   if (grp == 1) __builtin_amdgcn_s_barrier();  // the stagger: group 1 runs one phase behind
   const int iters = (t1 - t0 + 1) >> 1;
   for (int k = 0; k < iters; ++k) {
@@ -348,7 +520,7 @@ __global__ __launch_bounds__(NTP, 2) void conv_pp128_kernel(Args a) {
       for (int j = 0; j < NF; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
     WPre wpre;
 #pragma unroll
-    for (int c = 0; c < NCH; ++c) {
+    for (int c = 0; c < NC; ++c) {
       // P1: input chunk c -> activated image.  Behind it the next chunk's halo (or the group's next
       // tile's first) and then the first weight fragments of this chunk's MFMA phase.  Loads return in
       // issue order: a halo issued inside the MFMA phase held every later weight fragment back until
@@ -356,9 +528,27 @@ __global__ __launch_bounds__(NTP, 2) void conv_pp128_kernel(Args a) {
       // travels while the group waits at the barrier for the other group's MFMA phase to end.
       int gc = gt0;
       asm volatile("" : "+v"(gc));
+      if constexpr (POOL) {
+        reduce_a(halo);
+        if (c > 0) {
+          __builtin_amdgcn_sched_barrier(0);
+          issue_halo_b(a, cur, c, gc, halo);
+        }
+        reduce_b(halo);
+        if constexpr (PROJ) {
+          if (c > 0) {
+            __builtin_amdgcn_sched_barrier(0);
+            issue_affp(a, c, gc, halo);
+          }
+        }
+      }
       commit(a, cur, gc, halo, reg);
+      if constexpr (PROJ) {
+        __builtin_amdgcn_sched_barrier(0);
+        commit_proj(c, gc, halo, rpj);
+      }
       __builtin_amdgcn_sched_barrier(0);
-      if (c + 1 < NCH)
+      if (c + 1 < NC)
         issue_halo(a, cur, c + 1, gc, halo);
       else
         issue_halo(a, tile_of(a, min(t + 2, t1 - 1)), 0, gc, halo);
@@ -378,7 +568,34 @@ __global__ __launch_bounds__(NTP, 2) void conv_pp128_kernel(Args a) {
     int g3 = gt0;
     asm volatile("" : "+v"(g3));
     const bool full = cur.ty0 + TH <= a.H && cur.tx0 + TW <= a.W;  // workgroup-uniform, as a.res is
-    if (a.res != nullptr && a.res_up2) {
+    if constexpr (POOL) {
+      // the second half of the next tile's first halo travels during the epilogue and the barrier wait
+      // (PROJ: during the barrier wait only; the projection needs the accumulators' registers once more)
+      if constexpr (!PROJ) {
+        issue_halo_b(a, tile_of(a, min(t + 2, t1 - 1)), 0, g3, halo);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      if (full)
+        epilogue<0, true>(a, cur, acc, cp, g3 & 15, (g3 & 63) >> 4, act);
+      else
+        epilogue<0, false>(a, cur, acc, cp, g3 & 15, (g3 & 63) >> 4, act);
+      if constexpr (PROJ) {
+        __builtin_amdgcn_sched_barrier(0);
+        int g4 = gt0;
+        asm volatile("" : "+v"(g4));
+        proj_mma(acc, rpj, w_lane(a.wpf, cp, g4 & 63), g4 & 15, (g4 & 63) >> 4);
+        Args b = a;
+        b.out = a.out2;
+        b.bias = a.bias_p;
+        if (full)
+          epilogue<0, true>(b, cur, acc, cp, g4 & 15, (g4 & 63) >> 4, act);
+        else
+          epilogue<0, false>(b, cur, acc, cp, g4 & 15, (g4 & 63) >> 4, act);
+        __builtin_amdgcn_sched_barrier(0);
+        issue_halo_b(a, tile_of(a, min(t + 2, t1 - 1)), 0, g4, halo);
+        issue_affp(a, 0, g4, halo);
+      }
+    } else if (a.res != nullptr && a.res_up2) {
       if (full)
         epilogue<2, true>(a, cur, acc, cp, g3 & 15, (g3 & 63) >> 4, act);
       else
@@ -428,8 +645,22 @@ int g_pp128_res_up2 = [] {
   return e ? atoi(e) : 1;
 }();
 
+// BE_CONV_PP128_POOL (default 1, A/B): 0 keeps the pooled 64 -> 128 entry conv on conv2d_nhwc_kernel
+int g_pp128_pool = [] {
+  const char* e = getenv("BE_CONV_PP128_POOL");
+  return e ? atoi(e) : 1;
+}();
+
+// BE_CONV_PP128_POOL_PROJ (default 1, A/B): 0 makes be_conv_pp128_takes_pool_proj answer 0, so the
+// level's 1x1 projection stays a launch of its own beside the pooled build
+int g_pp128_pool_proj = [] {
+  const char* e = getenv("BE_CONV_PP128_POOL_PROJ");
+  return e ? atoi(e) : 1;
+}();
+
 int g_pp128_grid = 0;      // be_conv_pp128_set_grid (0 = one workgroup per CU)
 int g_pp128_launches = 0;  // be_conv_pp128_launches
+int g_pp128_pool_launches = 0;  // be_conv_pp128_pool_launches
 unsigned long long* g_pp128_stamps = nullptr;  // diagnostics: be_conv_pp128_set_stamps
 int g_pp128_stamps_cap = 0;                    // workgroups the stamp buffer holds
 
@@ -482,7 +713,9 @@ int be_conv_pp128_launches() { return g_pp128_launches; }
 // null).  A 3x3, Cin = Cout = 128, INMODE 0, no-x2, bf16-NHWC-output call without an output
 // activation runs on conv_pp128_kernel when every group of every workgroup gets at least two 8 x 28
 // tiles (as pp64_ok: batch-1 latency calls would only recompute dummy tiles) or the grid is forced
-// (be_conv_pp128_set_grid); every other call goes to be_conv2d_nhwc unchanged.
+// (be_conv_pp128_set_grid); every other call goes to be_conv2d_nhwc unchanged.  Under the same size
+// rule a 3x3, Cin = 64, Cout = 128, INMODE 2 call from an even source, without a residual, runs on the
+// kernel's pooled build (be_conv_pp128_takes_pool).
 //
 // res_up2 != 0: `res` is [N, H/2, W/2, 128] and is read through nearest 2x up-sampling.  Only the
 // ping-pong kernel has that epilogue: the caller asks be_conv_pp128_takes_res_up2 first, and a call
@@ -495,14 +728,34 @@ int be_conv2d_nhwc_frag_res(const void* x, const void* x2, const float* pscale, 
   const bool shape_ok = wfrag && ks == 3 && ck == 32 && inmode == 0 && !x2 && !out_f32_nchw && Cin == 128 &&
                         Cout == 128 && Hs == H && Ws == W && !(prelu & 2) && !qscale && !qshift && x && out;
   if (res_up2 && !(shape_ok && res && H % 2 == 0 && W % 2 == 0)) return -31;
-  if (shape_ok) {
+  // the pooled entry conv: 3x3, 64 -> 128, INMODE 2 from an even source, no residual
+  const bool pool_ok = g_pp128_pool && wfrag && ks == 3 && ck == 32 && inmode == 2 && !x2 && !out_f32_nchw && Cin == 64 &&
+                       Cout == 128 && Hs == 2 * H && Ws == 2 * W && !(prelu & 2) && !qscale && !qshift && !res && x && out;
+  if (shape_ok || pool_ok) {
     pp128::Args a;
     const int g = pp128_grid_for(N, H, W, &a.tiles_x, &a.tiles_y);
+    if (g > 0 && pool_ok) {
+      a.x = (const bf16_t*)x; a.sa = pscale; a.ta = pshift; a.sa_ns = pscale_ns; a.ta_ns = pshift_ns;
+      a.wf = (const bf16_t*)wfrag; a.bias = bias; a.res = nullptr; a.out = (bf16_t*)out;
+      a.N = N; a.H = H; a.W = W; a.relu = prelu & 1;
+      a.res_up2 = 0;
+      a.sp = a.tp = a.bias_p = nullptr; a.wpf = nullptr; a.out2 = nullptr;
+      a.stamps = g_pp128_stamps;
+      ++g_pp128_pool_launches;
+      if (g_pp128_stamps != nullptr) {
+        if (g > g_pp128_stamps_cap) return -30;
+        hipLaunchKernelGGL((pp128::conv_pp128_kernel<true, true>), dim3(g), dim3(pp128::NTP), pp128::LDS, stream, a);
+        return BE_CHECK_LAUNCH();
+      }
+      hipLaunchKernelGGL((pp128::conv_pp128_kernel<false, true>), dim3(g), dim3(pp128::NTP), pp128::LDS, stream, a);
+      return BE_CHECK_LAUNCH();
+    }
     if (g > 0) {
       a.x = (const bf16_t*)x; a.sa = pscale; a.ta = pshift; a.sa_ns = pscale_ns; a.ta_ns = pshift_ns;
       a.wf = (const bf16_t*)wfrag; a.bias = bias; a.res = (const bf16_t*)res; a.out = (bf16_t*)out;
       a.N = N; a.H = H; a.W = W; a.relu = prelu & 1;
       a.res_up2 = res_up2 ? 1 : 0;
+      a.sp = a.tp = a.bias_p = nullptr; a.wpf = nullptr; a.out2 = nullptr;
       a.stamps = g_pp128_stamps;
       ++g_pp128_launches;
       if (g_pp128_stamps != nullptr) {
@@ -533,6 +786,70 @@ int be_conv2d_nhwc_frag(const void* x, const void* x2, const float* pscale, cons
 // input transform, bf16 NHWC output) with N images of H x W runs on conv_pp128_kernel now: the size
 // rule above under the present BE_CONV_PP128 and be_conv_pp128_set_grid.
 int be_conv_pp128_takes(int N, int H, int W) { return pp128_grid_for(N, H, W, nullptr, nullptr) > 0 ? 1 : 0; }
+
+// 1 if a be_conv2d_nhwc_frag call of the pooled entry shape (3x3, 64 -> 128, INMODE 2, fragment-order
+// weights, no residual, bf16 NHWC output) with N source images of Hs x Ws runs on the kernel's pooled
+// build now: an even source size, the size rule of the Hs/2 x Ws/2 output, BE_CONV_PP128_POOL.
+int be_conv_pp128_takes_pool(int N, int Hs, int Ws) {
+  return g_pp128_pool && Hs % 2 == 0 && Ws % 2 == 0 && pp128_grid_for(N, Hs / 2, Ws / 2, nullptr, nullptr) > 0 ? 1 : 0;
+}
+
+// Tests / A/B runs in one process: the two switches that BE_CONV_PP128_POOL and BE_CONV_PP128_POOL_PROJ
+// set when the library is loaded.
+int be_conv_pp128_set_pool(int pool, int pool_proj) {
+  g_pp128_pool = pool;
+  g_pp128_pool_proj = pool_proj;
+  return 0;
+}
+
+// Launches of the pooled builds (with or without the projection) by this process so far.  They have a
+// counter of their own: be_conv_pp128_launches keeps counting the 128 -> 128 calls alone.
+int be_conv_pp128_pool_launches() { return g_pp128_pool_launches; }
+
+// 1 if be_conv_pp128_pool_proj takes N source images of Hs x Ws now: the rule above and
+// BE_CONV_PP128_POOL_PROJ.
+int be_conv_pp128_takes_pool_proj(int N, int Hs, int Ws) {
+  return g_pp128_pool_proj && be_conv_pp128_takes_pool(N, Hs, Ws);
+}
+
+// The level-2 entry of CPnet's encoder in one launch, from x [N, Hs, Ws, 64] bf16 through a 2x2 max-pool:
+//   out  = conv3x3( relu?( pool(x) * pscale + pshift[n] ) ) + bias      [N, Hs/2, Ws/2, 128]
+//   out2 = conv1x1(        pool(x) * sp     + tp          ) + bias_p    likewise
+// each bit for bit what be_conv2d_nhwc gives for it alone (INMODE 2; ck 32 and ck 64).  wfrag: the 3x3
+// conv in pack_frag order [2][9][8][64][8]; wpfrag: the 1x1 in pack_frag_1x1 order [2][8][64][8].  The
+// caller asks be_conv_pp128_takes_pool_proj first: a call the kernel does not take is an error (-32).
+int be_conv_pp128_pool_proj(const void* x, const float* pscale, const float* pshift, int pshift_ns, int pscale_ns, int prelu,
+                            const void* wfrag, const float* bias, void* out, const float* sp, const float* tp,
+                            const void* wpfrag, const float* bias_p, void* out2, int N, int Hs, int Ws,
+                            hipStream_t stream) {
+  if (!x || !wfrag || !out || !sp || !tp || !wpfrag || !out2 || out == out2 || (prelu & ~1)) return -32;
+  if (!be_conv_pp128_takes_pool_proj(N, Hs, Ws)) return -32;
+  pp128::Args a;
+  const int g = pp128_grid_for(N, Hs / 2, Ws / 2, &a.tiles_x, &a.tiles_y);
+  a.x = (const bf16_t*)x; a.sa = pscale; a.ta = pshift; a.sa_ns = pscale_ns; a.ta_ns = pshift_ns;
+  a.wf = (const bf16_t*)wfrag; a.bias = bias; a.res = nullptr; a.out = (bf16_t*)out;
+  a.N = N; a.H = Hs / 2; a.W = Ws / 2; a.relu = prelu & 1;
+  a.res_up2 = 0;
+  a.sp = sp; a.tp = tp; a.wpf = (const bf16_t*)wpfrag; a.bias_p = bias_p; a.out2 = (bf16_t*)out2;
+  a.stamps = g_pp128_stamps;
+  static bool attr_set[BE_MAX_DEV] = {};
+  if (!attr_set[be_cur_dev()]) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&pp128::conv_pp128_kernel<false, true, true>),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, pp128::LDS_PROJ) != hipSuccess ||
+        hipFuncSetAttribute(reinterpret_cast<const void*>(&pp128::conv_pp128_kernel<true, true, true>),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, pp128::LDS_PROJ) != hipSuccess)
+      return -33;
+    attr_set[be_cur_dev()] = true;
+  }
+  ++g_pp128_pool_launches;
+  if (g_pp128_stamps != nullptr) {  // diagnostics: be_conv_pp128_set_stamps
+    if (g > g_pp128_stamps_cap) return -30;
+    hipLaunchKernelGGL((pp128::conv_pp128_kernel<true, true, true>), dim3(g), dim3(pp128::NTP), pp128::LDS_PROJ, stream, a);
+    return BE_CHECK_LAUNCH();
+  }
+  hipLaunchKernelGGL((pp128::conv_pp128_kernel<false, true, true>), dim3(g), dim3(pp128::NTP), pp128::LDS_PROJ, stream, a);
+  return BE_CHECK_LAUNCH();
+}
 
 // 1 if such a call may also hand its residual over at half resolution (be_conv2d_nhwc_frag_res).
 int be_conv_pp128_takes_res_up2(int N, int H, int W) {
