@@ -270,6 +270,20 @@ class CellposeFinetune:
         raise ValueError(f"Model identifier '{model}' is not a known pretrained model or a valid session ID / "
                          "published artifact reference.")
 
+    def _norm_prm(self, model_id: str, normalize) -> dict:
+        """The ``normalize`` of a request as runner parameters: ``{"normalize": NormParams}`` (hashable,
+        so it can sit in the batching key) plus ``norm3d`` when the dict names ``norm3D``.  A request
+        that gives none takes what the session ``model_id`` was trained with, if it stored one."""
+        from bioengine_worker_amd.cellpose.pipeline import norm_options
+
+        normalize = _opt(normalize)
+        if normalize is None:
+            f = session_dir(model_id) / TRAINING_PARAMS_FILENAME
+            if model_id not in BUILTIN_MODELS and f.exists():
+                normalize = json.loads(f.read_text()).get("normalize")
+        norm, norm3d = norm_options(True if normalize is None else normalize)
+        return {"normalize": norm} if norm3d is None else {"normalize": norm, "norm3d": norm3d}
+
     async def _fetch_published(self, ref: str) -> str:
         """``ws/alias`` or ``https://server/<ws>/artifacts/<alias>`` -> local session holding its weights."""
         if "/artifacts/" in ref:
@@ -488,6 +502,10 @@ class CellposeFinetune:
                                                              "cell diameter in pixels."),
         augment: bool = Field(False, description="Test-time augmentation: half-overlapping tiles, each mirrored by "
                                                  "its grid position, outputs mirrored back and averaged (slower)."),
+        normalize: bool | dict | None = Field(None, description="Intensity normalisation: a bool, or a dict with "
+                                                                "cellpose's keys (percentile, lowhigh, invert, "
+                                                                "tile_norm_blocksize, norm3D). Default: what the "
+                                                                "session named as model was trained with, else True."),
     ) -> list:
         """Segment images; returns one {input_path, output(, flows)(, measurements, diameter_px)} per image.  With ``z_axis``,
         ``stitch_threshold > 0`` or ``do_3D`` every input array is one z-stack and ``output`` is
@@ -497,7 +515,9 @@ class CellposeFinetune:
         row per label of ``output``; a z-stack is measured as one volume against the stack as given)
         and ``diameter_px`` the median cell diameter, the value ``diameter`` expects.  ``augment``
         (allowed in every mode, stacks and ``do_3D`` included) is part of the batching group key:
-        requests that differ in it never share a batch."""
+        requests that differ in it never share a batch.  So is ``normalize``, in its canonical
+        form (``pipeline.NormParams``); ``tile_norm_blocksize`` is not allowed with ``do_3D`` or with
+        a stack normalised as a whole (``norm3D``, the default)."""
         if isinstance(artifact, dict):
             w = artifact
             artifact = w.get("artifact", w.get("artifact_id", w.get("id")))
@@ -510,7 +530,7 @@ class CellposeFinetune:
             stitch_threshold, z_axis = w.get("stitch_threshold", stitch_threshold), w.get("z_axis", z_axis)
             do_3D, anisotropy = w.get("do_3D", do_3D), w.get("anisotropy", anisotropy)
             return_measurements = w.get("return_measurements", return_measurements)
-            augment = w.get("augment", augment)
+            augment, normalize = w.get("augment", augment), w.get("normalize", normalize)
         return_measurements = bool(_opt(return_measurements) or False)
         stitch_threshold = float(_opt(stitch_threshold) or 0.0)
         z_axis = _opt(z_axis)
@@ -542,7 +562,7 @@ class CellposeFinetune:
         runner = await self._runner(model_id)
         prm = {"diameter": _opt(diameter), "flow_threshold": float(flow_threshold),
                "cellprob_threshold": float(cellprob_threshold), "niter": int(_opt(niter) or 200),
-               "augment": bool(_opt(augment) or False)}
+               "augment": bool(_opt(augment) or False), **self._norm_prm(model_id, normalize)}
         if stack_mode:
             out = await self._infer_stacks(runner, names, images, prm, stitch_threshold, int(z_axis or 0),
                                            bool(return_flows), bool(json_safe), do_3D, anisotropy, return_measurements)
@@ -635,6 +655,10 @@ class CellposeFinetune:
                                                           "(default [0.5, 0.75, 0.9]; at most 8, each in (0, 1])."),
         augment: bool = Field(False, description="Test-time augmentation: half-overlapping tiles, each mirrored by "
                                                  "its grid position, outputs mirrored back and averaged (slower)."),
+        normalize: bool | dict | None = Field(None, description="Intensity normalisation: a bool, or a dict with "
+                                                                "cellpose's keys (percentile, lowhigh, invert, "
+                                                                "tile_norm_blocksize, norm3D). Default: what the "
+                                                                "session named as model was trained with, else True."),
     ) -> dict:
         """Segment labelled images and score the masks against their annotations: average precision
         at each IoU threshold (``cellpose.metrics.average_precision``).  Returns ``per_image``, one
@@ -652,6 +676,7 @@ class CellposeFinetune:
             cellprob_threshold = w.get("cellprob_threshold", cellprob_threshold)
             niter, enable_clahe = w.get("niter", niter), w.get("enable_clahe", enable_clahe)
             thresholds, augment = w.get("thresholds", thresholds), w.get("augment", augment)
+            normalize = w.get("normalize", normalize)
         from bioengine_worker_amd.cellpose.metrics import DEFAULT_THRESHOLDS, metrics_document
 
         ths = [float(t) for t in (_opt(thresholds) or DEFAULT_THRESHOLDS)]
@@ -678,7 +703,7 @@ class CellposeFinetune:
         runner = await self._runner(model_id)
         prm = {"diameter": _opt(diameter), "flow_threshold": float(flow_threshold),
                "cellprob_threshold": float(cellprob_threshold), "niter": int(_opt(niter) or 200),
-               "augment": bool(_opt(augment) or False)}
+               "augment": bool(_opt(augment) or False), **self._norm_prm(model_id, normalize)}
         chw = [image_chw(im, runner.nchan) for im in images]
         groups: dict = {}
         for i, (name, c, lab) in enumerate(zip(names, chw, labels)):
@@ -803,6 +828,10 @@ class CellposeFinetune:
         validation_interval: int | None = Field(None, description="Validate every N epochs (and at epoch 1); default 10."),
         enable_clahe: bool = Field(False, description="CLAHE pre-processing of training and test images."),
         rescale: bool = Field(False, description="Rescale crops by each image's estimated cell diameter."),
+        normalize: bool | dict = Field(True, description="Intensity normalisation of training, test and validation "
+                                                         "images: a bool, or a dict with cellpose's keys (percentile, "
+                                                         "lowhigh, invert, tile_norm_blocksize). Stored with the session "
+                                                         "and the default of infer / evaluate with it as model."),
         label: str | None = Field(None, description="Annotation label (saved with the session, used as a filter)."),
         batch_size: int = Field(1, description="Crops per optimisation step and GPU (reference: 1)."),
         n_gpus: int = Field(1, description="Data-parallel GPUs (a gang of one process per GPU, RCCL all-reduce)."),
@@ -825,6 +854,7 @@ class CellposeFinetune:
             validation_interval = w.get("validation_interval", validation_interval)
             enable_clahe, rescale = bool(w.get("enable_clahe", enable_clahe)), bool(w.get("rescale", rescale))
             label, context = w.get("label", label), w.get("context", context)
+            normalize = w.get("normalize", normalize)
         artifact, metadata_dir = _opt(artifact), _opt(metadata_dir)
         train_images, train_annotations = _opt(train_images), _opt(train_annotations)
         test_images, test_annotations = _opt(test_images), _opt(test_annotations)
@@ -844,6 +874,11 @@ class CellposeFinetune:
         if (test_images is None) != (test_annotations is None):
             raise ValueError("test_images and test_annotations must be provided together")
         model_id = await self.resolve_model_id(_opt(model) or "cpsam")
+        from bioengine_worker_amd.cellpose.pipeline import norm_options
+
+        normalize = True if _opt(normalize) is None else normalize
+        normalize = dict(normalize) if isinstance(normalize, dict) else bool(normalize)
+        norm_options(normalize)  # a bad option fails the call, not the session minutes later
         sid = datetime.now(timezone.utc).strftime("%Y-%m-%d-%H%M%S") + "-" + uuid.uuid4().hex[:8]
         params = {"artifact_id": artifact, "train_images": train_images, "train_annotations": train_annotations,
                   "metadata_dir": metadata_dir, "test_images": test_images, "test_annotations": test_annotations,
@@ -854,7 +889,7 @@ class CellposeFinetune:
                   "n_samples": int(n_samples) if _opt(n_samples) is not None else None, "session_id": sid,
                   "min_train_masks": int(min_train_masks if _opt(min_train_masks) is not None else 5),
                   "validation_interval": int(validation_interval) if _opt(validation_interval) is not None else None,
-                  "enable_clahe": bool(enable_clahe), "rescale": bool(rescale),
+                  "enable_clahe": bool(enable_clahe), "rescale": bool(rescale), "normalize": normalize,
                   "label": (str(label).strip() or None) if _opt(label) is not None else None,
                   "batch_size": int(batch_size or 1), "n_gpus": int(n_gpus or 1),
                   "data_source": "arrays" if arrays is not None else "artifact"}

@@ -7,6 +7,7 @@ per-mask job lists).  The semantics are those of :mod:`bioengine_worker_amd.cell
 """
 from __future__ import annotations
 
+import collections
 import ctypes
 import os
 
@@ -72,6 +73,157 @@ def normalize99(x: torch.Tensor, lower: float = 1.0, upper: float = 99.0) -> tor
     out = torch.empty_like(xf)
     _native.call("be_pct_normalize", _native.ptr(xf), rows, H * W, float(lower), float(upper), _native.ptr(out),
                  _native.ptr(ws), ws.numel() // 4 * 4, sptr)
+    return out
+
+
+#: largest block grid (ny * nx) of the tile normalisation (csrc/kernels/percentile.h kMaxCells)
+TILE_NORM_MAX_CELLS = 4096
+
+#: small device constants of the options (block starts per image shape, ``lowhigh`` bounds), least
+#: recently used first; both come from requests, so each cache holds at most ``_CONST_CACHE_MAX``
+#: entries.  An evicted tensor lives on while something else refers to it: eager launches are ordered
+#: on the stream that frees it, a captured graph holds :func:`norm_constants`.
+_CONST_CACHE_MAX = 64
+_tile_norm_grids: "collections.OrderedDict" = collections.OrderedDict()
+_lowhigh_consts: "collections.OrderedDict" = collections.OrderedDict()
+
+
+def _cached_const(cache, key, make):
+    v = cache.get(key)
+    if v is None:
+        v = cache[key] = make()
+        while len(cache) > _CONST_CACHE_MAX:
+            cache.popitem(last=False)
+    else:
+        cache.move_to_end(key)
+    return v
+
+
+def _gauss9() -> list[float]:
+    """Weights at distance 0..4 of scipy's ``gaussian_filter1d(sigma=1)`` kernel (truncate 4)."""
+    w = np.exp(-0.5 * np.arange(-4, 5, dtype=np.float64) ** 2)
+    w /= w.sum()
+    return [float(v) for v in w[4:]]
+
+
+def _tile_norm_grid(H: int, W: int, blocksize: int, device):
+    """Block starts of the tile normalisation on ``device``: ``(ys_t, xs_t, ny, nx, bh, bw)``.  Raises
+    ``ValueError`` before anything is launched when the grid has more cells than the maps kernel holds."""
+    if int(blocksize) <= 0:
+        raise ValueError(f"tile normalisation needs a positive blocksize, got {blocksize}")
+    ys, bh = ref.tile_norm_blocks(H, blocksize)
+    xs, bw = ref.tile_norm_blocks(W, blocksize)
+    if len(ys) * len(xs) > TILE_NORM_MAX_CELLS:
+        raise ValueError(f"tile_norm_blocksize={blocksize} on a {H} x {W} image gives a {len(ys)} x {len(xs)} block grid; "
+                         f"at most {TILE_NORM_MAX_CELLS} blocks are supported")
+    key = (H, W, int(blocksize), torch.device(device))
+    return _cached_const(_tile_norm_grids, key, lambda: (torch.tensor(ys, dtype=torch.int32, device=device),
+                                                         torch.tensor(xs, dtype=torch.int32, device=device),
+                                                         len(ys), len(xs), bh, bw))
+
+
+def _check_raw(x_raw: torch.Tensor, what: str) -> None:
+    if x_raw.dim() != 4 or x_raw.dtype not in RAW_DTYPES or not x_raw.is_contiguous():
+        raise ValueError(f"{what} takes a contiguous [B, C, H, W] uint8, uint16 or float32 tensor, got "
+                         f"{x_raw.dtype} {tuple(x_raw.shape)}")
+
+
+def tile_block_percentiles_gpu(x_raw: torch.Tensor, blocksize: int, lower: float = 1.0, upper: float = 99.0,
+                               c_use: int | None = None):
+    """Percentiles of the overlapping blocks (:func:`reference.tile_norm_raw_maps`) of the first
+    ``c_use`` channels of raw ``x_raw`` [B, C, H, W]: ``(x01, x99)``, each [B, c_use, ny, nx] float32."""
+    _check_raw(x_raw, "tile_block_percentiles_gpu")
+    B, C, H, W = x_raw.shape
+    c_use = C if c_use is None else min(int(c_use), C)
+    ys_t, xs_t, ny, nx, bh, bw = _tile_norm_grid(H, W, blocksize, x_raw.device)
+    lo = torch.empty(B, c_use, ny, nx, dtype=torch.float32, device=x_raw.device)
+    hi = torch.empty_like(lo)
+    _native.call("be_pct_block_select", _native.ptr(x_raw), RAW_DTYPES[x_raw.dtype], B, C, c_use, H, W, _native.ptr(ys_t),
+                 _native.ptr(xs_t), ny, nx, bh, bw, float(lower), float(upper), _native.ptr(lo), _native.ptr(hi),
+                 _native.stream(x_raw.device))
+    return lo, hi
+
+
+def tile_maps_fill_smooth_gpu(x01: torch.Tensor, x99: torch.Tensor):
+    """Block percentiles [B, C, ny, nx] -> the maps the apply samples (:func:`reference.tile_norm_fill`,
+    then :func:`reference.tile_norm_smooth`), in place; returns its arguments."""
+    B, C, ny, nx = x01.shape
+    if ny * nx > TILE_NORM_MAX_CELLS:
+        raise ValueError(f"a {ny} x {nx} block grid has more than {TILE_NORM_MAX_CELLS} blocks")
+    if not (x01.is_contiguous() and x99.is_contiguous() and x01.dtype == x99.dtype == torch.float32):
+        raise ValueError("tile_maps_fill_smooth_gpu takes contiguous float32 maps")
+    _native.call("be_pct_tile_maps", _native.ptr(x01), _native.ptr(x99), B * C, ny, nx, *_gauss9(), _native.stream(x01.device))
+    return x01, x99
+
+
+def tile_norm_maps_gpu(x_raw: torch.Tensor, blocksize: int, lower: float = 1.0, upper: float = 99.0,
+                       c_use: int | None = None):
+    """:func:`reference.tile_norm_maps` of every image of raw ``x_raw`` [B, C, H, W] (uint8, uint16
+    or float32, first ``c_use`` channels): ``(x01, x99)``, each [B, c_use, ny, nx] float32.  Two
+    launches (block select, fill + smoothing), no workspace and no host read."""
+    return tile_maps_fill_smooth_gpu(*tile_block_percentiles_gpu(x_raw, blocksize, lower, upper, c_use))
+
+
+def _lowhigh_tensor(lowhigh, c_use: int, device) -> torch.Tensor:
+    """``NormParams.lowhigh`` as a [c_use, 2] float32 device tensor (one small upload per value)."""
+    pairs = [lowhigh] * c_use if not isinstance(lowhigh[0], tuple) else list(lowhigh)
+    if len(pairs) < c_use:
+        raise ValueError(f"normalize: lowhigh has {len(pairs)} pairs for {c_use} channels")
+    key = (tuple(pairs[:c_use]), torch.device(device))
+    return _cached_const(_lowhigh_consts, key, lambda: torch.tensor(pairs[:c_use], dtype=torch.float32, device=device))
+
+
+def norm_constants(params, C: int, H: int, W: int, device) -> tuple:
+    """The cached device tensors that normalising [*, C, H, W] images by ``params`` reads (block
+    starts of the tile normalisation, ``lowhigh`` bounds), the very objects the caches hold now.
+    The caches evict; whoever records kernel arguments for later (a captured HIP graph) keeps this
+    tuple alive next to the recording."""
+    out = ()
+    if params.normalize and params.tile_blocksize > 0:
+        out += tuple(_tile_norm_grid(H, W, params.tile_blocksize, device)[:2])
+    if params.normalize and params.lowhigh is not None:
+        out += (_lowhigh_tensor(params.lowhigh, C, device),)
+    return out
+
+
+def _plain_percentile(params) -> bool:
+    """Whether ``params`` is the percentile rule alone, which the entry points from before the
+    options existed compute."""
+    return params.lowhigh is None and not params.invert and params.tile_blocksize == 0
+
+
+def normalize_img_gpu(x: torch.Tensor, params=None, c_use: int | None = None) -> torch.Tensor:
+    """:func:`reference.normalize_img` of every image of ``x`` [B, C, H, W] on the GPU -> float32
+    [B, c_use, H, W].  The default rule (and other percentiles alone) is :func:`normalize99`; fixed
+    bounds, inversion and tile normalisation run the unfused kernels that share their per-pixel
+    function with :meth:`TilePlan.gather_normalized`, so both give the same bits."""
+    from .pipeline import NormParams
+
+    params = NormParams() if params is None else params
+    C = x.shape[1]
+    c_use = C if c_use is None else min(int(c_use), C)
+    if not params.normalize:
+        return x[:, :c_use].float()
+    if _plain_percentile(params):
+        return normalize99(x[:, :c_use], params.lower, params.upper)
+    if x.device.type != "cuda":
+        return torch.stack([torch.from_numpy(ref.normalize_img(x[b, :c_use].numpy(), params)) for b in range(x.shape[0])])
+    if x.dtype not in RAW_DTYPES:
+        x = x.float()
+    x = x.contiguous()
+    B, C, H, W = x.shape
+    out = torch.empty(B, c_use, H, W, dtype=torch.float32, device=x.device)
+    sptr = _native.stream(x.device)
+    if params.tile_blocksize > 0:
+        lo, hi = tile_norm_maps_gpu(x, params.tile_blocksize, params.lower, params.upper, c_use)
+        _native.call("be_pct_normalize_tile", _native.ptr(x), RAW_DTYPES[x.dtype], B, C, c_use, H, W, _native.ptr(lo),
+                     _native.ptr(hi), lo.shape[2], lo.shape[3], int(params.invert), _native.ptr(out), sptr)
+        return out
+    lh = _lowhigh_tensor(params.lowhigh, c_use, x.device) if params.lowhigh is not None else None
+    ws = _pct_workspace(x.device, sptr, B * c_use)
+    _native.call("be_pct_normalize_ext", _native.ptr(x), RAW_DTYPES[x.dtype], B, C, c_use, H, W, float(params.lower),
+                 float(params.upper), _native.ptr(lh), int(params.invert), _native.ptr(out), _native.ptr(ws),
+                 ws.numel() // 4 * 4, sptr)
     return out
 
 
@@ -148,17 +300,39 @@ class TilePlan:
         return out
 
     def gather_normalized(self, x_raw: torch.Tensor, cpad: int, c_use: int | None = None, lower: float = 1.0,
-                          upper: float = 99.0) -> torch.Tensor:
+                          upper: float = 99.0, params=None) -> torch.Tensor:
         """``gather(normalize99(x_raw[:, :c_use].float(), lower, upper), cpad)`` bit for bit, from
         the raw pixels in one native call: ``x_raw`` is a contiguous [B, C, H, W] uint8, uint16 or
-        float32 device tensor (:func:`takes_fused_front`); channels from ``c_use`` on are ignored."""
+        float32 device tensor (:func:`takes_fused_front`); channels from ``c_use`` on are ignored.
+
+        ``params`` (a :class:`~.pipeline.NormParams`; ``None`` is exactly the call above): the
+        gather of ``normalize_img_gpu(x_raw, params, c_use)`` bit for bit.  Its percentiles replace
+        ``lower`` / ``upper``; fixed bounds skip the select, tile normalisation runs the block
+        select and the maps kernel first and the gather samples the maps per pixel."""
         B, C, H, W = x_raw.shape
         if x_raw.dtype not in RAW_DTYPES or not x_raw.is_contiguous():
             raise ValueError(f"gather_normalized takes a contiguous uint8, uint16 or float32 tensor, got {x_raw.dtype}")
         c_use = C if c_use is None else min(int(c_use), C)
+        if params is not None:
+            if not params.normalize:
+                raise ValueError("gather_normalized needs normalisation on; use gather() for the pixels as they are")
+            lower, upper = params.lower, params.upper
         out = torch.empty(B * self.nt, self.by, self.bx, cpad, dtype=torch.bfloat16, device=x_raw.device)
         sptr = _native.stream(x_raw.device)
+        tail = (self.pad_y, self.pad_x, _native.ptr(self.ys_t), _native.ptr(self.xs_t), len(self.ys), len(self.xs), self.by,
+                self.bx, cpad, _native.ptr(out))
+        if params is not None and params.tile_blocksize > 0:
+            lo, hi = tile_norm_maps_gpu(x_raw, params.tile_blocksize, lower, upper, c_use)
+            _native.call("be_tiles_gather_tilenorm" + self._sfx, _native.ptr(x_raw), RAW_DTYPES[x_raw.dtype], B, C, c_use, H, W,
+                         _native.ptr(lo), _native.ptr(hi), lo.shape[2], lo.shape[3], int(params.invert), *tail, sptr)
+            return out
         ws = _pct_workspace(x_raw.device, sptr, B * c_use)
+        if params is not None and not _plain_percentile(params):
+            lh = _lowhigh_tensor(params.lowhigh, c_use, x_raw.device) if params.lowhigh is not None else None
+            _native.call("be_tiles_gather_normx" + self._sfx, _native.ptr(x_raw), RAW_DTYPES[x_raw.dtype], B, C, c_use, H, W,
+                         float(lower), float(upper), _native.ptr(lh), int(params.invert), *tail, _native.ptr(ws),
+                         ws.numel() // 4 * 4, sptr)
+            return out
         _native.call("be_tiles_gather_norm" + self._sfx, _native.ptr(x_raw), RAW_DTYPES[x_raw.dtype], B, C, c_use, H, W, float(lower),
                      float(upper), self.pad_y, self.pad_x, _native.ptr(self.ys_t), _native.ptr(self.xs_t), len(self.ys),
                      len(self.xs), self.by, self.bx, cpad, _native.ptr(out), _native.ptr(ws), ws.numel() // 4 * 4, sptr)

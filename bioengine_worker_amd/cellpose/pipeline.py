@@ -26,6 +26,100 @@ from ..profiling import trace
 from . import reference as ref
 
 
+@dataclass(frozen=True)
+class NormParams:
+    """The canonical, hashable form of cellpose's ``normalize`` argument (:func:`norm_params`)."""
+    normalize: bool = True
+    lower: float = 1.0
+    upper: float = 99.0
+    #: fixed bounds instead of percentiles: ``(lo, hi)`` for every channel, or one pair per channel
+    lowhigh: tuple | None = None
+    invert: bool = False
+    #: local normalisation against percentiles of blocks of about this size (0 = whole image)
+    tile_blocksize: int = 0
+
+    @property
+    def is_default(self) -> bool:
+        return self == NormParams()
+
+
+#: cellpose ``models.normalize_default``, the dict a ``normalize`` dict is merged over
+NORMALIZE_DEFAULT = {"lowhigh": None, "percentile": None, "normalize": True, "norm3D": True, "sharpen_radius": 0,
+                     "smooth_radius": 0, "tile_norm_blocksize": 0, "tile_norm_smooth3D": 1, "invert": False}
+_UNSUPPORTED_NORM = {"sharpen_radius": 0, "smooth_radius": 0, "tile_norm_smooth3D": 1}
+
+
+def _num(v, what) -> float:
+    try:
+        return float(v)
+    except (TypeError, ValueError):
+        raise ValueError(f"normalize: {what} must be a number, got {v!r}") from None
+
+
+def _pair(v, what):
+    try:
+        lo, hi = (float(t) for t in v)
+    except (TypeError, ValueError):
+        raise ValueError(f"normalize: {what} must be a pair of numbers, got {v!r}") from None
+    return lo, hi
+
+
+def norm_options(value) -> tuple[NormParams, bool | None]:
+    """``normalize`` as cellpose takes it (bool, dict with cellpose's keys, or a :class:`NormParams`)
+    -> ``(NormParams, norm3D or None)``.  A dict is merged over :data:`NORMALIZE_DEFAULT`; ``norm3D``
+    comes back only when the dict names it.  Raises ``ValueError`` for unknown keys, for options
+    that are not supported here (``sharpen_radius``, ``smooth_radius``, ``tile_norm_smooth3D`` away
+    from their defaults), for bounds out of order, for ``tile_norm_blocksize`` together with
+    ``lowhigh`` and for ``invert`` without normalisation (cellpose skips the inversion silently)."""
+    if isinstance(value, NormParams):
+        return value, None
+    if value is None or isinstance(value, (bool, np.bool_)):
+        return NormParams(normalize=True if value is None else bool(value)), None
+    if not isinstance(value, dict):
+        raise ValueError(f"normalize must be a bool, a dict or NormParams, got {type(value).__name__}")
+    unknown = sorted(set(value) - set(NORMALIZE_DEFAULT))
+    if unknown:
+        raise ValueError(f"normalize: unknown key(s) {unknown}; known: {sorted(NORMALIZE_DEFAULT)}")
+    d = {**NORMALIZE_DEFAULT, **value}
+    for k, dv in _UNSUPPORTED_NORM.items():
+        if d[k] is not None and _num(d[k], k) != dv:
+            raise ValueError(f"normalize: {k}={d[k]!r} is not supported here (only its default {dv})")
+    lower, upper = (1.0, 99.0) if d["percentile"] is None else _pair(d["percentile"], "percentile")
+    if not 0.0 <= lower < upper <= 100.0:
+        raise ValueError(f"normalize: percentile needs 0 <= lower < upper <= 100, got {[lower, upper]}")
+    lowhigh = d["lowhigh"]
+    if lowhigh is not None:
+        lh = list(lowhigh)
+        if len(lh) and isinstance(lh[0], (list, tuple, np.ndarray)):
+            lowhigh = tuple(_pair(p, "lowhigh") for p in lh)
+            pairs = lowhigh
+        else:
+            lowhigh = _pair(lh, "lowhigh")
+            pairs = (lowhigh,)
+        for lo, hi in pairs:
+            if not hi - lo > 1e-3:
+                raise ValueError(f"normalize: lowhigh needs hi - lo > 1e-3, got {[lo, hi]}")
+    bs = d["tile_norm_blocksize"]
+    bs = 0.0 if bs is None else _num(bs, "tile_norm_blocksize")
+    if isinstance(d["tile_norm_blocksize"], (bool, np.bool_)) or not 0 <= bs < 2 ** 31:
+        raise ValueError(f"normalize: tile_norm_blocksize must be a finite number >= 0, got {d['tile_norm_blocksize']!r}")
+    bs = int(bs)
+    if bs > 0 and lowhigh is not None:
+        raise ValueError("normalize: tile_norm_blocksize and lowhigh exclude each other")
+    on = bool(d["normalize"])
+    if bool(d["invert"]) and not on:
+        raise ValueError("normalize: invert needs normalize=True (the inversion is 1 - x of the normalised image)")
+    if not on:
+        return NormParams(normalize=False), (bool(value["norm3D"]) if "norm3D" in value else None)
+    p = NormParams(True, lower, upper, lowhigh, bool(d["invert"]), bs)
+    return p, (bool(value["norm3D"]) if "norm3D" in value else None)
+
+
+def norm_params(value) -> NormParams:
+    """:func:`norm_options` without the ``norm3D`` switch."""
+    return norm_options(value)[0]
+
+
 @dataclass
 class EvalParams:
     diameter: float | None = None
@@ -34,7 +128,9 @@ class EvalParams:
     cellprob_threshold: float = 0.0
     min_size: int = 15
     max_size_fraction: float = 0.4
-    normalize: bool = True
+    #: cellpose ``normalize``: a bool, a dict with cellpose's keys or a :class:`NormParams`
+    #: (:func:`norm_options`); the runner's entry points replace it by its :class:`NormParams`
+    normalize: "bool | dict | NormParams" = True
     tile: bool = True
     bsize: int | None = None  # None: the network's native tile (224 CPnet, 256 Cellpose-SAM)
     tile_overlap: float = 0.1
@@ -60,6 +156,20 @@ class EvalParams:
     #: z spacing / xy spacing: the volume is resampled along z to round(Z * anisotropy) planes before
     #: the three views run (None or 1 = isotropic voxels)
     anisotropy: float | None = None
+
+
+def resolve_norm(p: EvalParams) -> EvalParams:
+    """Canonicalise ``p.normalize`` in place (and take ``norm3D`` of a dict into ``p.norm3d``)."""
+    if not isinstance(p.normalize, NormParams):
+        p.normalize, n3 = norm_options(p.normalize)
+        if n3 is not None:
+            p.norm3d = n3
+    return p
+
+
+def norm_on(p: EvalParams) -> bool:
+    """Whether ``p`` asks for normalisation, whichever form ``p.normalize`` has."""
+    return norm_params(p.normalize).normalize
 
 
 def as_batch(images, nchan: int, device=None, keep_raw: bool = False):
@@ -184,8 +294,9 @@ class CellposeRunner:
         """x: normalised [B, nchan, H, W] on device -> (y [B, 3, H, W] fp32, style [B, S]).
 
         ``raw`` (tiled GPU path only): ``x`` is the un-normalised batch in the form :meth:`_front`
-        passes on, and the tile gather normalises it (1st / 99th percentile) as it reads."""
+        passes on, and the tile gather normalises it (by ``p.normalize``) as it reads."""
         B, C, H, W = x.shape
+        norm = norm_params(p.normalize)
         if p.augment and not p.tile:
             raise ValueError("augment=True needs tile=True: the augmentation mirrors tiles")
         if raw and not (self.device.type == "cuda" and p.tile):
@@ -194,7 +305,8 @@ class CellposeRunner:
             if p.tile:
                 plan = self._plan(H, W, p)
                 with trace.span("cellpose.tiles_gather", cuda=True, tiles=B * plan.nt):
-                    tiles = plan.gather_normalized(x, self.cin_pad, self.nchan) if raw else plan.gather(x, self.cin_pad)
+                    tiles = (plan.gather_normalized(x, self.cin_pad, self.nchan, params=None if norm.is_default else norm)
+                             if raw else plan.gather(x, self.cin_pad))
                 with trace.span("cellpose.net", cuda=True, tiles=B * plan.nt):
                     if self.is_sam:
                         yt = self._sam_tiles(tiles)
@@ -255,6 +367,7 @@ class CellposeRunner:
         p = p or EvalParams()
         for k, v in kw.items():
             setattr(p, k, v)
+        resolve_norm(p)
         x, raw = as_batch(self._stage(images), self.nchan, self.device, keep_raw=True)
         B, C, H, W = x.shape
         nch = min(p.pipeline_chunks, B // max(1, p.pipeline_min_chunk))
@@ -275,6 +388,10 @@ class CellposeRunner:
         p = dataclasses.replace(p) if p is not None else EvalParams()
         for k, v in kw.items():
             setattr(p, k, v)
+        resolve_norm(p)
+        if norm_on(p) and p.norm3d and p.normalize.tile_blocksize > 0:
+            raise ValueError("tile_norm_blocksize over a whole stack (norm3D) is not supported: give norm3D=False "
+                             "to normalise every plane against its own block grid")
         x = torch.as_tensor(np.asarray(stack) if not torch.is_tensor(stack) else stack)
         if x.dim() == 3:
             x = x[:, None]
@@ -288,10 +405,10 @@ class CellposeRunner:
         if Z == 0:
             raise ValueError("eval_stack: empty stack")
         pp = dataclasses.replace(p)
-        if p.normalize and p.norm3d:
+        if norm_on(p) and p.norm3d:
             with trace.span("cellpose.normalize99", cuda=self.device.type == "cuda", images=Z):
                 xs = x.permute(1, 0, 2, 3).reshape(1, C, Z * H, W)
-                x = self._normalize(xs).reshape(C, Z, H, W).permute(1, 0, 2, 3).contiguous()
+                x = self._normalize(xs, p.normalize).reshape(C, Z, H, W).permute(1, 0, 2, 3).contiguous()
             pp.normalize = False
         masks, flows, styles = [], [], []
         step = max(1, int(p.stack_batch))
@@ -343,6 +460,9 @@ class CellposeRunner:
         p = dataclasses.replace(p) if p is not None else EvalParams()
         for k, v in kw.items():
             setattr(p, k, v)
+        resolve_norm(p)
+        if norm_on(p) and p.normalize.tile_blocksize > 0:
+            raise ValueError("tile_norm_blocksize is not supported by eval_3d: the volume is normalised once over all voxels")
         x = torch.as_tensor(np.asarray(volume) if not torch.is_tensor(volume) else volume)
         if x.dim() == 3:
             x = x[:, None]
@@ -366,10 +486,10 @@ class CellposeRunner:
             from . import gpu
 
             gpu._check_volume(Zr, H, W)
-        if p.normalize:
+        if norm_on(p):
             with trace.span("cellpose.normalize99", cuda=on_gpu, images=Z):
                 xs = x.permute(1, 0, 2, 3).reshape(1, C, Z * H, W)
-                x = self._normalize(xs).reshape(C, Z, H, W).permute(1, 0, 2, 3).contiguous()
+                x = self._normalize(xs, p.normalize).reshape(C, Z, H, W).permute(1, 0, 2, 3).contiguous()
         if Zr != Z:
             x = F.interpolate(x.permute(1, 0, 2, 3)[None], size=(Zr, H, W), mode="trilinear",
                               align_corners=False)[0].permute(1, 0, 2, 3).contiguous()
@@ -441,18 +561,27 @@ class CellposeRunner:
         B = x.shape[0]
         if self.device.type != "cuda" or B > self.GRAPH_NET_MAX_B or not x.is_cuda:
             return None
-        key = (tuple(x.shape), x.dtype, bool(p.normalize), bool(p.tile), p.bsize, p.tile_overlap, p.max_tiles,
+        key = (tuple(x.shape), x.dtype, norm_params(p.normalize), bool(p.tile), p.bsize, p.tile_overlap, p.max_tiles,
                bool(p.augment))
         ent = self._net_graphs.get(key)
         if ent is False:
             return None
         if ent is None:
+            from .gpu import norm_constants
+
             xs = x.clone()
+            # The cached device constants of the options (block starts, lowhigh bounds): the capture
+            # bakes their addresses into the graph, and the caches they come from evict, so the
+            # entry holds them for as long as the graph lives.
+            def consts():
+                return norm_constants(norm_params(p.normalize), x.shape[1], x.shape[2], x.shape[3], x.device)
+
+            keep = consts()
             side = torch.cuda.Stream(self.device)
             side.wait_stream(torch.cuda.current_stream(self.device))
 
             def body():
-                xx = self._normalize(xs) if p.normalize else xs
+                xx = self._normalize(xs, p.normalize) if norm_on(p) else xs
                 return self.run_net(xx, p)
 
             try:
@@ -462,11 +591,13 @@ class CellposeRunner:
                 g = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g, capture_error_mode="thread_local"):
                     y, style = body()
+                if not all(a is b for a, b in zip(keep, consts())):
+                    raise RuntimeError("an option constant was evicted and rebuilt while the graph was captured")
             except Exception:  # noqa: BLE001 -- this shape runs eagerly
                 self._net_graphs[key] = False
                 return None
-            ent = self._net_graphs[key] = (g, xs, y, style)
-        g, xs, y, style = ent
+            ent = self._net_graphs[key] = (g, xs, y, style, keep)
+        g, xs, y, style = ent[:4]
         xs.copy_(x)
         g.replay()
         return y.clone(), style.clone()
@@ -475,15 +606,16 @@ class CellposeRunner:
         """Decide the front end of one network stage for a batch that :func:`as_batch` kept ``raw``
         (own dtype, all channels).  Returns ``(x, raw)``: still raw, ``x`` goes to ``run_net(...,
         raw=True)``, whose gather takes the percentiles on the raw pixels and normalises as it reads
-        (:meth:`gpu.TilePlan.gather_normalized`).  That needs the tiled GPU path with normalisation
-        on, no diameter rescale (the resize reads the normalised image) and no HIP-graph replay;
-        otherwise ``x`` comes back as float32 [B, nchan, H, W] for the unfused sequence."""
+        (:meth:`gpu.TilePlan.gather_normalized`; every :class:`NormParams` with normalisation on
+        takes it).  That needs the tiled GPU path with normalisation on, no diameter rescale (the
+        resize reads the normalised image) and no HIP-graph replay; otherwise ``x`` comes back as
+        float32 [B, nchan, H, W] for the unfused sequence."""
         if not raw:
             return x, False
         from .gpu import takes_fused_front
 
         rescaled = p.diameter is not None and p.diameter > 0 and abs(self.diam_mean / float(p.diameter) - 1.0) > 1e-3
-        if (self.device.type == "cuda" and p.normalize and p.tile and not rescaled and x.shape[0] > self.GRAPH_NET_MAX_B
+        if (self.device.type == "cuda" and norm_on(p) and p.tile and not rescaled and x.shape[0] > self.GRAPH_NET_MAX_B
                 and takes_fused_front(x)):
             return x, True
         return x.float()[:, : self.nchan], False
@@ -500,9 +632,9 @@ class CellposeRunner:
                 with trace.span("cellpose.masks", cuda=True, images=B):
                     masks = self.compute_masks(y, p, 1.0)
                 return masks, y, style
-        if p.normalize and not raw:
+        if norm_on(p) and not raw:
             with trace.span("cellpose.normalize99", cuda=True, images=B):
-                x = self._normalize(x)
+                x = self._normalize(x, p.normalize)
         rescale = 1.0
         if p.diameter is not None and p.diameter > 0:
             rescale = self.diam_mean / float(p.diameter)
@@ -526,9 +658,9 @@ class CellposeRunner:
             r = self._net_graphed(x, p)
             if r is not None:
                 return r[0], r[1], 1.0
-        if p.normalize and not raw:
+        if norm_on(p) and not raw:
             with trace.span("cellpose.normalize99", cuda=True, images=B):
-                x = self._normalize(x)
+                x = self._normalize(x, p.normalize)
         rescale = 1.0
         if p.diameter is not None and p.diameter > 0:
             rescale = self.diam_mean / float(p.diameter)
@@ -588,6 +720,7 @@ class CellposeRunner:
         p = p or EvalParams()
         for k, v in kw.items():
             setattr(p, k, v)
+        resolve_norm(p)
         if self.device.type != "cuda" or not p.compute_masks:
             with net_lock:
                 m, y, st = self.eval(images, p)
@@ -624,12 +757,16 @@ class CellposeRunner:
         ``flush()`` returns the last batch's.  Same per-batch results as :meth:`eval`."""
         return _EvalStream(self, p or EvalParams())
 
-    def _normalize(self, x):
+    def _normalize(self, x, norm=True):
+        """``x`` [B, C, H, W] normalised per image by ``norm`` (anything :func:`norm_params` takes)."""
+        norm = norm_params(norm)
         if self.device.type == "cuda":
-            from .gpu import normalize99
+            from .gpu import normalize99, normalize_img_gpu
 
-            return normalize99(x)
-        return torch.stack([torch.from_numpy(ref.normalize99(x[b].numpy())) for b in range(x.shape[0])])
+            return normalize99(x) if norm.is_default else normalize_img_gpu(x, norm)
+        if norm.is_default:
+            return torch.stack([torch.from_numpy(ref.normalize99(x[b].numpy())) for b in range(x.shape[0])])
+        return torch.stack([torch.from_numpy(ref.normalize_img(x[b].numpy(), norm)) for b in range(x.shape[0])])
 
     def compute_masks(self, y: torch.Tensor, p: EvalParams, rescale: float = 1.0) -> torch.Tensor:
         niter = p.niter if p.niter else int(200 / max(rescale, 1e-3))
@@ -821,7 +958,7 @@ class _EvalStream:
     """See :meth:`CellposeRunner.stream` (GPU only; a CPU runner evaluates each batch directly)."""
 
     def __init__(self, runner: CellposeRunner, p: EvalParams):
-        self.r, self.p = runner, p
+        self.r, self.p = runner, resolve_norm(p)
         self.pending = None
         self.cuda = runner.device.type == "cuda" and p.compute_masks
         if self.cuda:

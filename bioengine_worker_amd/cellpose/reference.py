@@ -9,6 +9,12 @@ semantics; this module is what their tests compare against.
 Stages
 ------
 normalize99      per-channel 1st/99th percentile scaling (linear-interpolated percentiles)
+normalize_img    the options of cellpose's ``normalize`` dict (written from memory of cellpose 3's
+                 ``transforms.normalize_img`` / ``normalize99_tile``; not compared with the library):
+                 other percentiles, fixed ``lowhigh`` bounds, ``invert`` (1 - x), and tile normalisation:
+                 tile_norm_raw_maps (percentiles of blocks overlapping by ~20 %) -> tile_norm_fill
+                 (degenerate blocks take the nearest valid block) -> tile_norm_smooth (Gaussian, sigma 1)
+                 -> normalize99_tile (maps enlarged bilinearly, (x - X01) / (X99 - X01) per pixel)
 make_tiles       224x224 tiles with 10 % overlap over an image padded to a multiple of 16 (+8 margin)
 average_tiles    tapered-mask weighted blend of tile outputs
 augment          test-time augmentation (cellpose ``augment=True``, written from memory of cellpose 3's
@@ -65,6 +71,116 @@ def tile_starts(L: int, bsize: int = 224, overlap: float = 0.1) -> list[int]:
     b = min(bsize, L)
     n = 1 if L <= bsize else int(math.ceil((1.0 + 2 * overlap) * L / bsize))
     return [int(v) for v in np.linspace(0, L - b, n).astype(int)]
+
+
+def tile_norm_blocks(L: int, blocksize: int) -> tuple[list[int], int]:
+    """Blocks of the tile normalisation along one axis: ``(starts, b)``, by the rule of
+    ``tile_starts(L, blocksize, 0.1)`` (blocks of ``b = min(blocksize, L)`` overlapping by ~20 %)."""
+    return tile_starts(int(L), int(blocksize), 0.1), min(int(blocksize), int(L))
+
+
+def tile_norm_raw_maps(img: np.ndarray, blocksize: int, lower: float = 1.0, upper: float = 99.0, dtype=np.float32):
+    """Per-block percentiles of ``img`` [C, H, W]: ``(x01, x99)``, each [C, ny, nx] float32
+    (``np.percentile`` with linear interpolation on the block's pixels as float32).  ``dtype``
+    (here and in the stages below): float64 runs the same rules in double precision, the yardstick
+    the tests measure the float32 rounding of these stages with."""
+    C, H, W = img.shape
+    ys, bh = tile_norm_blocks(H, blocksize)
+    xs, bw = tile_norm_blocks(W, blocksize)
+    x01 = np.zeros((C, len(ys), len(xs)), dtype)
+    x99 = np.zeros_like(x01)
+    for c in range(C):
+        for j, y0 in enumerate(ys):
+            for i, x0 in enumerate(xs):
+                blk = img[c, y0: y0 + bh, x0: x0 + bw].astype(dtype)
+                x01[c, j, i], x99[c, j, i] = np.percentile(blk, lower), np.percentile(blk, upper)
+    return x01, x99
+
+
+def tile_norm_fill(x01: np.ndarray, x99: np.ndarray):
+    """Degenerate blocks (``x99 - x01 < 1e-3``) take both values of the nearest non-degenerate block
+    of their channel (squared distance in grid indices, the raster-first block on ties, as ``argmin``
+    gives); a channel without any valid block gets ``x01 = 0``, ``x99 = 1``.  Returns copies."""
+    x01, x99 = np.array(x01, copy=True), np.array(x99, copy=True)
+    C, ny, nx = x01.shape
+    gy, gx = np.mgrid[0:ny, 0:nx]
+    for c in range(C):
+        bad = (x99[c] - x01[c]) < np.asarray(1e-3, x01.dtype)
+        if bad.all():
+            x01[c], x99[c] = 0.0, 1.0
+            continue
+        vy, vx = gy[~bad], gx[~bad]  # raster order
+        for j, i in zip(gy[bad], gx[bad]):
+            k = int(np.argmin((vy - j) ** 2 + (vx - i) ** 2))
+            x01[c, j, i], x99[c, j, i] = x01[c, vy[k], vx[k]], x99[c, vy[k], vx[k]]
+    return x01, x99
+
+
+def tile_norm_smooth(m: np.ndarray) -> np.ndarray:
+    """Gaussian (sigma 1, scipy's reflect boundary and truncate 4: nine taps) along the grid's y
+    axis, then along its x axis; the result keeps ``m``'s dtype."""
+    return ndimage.gaussian_filter1d(ndimage.gaussian_filter1d(m, 1.0, axis=-2), 1.0, axis=-1)
+
+
+def tile_norm_maps(img: np.ndarray, blocksize: int, lower: float = 1.0, upper: float = 99.0, dtype=np.float32):
+    """Local percentile maps of ``img`` [C, H, W] (cellpose ``tile_norm_blocksize``): block
+    percentiles -> degenerate-block fill -> smoothing.  ``(x01, x99)``, each [C, ny, nx] float32.
+    Written from memory of cellpose 3's ``normalize99_tile``; not compared with the library."""
+    x01, x99 = tile_norm_fill(*tile_norm_raw_maps(img, blocksize, lower, upper, dtype))
+    return tile_norm_smooth(x01), tile_norm_smooth(x99)
+
+
+def _map_axis(n: int, L: int, dtype=np.float32):
+    """Bilinear source coordinates of an ``n``-cell map axis enlarged to ``L``: half-pixel centres,
+    clamped (``F.interpolate(align_corners=False)``): cells ``i0``, ``i1`` and the weight of ``i1``."""
+    s = (np.arange(L, dtype=dtype) + dtype(0.5)) * dtype(n / L) - dtype(0.5)
+    s = np.clip(s, dtype(0), dtype(n - 1))
+    i0 = s.astype(np.int64)
+    return i0, np.minimum(i0 + 1, n - 1), (s - i0.astype(dtype)).astype(dtype)
+
+
+def enlarge_map(m: np.ndarray, H: int, W: int) -> np.ndarray:
+    """[C, ny, nx] -> [C, H, W] bilinearly (:func:`_map_axis` along x, then along y), in ``m``'s dtype."""
+    dt = m.dtype.type
+    y0, y1, wy = _map_axis(m.shape[1], H, dt)
+    x0, x1, wx = _map_axis(m.shape[2], W, dt)
+    rows = m[:, :, x0] + wx * (m[:, :, x1] - m[:, :, x0])  # [C, ny, W]
+    top, bot = rows[:, y0], rows[:, y1]
+    return top + wy[None, :, None] * (bot - top)
+
+
+def normalize99_tile(img: np.ndarray, blocksize: int, lower: float = 1.0, upper: float = 99.0, dtype=np.float32) -> np.ndarray:
+    """img [C, H, W] -> float32, every pixel scaled between the local percentile maps of
+    :func:`tile_norm_maps` enlarged to the image: ``(x - X01) / (X99 - X01)``.  The fill and the
+    positive smoothing weights keep the denominator at about 1e-3 or more wherever a channel has a
+    valid block; it is 1 where it has none."""
+    C, H, W = img.shape
+    x01, x99 = tile_norm_maps(img, blocksize, lower, upper, dtype)
+    X01, X99 = enlarge_map(x01, H, W), enlarge_map(x99, H, W)
+    return ((img.astype(dtype) - X01) / (X99 - X01)).astype(dtype)
+
+
+def normalize_img(img: np.ndarray, params) -> np.ndarray:
+    """img [C, H, W] -> float32 under the normalisation options ``params`` (a
+    :class:`~bioengine_worker_amd.cellpose.pipeline.NormParams`; cellpose ``transforms.normalize_img``,
+    written from memory of cellpose 3 and not compared with the library): fixed ``lowhigh`` bounds
+    per channel, or tile normalisation, or :func:`normalize99` between the ``lower`` / ``upper``
+    percentiles; ``invert`` maps the result to ``1 - x``.  ``normalize=False`` converts only."""
+    x = np.asarray(img)
+    if not params.normalize:
+        return x.astype(np.float32)
+    if params.lowhigh is not None:
+        lh = params.lowhigh
+        pairs = [lh] * x.shape[0] if np.isscalar(lh[0]) else list(lh)
+        if len(pairs) < x.shape[0]:
+            raise ValueError(f"lowhigh has {len(pairs)} pairs for {x.shape[0]} channels")
+        out = np.stack([(x[c].astype(np.float32) - np.float32(lo)) / (np.float32(hi) - np.float32(lo))
+                        for c, (lo, hi) in zip(range(x.shape[0]), pairs)])
+    elif params.tile_blocksize > 0:
+        out = normalize99_tile(x, params.tile_blocksize, params.lower, params.upper)
+    else:
+        out = normalize99(x, params.lower, params.upper)
+    return (1.0 - out).astype(np.float32) if params.invert else out.astype(np.float32)
 
 
 def taper_mask(ly: int = 224, lx: int = 224, sig: float = 7.5) -> np.ndarray:

@@ -117,14 +117,26 @@ def load_pairs(pairs: list[dict], nchan: int, enable_clahe: bool = False, device
     return imgs, labs
 
 
-def _prep(imgs, labs, device):
-    """normalize99 per image (cellpose ``normalize_img``) + labels -> [instances, flowY, flowX] on device."""
-    from ..cellpose.reference import normalize99
+def _prep(imgs, labs, device, normalize=True):
+    """Images normalised one by one (cellpose ``normalize_img`` with the session's ``normalize``: a
+    bool or a dict with cellpose's keys) + labels -> [instances, flowY, flowX] on device.  On a GPU
+    the image is copied over as it is and normalised there (:func:`~..cellpose.gpu.normalize_img_gpu`);
+    on the CPU the numpy oracle does it."""
+    from ..cellpose.pipeline import norm_params
+    from ..cellpose.reference import normalize_img
     from .cellpose_train import labels_to_flows
 
+    norm = norm_params(normalize)
+    on_gpu = torch.device(device).type == "cuda"
+    if on_gpu:
+        from ..cellpose.gpu import normalize_img_gpu
     xs, ys = [], []
     for im, lab in zip(imgs, labs):
-        xs.append(torch.from_numpy(normalize99(im)).float().to(device))
+        if on_gpu:
+            a = np.ascontiguousarray(im if im.dtype in (np.uint8, np.uint16, np.float32) else im.astype(np.float32))
+            xs.append(normalize_img_gpu(torch.from_numpy(a)[None].to(device), norm)[0])
+        else:
+            xs.append(torch.from_numpy(normalize_img(im, norm)).float().to(device))
         ys.append(labels_to_flows(torch.from_numpy(lab.astype(np.int32))[None].to(device))[0])
     return xs, ys
 
@@ -155,8 +167,9 @@ def train_session(session_dir: str | Path, params: dict, device=None, rank: int 
             raise ValueError(f"no training image has at least min_train_masks={mtm} masks")
         imgs, labs = [imgs[i] for i in keep], [labs[i] for i in keep]
         diams = [cell_diameter(l) for l in labs]
-        tx, tl = _prep(imgs, labs, dev)
-        vx, vl = _prep(timgs, tlabs, dev) if timgs else (None, None)
+        normalize = params.get("normalize", True)
+        tx, tl = _prep(imgs, labs, dev, normalize)
+        vx, vl = _prep(timgs, tlabs, dev, normalize) if timgs else (None, None)
         with torch.no_grad():
             net.diam_labels.fill_(float(np.mean(diams)) if diams else 30.0)
         bsize = int(getattr(net, "bsize", 0) or params.get("bsize", 256))
@@ -231,7 +244,7 @@ def train_session(session_dir: str | Path, params: dict, device=None, rank: int 
         if timgs:
             write_status(sdir, message="Computing instance metrics on the test images")
             try:
-                write_status(sdir, instance_metrics=instance_metrics(trainer.net, timgs, tlabs, dev))
+                write_status(sdir, instance_metrics=instance_metrics(trainer.net, timgs, tlabs, dev, normalize))
             except Exception as e:  # noqa: BLE001 -- metrics are best effort, as in the reference
                 log.warning("instance metrics failed: %s", e)
         log_info(sdir, f"completed in {time.time() - t_start:.1f} s")
@@ -325,7 +338,7 @@ def train_session_rank(rank: int, world: int, session_dir: str, params: dict, cp
     return {"rank": rank, "weights_sha256": st.get("weights_sha256"), "status_type": st.get("status_type")}
 
 
-def instance_metrics(net, test_imgs, test_labs, device) -> dict:
+def instance_metrics(net, test_imgs, test_labs, device, normalize=True) -> dict:
     """Full Cellpose eval of the fine-tuned net on every test image, then AP at IoU 0.5/0.75/0.9
     (reference main.py:1977-2029).  Images are segmented one at a time (the kernel choice depends on
     the batch size, so the masks stay what they were); on a GPU the masks stay there and are scored
@@ -337,7 +350,7 @@ def instance_metrics(net, test_imgs, test_labs, device) -> dict:
     on_gpu = runner.device.type == "cuda"
     preds = []
     for img in test_imgs:
-        masks, _, _ = runner.eval(np.asarray(img)[None])
+        masks, _, _ = runner.eval(np.asarray(img)[None], normalize=normalize)
         preds.append(masks[0] if on_gpu else masks[0].cpu().numpy())
     labs = [np.asarray(l, np.int32) for l in test_labs]
     if on_gpu:

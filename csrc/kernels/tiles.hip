@@ -39,12 +39,15 @@ constexpr int kMaxGridYZ = 65535;
 // reversed when tj is odd and its columns reversed when ti is odd, i.e. tile row ty holds image row
 // ys[ti] + (by - 1 - ty).  Both flags are per block, the stores stay ascending; only the load index
 // runs backwards.
-template <typename T, bool NORM, bool AUG = false>
+// XM (the options of be_pct::NormExt, percentile.h): 1 = the global rules with fixed bounds and / or
+// inversion, 2 = tile normalisation against the sampled maps; 0 compiles exactly the kernels above.
+template <typename T, bool NORM, bool AUG = false, int XM = 0>
 __global__ __launch_bounds__(256) void tiles_gather_kernel(const T* __restrict__ img, int tile0, int C_src, int C_use, int H,
                                                            int W, int pad_y, int pad_x, const int* __restrict__ ys,
                                                            const int* __restrict__ xs, int nty, int ntx, int by, int bx,
                                                            int cpad, const be_pct::Coef cf,
-                                                           const uint32_t* __restrict__ state, bf16_t* __restrict__ out) {
+                                                           const uint32_t* __restrict__ state, bf16_t* __restrict__ out,
+                                                           const be_pct::NormExt ext) {
   const int ngrp = cpad >> 3;
   const int q = blockIdx.x * 256 + threadIdx.x;
   const int tx = ngrp == 1 ? q : q / ngrp;
@@ -65,20 +68,35 @@ __global__ __launch_bounds__(256) void tiles_gather_kernel(const T* __restrict__
   for (int r = 0; r < kRows; ++r)
 #pragma unroll
     for (int j = 0; j < 8; ++j) f[r][j] = 0.f;
+  int mx0 = 0, mx1 = 0;
+  float mwx = 0.f;
+  if (XM == 2 && inx) be_pct::map_coord(xx, ext.sx, ext.nx, mx0, mx1, mwx);
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
     const int c = 8 * g + j;
     if (c < C_use) {
       float p1 = 0.f, scale = 1.f;
       bool cst = false;
-      if (NORM) be_pct::row_consts<T>(state + ((size_t)b * C_use + c) * be_pct::kT * 2, cf, p1, scale, cst);
+      if (NORM && XM == 0) be_pct::row_consts<T>(state + ((size_t)b * C_use + c) * be_pct::kT * 2, cf, p1, scale, cst);
+      if (XM == 1)
+        be_pct::ext_consts<T>(ext, ext.lowhigh ? nullptr : state + ((size_t)b * C_use + c) * be_pct::kT * 2, cf, c, p1, scale, cst);
+      const size_t mo = XM == 2 ? ((size_t)b * C_use + c) * ext.ny * ext.nx : 0;
       const T* plane = img + ((size_t)b * C_src + c) * H * W;
 #pragma unroll
       for (int r = 0; r < kRows; ++r) {
         const int yy = fy ? yy0 - r : yy0 + r;
         if (inx && yy >= 0 && yy < H && ty0 + r < by) {
           const float v = (float)plane[(size_t)yy * W + xx];
-          f[r][j] = NORM ? (cst ? 0.f : (v - p1) * scale) : v;
+          if (XM == 2) {
+            int my0, my1;
+            float mwy;
+            be_pct::map_coord(yy, ext.sy, ext.ny, my0, my1, mwy);
+            f[r][j] = be_pct::tile_norm(v, ext.lo_map + mo, ext.hi_map + mo, ext.nx, my0, my1, mwy, mx0, mx1, mwx, ext.invert != 0);
+          } else if (XM == 1) {
+            f[r][j] = be_pct::norm_div(v, p1, scale, cst, ext.invert != 0);  // scale holds the denominator here
+          } else {
+            f[r][j] = NORM ? (cst ? 0.f : (v - p1) * scale) : v;
+          }
         }
       }
     }
@@ -94,16 +112,16 @@ __global__ __launch_bounds__(256) void tiles_gather_kernel(const T* __restrict__
   }
 }
 
-template <typename T, bool NORM, bool AUG = false>
+template <typename T, bool NORM, bool AUG = false, int XM = 0>
 int gather_launch(const void* img, int B, int C_src, int C_use, int H, int W, int pad_y, int pad_x, const int* ys,
                   const int* xs, int nty, int ntx, int by, int bx, int cpad, be_pct::Coef cf, const uint32_t* state,
-                  void* out, hipStream_t s) {
+                  void* out, hipStream_t s, const be_pct::NormExt ext = be_pct::NormExt{}) {
   const long long tiles = (long long)B * nty * ntx;
   const unsigned gx = (unsigned)(((long long)bx * (cpad >> 3) + 255) / 256), gy = (unsigned)((by + kRows - 1) / kRows);
   for (long long t0 = 0; t0 < tiles; t0 += kMaxGridYZ) {  // one launch unless a call has more tiles than grid.z holds
     const unsigned gz = (unsigned)(tiles - t0 < kMaxGridYZ ? tiles - t0 : kMaxGridYZ);
-    hipLaunchKernelGGL((tiles_gather_kernel<T, NORM, AUG>), dim3(gx, gy, gz), dim3(256), 0, s, static_cast<const T*>(img), (int)t0,
-                       C_src, C_use, H, W, pad_y, pad_x, ys, xs, nty, ntx, by, bx, cpad, cf, state, (bf16_t*)out);
+    hipLaunchKernelGGL((tiles_gather_kernel<T, NORM, AUG, XM>), dim3(gx, gy, gz), dim3(256), 0, s, static_cast<const T*>(img),
+                       (int)t0, C_src, C_use, H, W, pad_y, pad_x, ys, xs, nty, ntx, by, bx, cpad, cf, state, (bf16_t*)out, ext);
   }
   return BE_CHECK_LAUNCH();
 }
@@ -152,6 +170,55 @@ __global__ __launch_bounds__(256) void tiles_blend_kernel(const float* __restric
   }
   const float inv = wsum > 0.f ? 1.f / wsum : 0.f;
   for (int c = 0; c < nout && c < 4; ++c) out[(((size_t)b * nout + c) * H + y) * W + x] = acc[c] * inv;
+}
+
+// the element type and the mirroring of one extended gather (XM = 1, 2) -> its instantiation
+template <int XM>
+int gather_ext(bool aug, const void* x, int dtype, int B, int C_src, int C_use, int H, int W, int pad_y, int pad_x,
+               const int* ys, const int* xs, int nty, int ntx, int by, int bx, int cpad, be_pct::Coef cf, const uint32_t* state,
+               void* out, hipStream_t s, const be_pct::NormExt& ext) {
+#define BE_GATHER_EXT(T, A) \
+  gather_launch<T, true, A, XM>(x, B, C_src, C_use, H, W, pad_y, pad_x, ys, xs, nty, ntx, by, bx, cpad, cf, state, out, s, ext)
+  if (dtype == be_pct::kF32) return aug ? BE_GATHER_EXT(float, true) : BE_GATHER_EXT(float, false);
+  if (dtype == be_pct::kU16) return aug ? BE_GATHER_EXT(uint16_t, true) : BE_GATHER_EXT(uint16_t, false);
+  if (dtype == be_pct::kU8) return aug ? BE_GATHER_EXT(uint8_t, true) : BE_GATHER_EXT(uint8_t, false);
+#undef BE_GATHER_EXT
+  return -3;
+}
+
+int gather_normx(bool aug, const void* x, int dtype, int B, int C_src, int C_use, int H, int W, float lower, float upper,
+                 const float* lowhigh, int invert, int pad_y, int pad_x, const int* ys, const int* xs, int nty, int ntx, int by,
+                 int bx, int cpad, void* out, void* ws, long long ws_bytes, hipStream_t s) {
+  if (!gather_args_ok(B, C_src, H, W, nty, ntx, by, bx, cpad) || C_use <= 0 || C_use > C_src) return -1;
+  if (dtype != be_pct::kF32 && dtype != be_pct::kU16 && dtype != be_pct::kU8) return -3;
+  be_pct::NormExt ext;
+  ext.lowhigh = lowhigh;
+  ext.invert = invert;
+  be_pct::Coef cf{};
+  const uint32_t* state = nullptr;
+  if (!lowhigh) {
+    const int rc = be_pct::select_run(x, dtype, B, C_src, C_use, (long long)H * W, lower, upper, ws, ws_bytes, s, &cf, &state);
+    if (rc) return rc;
+  }
+  return gather_ext<1>(aug, x, dtype, B, C_src, C_use, H, W, pad_y, pad_x, ys, xs, nty, ntx, by, bx, cpad, cf, state, out, s, ext);
+}
+
+int gather_tilenorm(bool aug, const void* x, int dtype, int B, int C_src, int C_use, int H, int W, const float* lo_map,
+                    const float* hi_map, int ny, int nx, int invert, int pad_y, int pad_x, const int* ys, const int* xs, int nty,
+                    int ntx, int by, int bx, int cpad, void* out, hipStream_t s) {
+  if (!gather_args_ok(B, C_src, H, W, nty, ntx, by, bx, cpad) || C_use <= 0 || C_use > C_src || !lo_map || !hi_map || ny <= 0 ||
+      nx <= 0 || (long long)ny * nx > be_pct::kMaxCells)
+    return -1;
+  be_pct::NormExt ext;
+  ext.lo_map = lo_map;
+  ext.hi_map = hi_map;
+  ext.ny = ny;
+  ext.nx = nx;
+  ext.sy = (float)((double)ny / H);
+  ext.sx = (float)((double)nx / W);
+  ext.invert = invert;
+  return gather_ext<2>(aug, x, dtype, B, C_src, C_use, H, W, pad_y, pad_x, ys, xs, nty, ntx, by, bx, cpad, be_pct::Coef{}, nullptr,
+                       out, s, ext);
 }
 
 }  // namespace
@@ -227,6 +294,39 @@ int be_tiles_blend_aug(const float* yt, int B, int nout, int H, int W, int pad_y
   hipLaunchKernelGGL(tiles_blend_kernel<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, yt, B, nout, H, W, pad_y,
                      pad_x, ys, xs, nty, ntx, by, bx, wy, wx, out);
   return BE_CHECK_LAUNCH();
+}
+
+// ---- the options of the cellpose `normalize` dict in the gather (be_pct::NormExt): the global rules
+// with fixed bounds `lowhigh` ([C_use][2] on the device, no select runs; null: the percentiles) and /
+// or inversion, and tile normalisation against the maps of be_pct_tile_maps.  Each pixel is what
+// be_pct_normalize_ext / be_pct_normalize_tile give, rounded to bf16.
+
+int be_tiles_gather_normx(const void* x, int dtype, int B, int C_src, int C_use, int H, int W, float lower, float upper,
+                          const float* lowhigh, int invert, int pad_y, int pad_x, const int* ys, const int* xs, int nty, int ntx,
+                          int by, int bx, int cpad, void* out, void* ws, long long ws_bytes, hipStream_t s) {
+  return gather_normx(false, x, dtype, B, C_src, C_use, H, W, lower, upper, lowhigh, invert, pad_y, pad_x, ys, xs, nty, ntx, by, bx,
+                      cpad, out, ws, ws_bytes, s);
+}
+
+int be_tiles_gather_normx_aug(const void* x, int dtype, int B, int C_src, int C_use, int H, int W, float lower, float upper,
+                              const float* lowhigh, int invert, int pad_y, int pad_x, const int* ys, const int* xs, int nty,
+                              int ntx, int by, int bx, int cpad, void* out, void* ws, long long ws_bytes, hipStream_t s) {
+  return gather_normx(true, x, dtype, B, C_src, C_use, H, W, lower, upper, lowhigh, invert, pad_y, pad_x, ys, xs, nty, ntx, by, bx,
+                      cpad, out, ws, ws_bytes, s);
+}
+
+int be_tiles_gather_tilenorm(const void* x, int dtype, int B, int C_src, int C_use, int H, int W, const float* lo_map,
+                             const float* hi_map, int ny, int nx, int invert, int pad_y, int pad_x, const int* ys, const int* xs,
+                             int nty, int ntx, int by, int bx, int cpad, void* out, hipStream_t s) {
+  return gather_tilenorm(false, x, dtype, B, C_src, C_use, H, W, lo_map, hi_map, ny, nx, invert, pad_y, pad_x, ys, xs, nty, ntx, by,
+                         bx, cpad, out, s);
+}
+
+int be_tiles_gather_tilenorm_aug(const void* x, int dtype, int B, int C_src, int C_use, int H, int W, const float* lo_map,
+                                 const float* hi_map, int ny, int nx, int invert, int pad_y, int pad_x, const int* ys,
+                                 const int* xs, int nty, int ntx, int by, int bx, int cpad, void* out, hipStream_t s) {
+  return gather_tilenorm(true, x, dtype, B, C_src, C_use, H, W, lo_map, hi_map, ny, nx, invert, pad_y, pad_x, ys, xs, nty, ntx, by,
+                         bx, cpad, out, s);
 }
 
 }  // extern "C"
