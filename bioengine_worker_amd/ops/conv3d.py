@@ -153,6 +153,7 @@ def fused_conv3d_concat(xa: torch.Tensor, xb: torch.Tensor, pc: PackedConv3d, po
     zt = pc.ztap
     assert xa.dtype == xb.dtype == torch.bfloat16 and xa.is_contiguous() and xb.is_contiguous()
     assert Ca % 8 == 0 and Cb % 8 == 0 and (Ca + Cb) % zt.ck == 0 and pc.cout % 4 == 0
+    assert zt.ck in (8, 32), "the concat build has 8- and 32-channel K chunks (ask concat3d_fusible first)"
     out = torch.empty(N, D, H, W, pc.cout, device=xa.device, dtype=torch.bfloat16)
     _native.call("be_conv3d_ztaps_concat", _native.ptr(xa), _native.ptr(xb), _native.ptr(zt.wp), _native.ptr(zt.bias),
                  _native.ptr(out), N, D, H, W, Ca, Cb, pc.cout, zt.ck, zt.tco, int(post_relu), 4,
@@ -161,8 +162,11 @@ def fused_conv3d_concat(xa: torch.Tensor, xb: torch.Tensor, pc: PackedConv3d, po
 
 
 def concat3d_fusible(pc: PackedConv3d, ca: int, cb: int) -> bool:
-    """Whether :func:`fused_conv3d_concat` takes this conv over a [ca | cb]-channel concatenation."""
+    """Whether :func:`fused_conv3d_concat` takes this conv over a [ca | cb]-channel concatenation
+    (``be_conv3d_ztaps_concat`` is built for 8- and 32-channel K chunks, not the 16-channel ones that a
+    16-channel concatenation packs under ``BE_CONV3D_CK16=1``: that conv runs on the concatenated copy)."""
     return (os.environ.get("BE_CONV3D", "ztaps") == "ztaps" and pc.ks == 3 and pc.cout % 4 == 0
+            and pc.ztap.ck in (8, 32)
             and pc.cin_pad == ca + cb and pc.ztap.cin_pad == 3 * (ca + cb) and (ca + cb) % pc.ztap.ck == 0
             and ca % 8 == 0 and cb % 8 == 0)
 
