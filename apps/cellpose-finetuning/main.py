@@ -179,6 +179,16 @@ def measurement_items(table: dict, json_safe: bool) -> dict:
     return {"measurements": table, "diameter_px": float(table["diameter_px"])}
 
 
+def _diameter_arg(diameter):
+    """The ``diameter`` of a request: ``None``, a float, or the string ``"auto"``."""
+    diameter = _opt(diameter)
+    if diameter is None or diameter == "auto":
+        return diameter
+    if isinstance(diameter, str):
+        raise ValueError(f"diameter must be a number or 'auto', got {diameter!r}")
+    return float(diameter)
+
+
 def flow_rgb(dP: np.ndarray) -> np.ndarray:
     """cellpose ``dx_to_circ``: flow angle -> hue, magnitude -> value, as uint8 RGB [H, W, 3]."""
     dy, dx = dP[0], dP[1]
@@ -347,7 +357,11 @@ class CellposeFinetune:
     @serve.batch(max_batch_size=32, batch_wait_timeout_s=0.005, max_concurrent_batches=2)
     async def _segment_batch(self, reqs: list) -> list:
         """reqs: [(model_id, image CHW, params dict, want_flows[, want_measure])] -> [(masks, flows | None,
-        measurement table | None)].
+        measurement table | None)], with the diameter used as a fourth entry under ``diameter="auto"``.
+
+        A numeric ``diameter`` is not part of the grouping key: requests that differ only in it share
+        a batch, and the runner gets the list of their diameters (the one number when they all agree,
+        which is the scalar code path).  ``"auto"`` stays in the key, as its own value.
 
         Two batches are in flight: while one batch's kernels run (under the GPU lock, on the
         default stream), the other stacks its images or copies its masks back on a side stream
@@ -357,11 +371,16 @@ class CellposeFinetune:
         out = [None] * len(reqs)
         groups: dict = {}
         for i, (mid, img, prm, *_) in enumerate(reqs):
-            key = (mid, img.shape, img.dtype.str, isinstance(img, HWCImage), tuple(sorted(prm.items())))
+            rest = tuple(sorted((k, v) for k, v in prm.items() if k != "diameter"))
+            key = (mid, img.shape, img.dtype.str, isinstance(img, HWCImage), rest, prm.get("diameter") == "auto")
             groups.setdefault(key, []).append(i)
-        for (mid, shape, _, _, prm_items), idxs in groups.items():
+        for (mid, shape, _, _, prm_items, auto), idxs in groups.items():
             runner = await self._runner(mid)
             prm = dict(prm_items)
+            diams = [reqs[i][2].get("diameter") for i in idxs]
+            if "diameter" in reqs[idxs[0]][2]:
+                prm["diameter"] = "auto" if auto else (diams[0] if all(d == diams[0] for d in diams) else diams)
+            used: dict = {}  # under "auto": the diameters the runner estimated, one per image
             flows_needed = any(reqs[i][3] for i in idxs)
             # like want_flows, not part of the grouping key: the batch measures if any request asks
             measure_needed = any(len(reqs[i]) > 4 and reqs[i][4] for i in idxs)
@@ -386,6 +405,8 @@ class CellposeFinetune:
                             if m.is_cuda:
                                 ev = torch.cuda.Event()
                                 ev.record()
+                if auto:
+                    used["d"] = [float(v) for v in m.diameters]
                 with trace.span("app.d2h", images=len(idxs)):
                     if not m.is_cuda:
                         tabs = runner.measure(m, batch) if measure_needed else None
@@ -439,6 +460,8 @@ class CellposeFinetune:
             for j, i in enumerate(idxs):
                 want = tabs is not None and len(reqs[i]) > 4 and reqs[i][4]
                 out[i] = (masks[j], flows[j] if flows is not None and reqs[i][3] else None, tabs[j] if want else None)
+                if auto:
+                    out[i] += (used["d"][j],)
         return out
 
     def _stage_batch(self, images: list, runner):
@@ -481,7 +504,9 @@ class CellposeFinetune:
         input_arrays: list | None = Field(None, description="Images as arrays ([H,W], [H,W,C] or [C,H,W])."),
         model: str = Field("cpsam", description="Built-in model ('cpsam', 'cyto3'), a session id of a fine-tuned "
                                                 "model, or a published model artifact id."),
-        diameter: float | None = Field(None, description="Approximate object diameter (rescale to the model's 30 px)."),
+        diameter: float | str | None = Field(None, description="Approximate object diameter (rescale to the model's 30 px), "
+                                                               "or 'auto': estimate it per image from a first pass "
+                                                               "and segment again at that size (not for z-stacks)."),
         flow_threshold: float = Field(0.4, description="Flow error threshold (QC)."),
         cellprob_threshold: float = Field(0.0, description="Cell probability threshold."),
         niter: int | None = Field(None, description="Flow-dynamics iterations (default 200)."),
@@ -517,7 +542,11 @@ class CellposeFinetune:
         (allowed in every mode, stacks and ``do_3D`` included) is part of the batching group key:
         requests that differ in it never share a batch.  So is ``normalize``, in its canonical
         form (``pipeline.NormParams``); ``tile_norm_blocksize`` is not allowed with ``do_3D`` or with
-        a stack normalised as a whole (``norm3D``, the default)."""
+        a stack normalised as a whole (``norm3D``, the default).  A numeric ``diameter`` is not in the
+        key: requests that differ only in it share a batch, each image rescaled by its own.
+        ``diameter="auto"`` (plane mode only; its own batching group) estimates every image's diameter
+        from a first pass and segments the images that need it again at that size; each item then
+        carries ``diameter_px``, the diameter used, with or without ``return_measurements``."""
         if isinstance(artifact, dict):
             w = artifact
             artifact = w.get("artifact", w.get("artifact_id", w.get("id")))
@@ -555,12 +584,16 @@ class CellposeFinetune:
         else:
             raise ValueError("Provide input_arrays or artifact + image_paths")
         stack_mode = z_axis is not None or stitch_threshold > 0 or do_3D
+        diameter = _diameter_arg(diameter)
+        if diameter == "auto" and stack_mode:
+            raise ValueError("diameter='auto' is not supported for z-stacks (z_axis / stitch_threshold / do_3D): "
+                             "a stack takes one scalar diameter")
         if enable_clahe:
             if stack_mode:
                 raise ValueError("enable_clahe is not supported for z-stacks (z_axis / stitch_threshold / do_3D)")
             images = [clahe_image(im, self._device()) for im in images]
         runner = await self._runner(model_id)
-        prm = {"diameter": _opt(diameter), "flow_threshold": float(flow_threshold),
+        prm = {"diameter": diameter, "flow_threshold": float(flow_threshold),
                "cellprob_threshold": float(cellprob_threshold), "niter": int(_opt(niter) or 200),
                "augment": bool(_opt(augment) or False), **self._norm_prm(model_id, normalize)}
         if stack_mode:
@@ -578,10 +611,12 @@ class CellposeFinetune:
                 res = await asyncio.gather(*[self._segment_batch((model_id, c, prm, bool(return_flows),
                                                                   return_measurements)) for c in chw])
         out = []
-        for name, (m, f, tab) in zip(names, res):
+        for name, (m, f, tab, *used) in zip(names, res):
             item = {"input_path": name, "output": mask_png_payload(m) if json_safe else m}
             if return_measurements:
                 item.update(measurement_items(tab, bool(json_safe)))
+            if used:  # diameter="auto": the diameter this image was segmented at
+                item["diameter_px"] = float(used[0])
             if return_flows:
                 fl = [flow_rgb(f[:2]), f[:2], f[2]]
                 item["flows"] = [x.tolist() for x in fl] if json_safe else fl
@@ -646,7 +681,9 @@ class CellposeFinetune:
         label_arrays: list | None = Field(None, description="Ground-truth label images [H,W], one per input array."),
         model: str = Field("cpsam", description="Built-in model ('cpsam', 'cyto3'), a session id of a fine-tuned "
                                                 "model, or a published model artifact id."),
-        diameter: float | None = Field(None, description="Approximate object diameter (rescale to the model's 30 px)."),
+        diameter: float | str | None = Field(None, description="Approximate object diameter (rescale to the model's 30 px), "
+                                                               "or 'auto': estimate it per image from a first pass "
+                                                               "and segment again at that size."),
         flow_threshold: float = Field(0.4, description="Flow error threshold (QC)."),
         cellprob_threshold: float = Field(0.0, description="Cell probability threshold."),
         niter: int | None = Field(None, description="Flow-dynamics iterations (default 200)."),
@@ -701,7 +738,7 @@ class CellposeFinetune:
         if _opt(enable_clahe):
             images = [clahe_image(im, self._device()) for im in images]
         runner = await self._runner(model_id)
-        prm = {"diameter": _opt(diameter), "flow_threshold": float(flow_threshold),
+        prm = {"diameter": _diameter_arg(diameter), "flow_threshold": float(flow_threshold),
                "cellprob_threshold": float(cellprob_threshold), "niter": int(_opt(niter) or 200),
                "augment": bool(_opt(augment) or False), **self._norm_prm(model_id, normalize)}
         chw = [image_chw(im, runner.nchan) for im in images]

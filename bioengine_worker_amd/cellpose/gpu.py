@@ -347,6 +347,173 @@ class TilePlan:
         return out
 
 
+def _taper_factors(by: int, bx: int):
+    """The 1-D factors ``(wy, wx)`` of the separable taper mask of a ``by x bx`` tile."""
+    m = ref.taper_mask(by, bx)
+    cy, cx = by // 2, bx // 2
+    return m[:, cx] / np.sqrt(m[cy, cx]), m[cy, :] / np.sqrt(m[cy, cx])
+
+
+class ScaledTilePlan:
+    """Cellpose tiling of a batch of (H, W) images that each have their own scale (per-image
+    ``diameter``): image ``b`` is resampled to ``(Hs_b, Ws_b) = scaled_size(H | W, scales[b])``
+    (``None``: not rescaled), padded and tiled as :class:`TilePlan` tiles an image of that size, and
+    its blended flows are resampled back to (H, W).  The resampling happens in the loads of the
+    gather and of the last kernel (``csrc/kernels/tiles_scaled.hip``): no resized image exists.
+
+    The network takes tiles of one shape per call, so the tiles are grouped by their shape
+    ``(by, bx)``: ``groups`` lists ``(by, bx, first tile, tiles)``.  Whenever every scaled, padded
+    image is at least ``bsize`` on both axes -- always under ``augment`` -- that is one group.  The
+    tile table (image, y0, x0, mirror flags per tile; the flags replace the ``_aug`` entry points)
+    and the per-image table are uploaded once, here; every offset in them is 64-bit."""
+
+    N_FIELDS = 16  # int64 fields per row of the image table (tiles_scaled.hip kI)
+
+    def __init__(self, H: int, W: int, scales, bsize: int = 224, overlap: float = 0.1, augment: bool = False, device="cpu"):
+        self.H, self.W, self.B = int(H), int(W), len(scales)
+        self.augment = bool(augment)
+        if self.B == 0:
+            raise ValueError("ScaledTilePlan needs at least one image")
+        per = []
+        for r in scales:
+            Hs, Ws = ref.scaled_size(H, r), ref.scaled_size(W, r)
+            ya, yb = ref.pad_amounts(Hs)
+            xa, xb = ref.pad_amounts(Ws)
+            Hp, Wp = Hs + ya + yb, Ws + xa + xb
+            if self.augment:
+                ys, xs = ref.tile_starts_augment(Hp, bsize), ref.tile_starts_augment(Wp, bsize)
+                by = bx = int(bsize)
+            else:
+                ys, xs = ref.tile_starts(Hp, bsize, overlap), ref.tile_starts(Wp, bsize, overlap)
+                by, bx = min(bsize, Hp), min(bsize, Wp)
+            per.append(dict(Hs=Hs, Ws=Ws, pad_y=ya, pad_x=xa, ys=ys, xs=xs, by=by, bx=bx, nt=len(ys) * len(xs)))
+        self.images = per
+        shapes = []
+        for im in per:
+            if (im["by"], im["bx"]) not in shapes:
+                shapes.append((im["by"], im["bx"]))
+        taper, taper_off = [], {}
+        for by, bx in shapes:
+            taper_off[(by, bx)] = sum(len(t) for t in taper)
+            taper.extend(_taper_factors(by, bx))
+        tiles, flat_ys, flat_xs = [], [], []
+        itab = np.zeros((self.B, self.N_FIELDS), np.int64)
+        self.groups = []
+        flow_pix = yt_pix = 0
+        order = []  # images in tile-table order
+        for by, bx in shapes:
+            first = len(tiles)
+            for b, im in enumerate(per):
+                if (im["by"], im["bx"]) != (by, bx):
+                    continue
+                order.append(b)
+                itab[b, :14] = (im["Hs"], im["Ws"], im["pad_y"], im["pad_x"], len(im["ys"]), len(im["xs"]), len(tiles),
+                                len(flat_ys), len(flat_xs), 0, by, bx, taper_off[(by, bx)], yt_pix)
+                for j, y0 in enumerate(im["ys"]):
+                    for i, x0 in enumerate(im["xs"]):
+                        tiles.append((b, y0, x0, ((i & 1) | ((j & 1) << 1)) if self.augment else 0))
+                flat_ys.extend(im["ys"])
+                flat_xs.extend(im["xs"])
+                yt_pix += im["nt"] * by * bx
+            self.groups.append((by, bx, first, len(tiles) - first))
+        for b, im in enumerate(per):  # the flat scaled-flow buffer holds the images in batch order
+            itab[b, 9] = flow_pix
+            flow_pix += im["Hs"] * im["Ws"]
+        self.itab = itab  # host copy; column 6 is an image's first row of the tile table
+        self.nt_total, self.flow_pix, self.yt_pix = len(tiles), flow_pix, yt_pix
+        self.max_pix = max(im["Hs"] * im["Ws"] for im in per)
+        # rows of the tile outputs that belong to each image, padded with one past the end (a zero row)
+        ntmax = max(im["nt"] for im in per)
+        rows = np.full((self.B, ntmax), len(tiles), np.int64)
+        for b, im in enumerate(per):
+            rows[b, : im["nt"]] = int(itab[b, 6]) + np.arange(im["nt"])
+        dev = torch.device(device)
+        self.tiles_t = torch.tensor(np.asarray(tiles, np.int32).reshape(-1, 4), device=dev)
+        self.itab_t = torch.tensor(itab, device=dev)
+        self.ys_t = torch.tensor(flat_ys, dtype=torch.int32, device=dev)
+        self.xs_t = torch.tensor(flat_xs, dtype=torch.int32, device=dev)
+        self.taper_t = torch.tensor(np.concatenate(taper), dtype=torch.float32, device=dev)
+        self.rows_t = torch.tensor(rows, device=dev)
+
+    def _gather(self, img: torch.Tensor, cpad: int, mode: int, c_use: int, lower=1.0, upper=99.0, lh=None, invert=False):
+        B, C, H, W = img.shape
+        if (B, H, W) != (self.B, self.H, self.W):
+            raise ValueError(f"this plan tiles [{self.B}, C, {self.H}, {self.W}] batches, got {tuple(img.shape)}")
+        sptr = _native.stream(img.device)
+        ws = _pct_workspace(img.device, sptr, B * c_use) if mode and lh is None else None
+        out = []
+        for by, bx, first, n in self.groups:
+            t = torch.empty(n, by, bx, cpad, dtype=torch.bfloat16, device=img.device)
+            _native.call("be_tiles_gather_scaled", _native.ptr(img), RAW_DTYPES[img.dtype], mode, B, C, c_use, H, W, float(lower),
+                         float(upper), _native.ptr(lh), int(invert), _native.ptr(self.tiles_t), _native.ptr(self.itab_t), first, n,
+                         by, bx, cpad, _native.ptr(t), _native.ptr(ws), ws.numel() // 4 * 4 if ws is not None else 0, sptr)
+            out.append(t)
+        return out
+
+    def gather(self, img: torch.Tensor, cpad: int) -> list:
+        """img [B, C, H, W], already normalised (or to be taken as it is) -> one NHWC bf16 tile
+        tensor [tiles, by, bx, cpad] per group: each tile pixel is the bilinear sample of the image at
+        its scaled coordinate, zero outside the scaled image, rounded once."""
+        return self._gather(img.float().contiguous(), cpad, 0, img.shape[1])
+
+    def gather_normalized(self, x_raw: torch.Tensor, cpad: int, c_use: int | None = None, params=None) -> list:
+        """``gather(normalize_img_gpu(x_raw, params, c_use), cpad)`` bit for bit from the raw pixels
+        (contiguous uint8, uint16 or float32): the percentile select runs on them and each of the
+        four taps is normalised with its row's constants before the lerp.  ``params``: a
+        :class:`~.pipeline.NormParams` of a global rule (``None``: the default percentiles); tile
+        normalisation has no fused form here -- normalise first and use :meth:`gather`."""
+        _check_raw(x_raw, "ScaledTilePlan.gather_normalized")
+        C = x_raw.shape[1]
+        c_use = C if c_use is None else min(int(c_use), C)
+        if params is None or _plain_percentile(params):
+            lower, upper = (1.0, 99.0) if params is None else (params.lower, params.upper)
+            return self._gather(x_raw, cpad, 1, c_use, lower, upper)
+        if not params.normalize or params.tile_blocksize > 0:
+            raise ValueError("ScaledTilePlan.gather_normalized takes the global normalisation rules only")
+        lh = _lowhigh_tensor(params.lowhigh, c_use, x_raw.device) if params.lowhigh is not None else None
+        return self._gather(x_raw, cpad, 2, c_use, params.lower, params.upper, lh, params.invert)
+
+    def blend(self, yts, unmirror: bool = True) -> torch.Tensor:
+        """Tile outputs (one [tiles, nout, by, bx] fp32 tensor per group, as the gathers return the
+        tiles) -> the flat fp32 buffer that holds image ``b``'s ``[nout, Hs_b, Ws_b]`` blend at
+        ``itab[b, 9] * nout``.  Output-centric, no atomics: bit-deterministic."""
+        yts = [yts] if torch.is_tensor(yts) else list(yts)
+        nout = yts[0].shape[1]
+        for yt, (by, bx, _, n) in zip(yts, self.groups):
+            if tuple(yt.shape) != (n, nout, by, bx) or yt.dtype != torch.float32:
+                raise ValueError(f"blend: expected float32 tile outputs {(n, nout, by, bx)}, got {yt.dtype} {tuple(yt.shape)}")
+        if len(yts) != len(self.groups) or nout > 4:
+            raise ValueError("blend: one tile-output tensor per group with at most 4 channels")
+        flat = yts[0].contiguous().view(-1) if len(yts) == 1 else torch.cat([y.reshape(-1) for y in yts])
+        out = torch.empty(self.flow_pix * nout, dtype=torch.float32, device=flat.device)
+        _native.call("be_tiles_blend_scaled", _native.ptr(flat), _native.ptr(self.tiles_t), _native.ptr(self.itab_t),
+                     _native.ptr(self.ys_t), _native.ptr(self.xs_t), _native.ptr(self.taper_t), self.B, nout, self.max_pix,
+                     int(bool(unmirror)), _native.ptr(out), _native.stream(flat.device))
+        return out
+
+    def resize_back(self, flat: torch.Tensor, nout: int) -> torch.Tensor:
+        """The buffer of :meth:`blend` -> [B, nout, H, W] fp32, each image resampled bilinearly from
+        its own ``(Hs_b, Ws_b)``."""
+        if flat.numel() != self.flow_pix * nout or flat.dtype != torch.float32 or not flat.is_contiguous():
+            raise ValueError("resize_back takes the flat float32 buffer blend() returned")
+        out = torch.empty(self.B, nout, self.H, self.W, dtype=torch.float32, device=flat.device)
+        _native.call("be_resize_bilinear_ragged", _native.ptr(flat), _native.ptr(self.itab_t), self.B, nout, self.H, self.W,
+                     _native.ptr(out), _native.stream(flat.device))
+        return out
+
+    def scaled_flow(self, flat: torch.Tensor, b: int, nout: int) -> torch.Tensor:
+        """Image ``b``'s ``[nout, Hs_b, Ws_b]`` view of the buffer of :meth:`blend`."""
+        im = self.images[b]
+        o = sum(i["Hs"] * i["Ws"] for i in self.images[:b]) * nout
+        return flat[o: o + nout * im["Hs"] * im["Ws"]].view(nout, im["Hs"], im["Ws"])
+
+    def sum_styles(self, sts) -> torch.Tensor:
+        """Per-tile style vectors (one [tiles, S] tensor per group) -> their sum per image [B, S]."""
+        sts = [sts] if torch.is_tensor(sts) else list(sts)
+        st = torch.cat(sts + [torch.zeros(1, sts[0].shape[1], dtype=sts[0].dtype, device=sts[0].device)])
+        return st[self.rows_t].sum(1)
+
+
 # ------------------------------------------------------------------ mask recovery
 
 

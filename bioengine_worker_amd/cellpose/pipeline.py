@@ -122,7 +122,14 @@ def norm_params(value) -> NormParams:
 
 @dataclass
 class EvalParams:
-    diameter: float | None = None
+    #: cell diameter in pixels the images are rescaled from (to the network's ``diam_mean``): one number
+    #: for the whole batch; a sequence or 1-D tensor with one entry per image (``None``, 0 and nan:
+    #: that image is not rescaled), which runs the batch through one ragged tile plan
+    #: (:class:`gpu.ScaledTilePlan`); or ``"auto"``: a first pass without rescaling, the diameter of
+    #: every image from its masks (:func:`reference.derive_measurements`' ``diameter_px``), and one
+    #: per-image pass for the images whose estimate asks for a rescale.  :meth:`CellposeRunner.eval_stack`
+    #: and :meth:`~CellposeRunner.eval_3d` take a number only.
+    diameter: "float | None | str | list | tuple | np.ndarray | torch.Tensor" = None
     niter: int = 200
     flow_threshold: float = 0.4
     cellprob_threshold: float = 0.0
@@ -170,6 +177,55 @@ def resolve_norm(p: EvalParams) -> EvalParams:
 def norm_on(p: EvalParams) -> bool:
     """Whether ``p`` asks for normalisation, whichever form ``p.normalize`` has."""
     return norm_params(p.normalize).normalize
+
+
+def diameter_form(diameter) -> str:
+    """``"scalar"`` (a number or None), ``"list"`` (one diameter per image) or ``"auto"``."""
+    if isinstance(diameter, str):
+        if diameter != "auto":
+            raise ValueError(f"diameter must be a number, a sequence with one entry per image or 'auto', got {diameter!r}")
+        return "auto"
+    if isinstance(diameter, (list, tuple)) or (isinstance(diameter, (np.ndarray, torch.Tensor)) and diameter.ndim > 0):
+        return "list"
+    return "scalar"
+
+
+def per_image_diameters(diameter, B: int, diam_mean: float) -> list:
+    """The sequence form of ``diameter`` -> a list of ``B`` entries: the diameter as a float, or
+    ``None`` where the image is not rescaled (``None``, 0, nan, negative, or within the band
+    ``|diam_mean / d - 1| <= 1e-3`` in which the scalar form does not rescale either)."""
+    if isinstance(diameter, (np.ndarray, torch.Tensor)):
+        if diameter.ndim != 1:
+            raise ValueError(f"diameter: expected one entry per image, got shape {tuple(diameter.shape)}")
+        diameter = diameter.tolist()
+    if len(diameter) != B:
+        raise ValueError(f"diameter has {len(diameter)} entries for a batch of {B} images")
+    out = []
+    for d in diameter:
+        try:
+            d = None if d is None else float(d)
+        except (TypeError, ValueError):
+            raise ValueError(f"diameter: every entry must be a number or None, got {d!r}") from None
+        if d is None or not d > 0 or abs(diam_mean / d - 1.0) <= 1e-3:
+            out.append(None)
+        else:
+            out.append(d)
+    return out
+
+
+class PerImageRescale(list):
+    """The rescale factor of every image of a batch (1.0 where it was not rescaled), in place of the
+    one ``rescale`` of a scalar ``diameter``; ``diameters`` is what ``masks.diameters`` reports."""
+
+    def __init__(self, factors, diameters):
+        super().__init__(factors)
+        self.diameters = [0.0 if d is None else float(d) for d in diameters]
+
+
+def _scalar_diameter_only(p: "EvalParams", what: str) -> None:
+    if diameter_form(p.diameter) != "scalar":
+        raise ValueError(f"{what} takes one scalar diameter for the whole volume, not a sequence or 'auto': "
+                         "per-image diameters belong to eval()")
 
 
 def as_batch(images, nchan: int, device=None, keep_raw: bool = False):
@@ -230,6 +286,7 @@ class CellposeRunner:
         self.cin_pad = (self.nchan + 7) // 8 * 8
         self._pinned: torch.Tensor | None = None  # host staging for numpy batches (pinned -> async DMA)
         self._plans: dict = {}
+        self._scaled_plans: dict = {}
         self._net_graphs: dict = {}
 
     # ---------------------------------------------------------------- network
@@ -241,6 +298,23 @@ class CellposeRunner:
         if key not in self._plans:
             self._plans[key] = TilePlan(H, W, bs, p.tile_overlap, device=self.device, augment=bool(p.augment))
         return self._plans[key]
+
+    #: ragged plans kept (least recently used first): their keys come from requests' diameters
+    SCALED_PLANS_MAX = 64
+
+    def _plan_scaled(self, H, W, scales, p: EvalParams):
+        from .gpu import ScaledTilePlan
+
+        bs = p.bsize or self.bsize
+        sizes = tuple((ref.scaled_size(H, r), ref.scaled_size(W, r)) for r in scales)
+        key = (H, W, sizes, bs, p.tile_overlap, bool(p.augment))
+        plan = self._scaled_plans.pop(key, None)
+        if plan is None:
+            plan = ScaledTilePlan(H, W, scales, bs, p.tile_overlap, augment=bool(p.augment), device=self.device)
+        self._scaled_plans[key] = plan  # most recently used last
+        while len(self._scaled_plans) > self.SCALED_PLANS_MAX:
+            self._scaled_plans.pop(next(iter(self._scaled_plans)))
+        return plan
 
     #: HBM bytes one 224^2 CPnet tile keeps live at the forward's peak (measured on MI355X: 23.0-23.4
     #: MB per tile at 16 / 64 tiles, max_memory_allocated over one engine call; rounded up)
@@ -360,20 +434,107 @@ class CellposeRunner:
         style = torch.stack(styles)
         return torch.stack(ys), style / torch.sqrt((style * style).sum(1, keepdim=True)).clamp_min(1e-12)
 
+    @torch.no_grad()
+    def run_net_scaled(self, x: torch.Tensor, p: EvalParams, scales, raw: bool = False) -> tuple[torch.Tensor, torch.Tensor]:
+        """:meth:`run_net` on the tiled GPU path with image ``b`` rescaled by ``scales[b]`` (``None``:
+        not rescaled): ``x`` [B, C, H, W] at its own size -> (y [B, 3, H, W] fp32, style [B, S]).  The
+        rescaling is in the loads of the ragged gather and of the resize that follows the blend
+        (:class:`gpu.ScaledTilePlan`); the network runs once per tile shape."""
+        if not (self.device.type == "cuda" and p.tile):
+            raise ValueError("run_net_scaled needs the tiled GPU path")
+        B, C, H, W = x.shape
+        norm = norm_params(p.normalize)
+        plan = self._plan_scaled(H, W, scales, p)
+        with trace.span("cellpose.tiles_gather", cuda=True, tiles=plan.nt_total):
+            tiles = (plan.gather_normalized(x, self.cin_pad, self.nchan, params=None if norm.is_default else norm)
+                     if raw else plan.gather(x, self.cin_pad))
+        with trace.span("cellpose.net", cuda=True, tiles=plan.nt_total):
+            yts, sts = [], []
+            for t in tiles:
+                if self.is_sam:
+                    yts.append(self._sam_tiles(t))
+                    sts.append(torch.zeros(t.shape[0], 256, device=x.device))
+                else:
+                    yt, st = self._tile_queue(t, p)
+                    yts.append(yt)
+                    sts.append(st)
+        with trace.span("cellpose.blend", cuda=True):
+            y = plan.resize_back(plan.blend(yts), yts[0].shape[1])
+        style = plan.sum_styles(sts)
+        return y, style / torch.sqrt((style * style).sum(1, keepdim=True)).clamp_min(1e-12)
+
     # ---------------------------------------------------------------- full eval
     @torch.no_grad()
     def eval(self, images, p: EvalParams | None = None, **kw):
-        """Returns (masks [B, H, W] int32 tensor, flows [B, 3, H, W] fp32 tensor, styles [B, S])."""
+        """Returns (masks [B, H, W] int32 tensor, flows [B, 3, H, W] fp32 tensor, styles [B, S]).
+        With a per-image or ``"auto"`` ``diameter`` the masks carry ``masks.diameters``: a float32
+        CPU tensor [B] of the diameter used for each image (0: not rescaled; under ``"auto"`` the
+        estimate, whether it led to a second pass or not)."""
         p = p or EvalParams()
         for k, v in kw.items():
             setattr(p, k, v)
         resolve_norm(p)
+        form = diameter_form(p.diameter)
+        if form == "auto" and not p.compute_masks:
+            raise ValueError("diameter='auto' estimates the diameters from the masks: it needs compute_masks=True")
         x, raw = as_batch(self._stage(images), self.nchan, self.device, keep_raw=True)
-        B, C, H, W = x.shape
+        if form == "auto":
+            return self._eval_auto(x, p, raw)
+        if form == "list":
+            p = dataclasses.replace(p, diameter=per_image_diameters(p.diameter, x.shape[0], self.diam_mean))
+        return self._eval_batch(x, p, raw)
+
+    def _eval_batch(self, x, p: EvalParams, raw: bool):
+        B = x.shape[0]
         nch = min(p.pipeline_chunks, B // max(1, p.pipeline_min_chunk))
         if self.device.type == "cuda" and p.compute_masks and nch >= 2:
             return self._eval_pipelined(x, p, nch, raw)
         return self._eval_one(x, p, raw)
+
+    def estimate_diameters(self, masks: torch.Tensor) -> np.ndarray:
+        """``diameter_px`` of :func:`reference.derive_measurements` for every image of ``masks``
+        [B, H, W]: ``median(sqrt(area)) * 2 / sqrt(pi)`` over its labels (0 without labels), float64
+        [B].  On the GPU the areas are :func:`gpu.label_counts`, the medians are taken on the device
+        and read back once for the whole batch."""
+        B = masks.shape[0]
+        if not masks.is_cuda:
+            med = np.zeros(B)
+            for b in range(B):
+                area = np.bincount(masks[b].numpy().ravel().astype(np.int64))[1:]
+                if (area > 0).any():
+                    med[b] = np.median(np.sqrt(area[area > 0].astype(np.float64)))
+            return med * 2.0 / np.sqrt(np.pi)
+        from .gpu import label_counts
+
+        nlab = getattr(masks, "label_bound", None) or int(masks.max()) + 1
+        if nlab <= 1:
+            return np.zeros(B)
+        counts = label_counts(masks.to(torch.int32), nlab)
+        present = counts > 0
+        n = present.sum(1, keepdim=True)
+        srt = torch.where(present, counts.double().sqrt(), torch.full((), float("inf"), dtype=torch.float64, device=masks.device))
+        srt = srt.sort(1).values
+        lo, hi = (n - 1).clamp_(min=0) // 2, (n // 2).clamp_(max=nlab - 1)
+        med = torch.where(n > 0, (srt.gather(1, lo) + srt.gather(1, hi)) / 2, torch.zeros((), dtype=torch.float64, device=masks.device))
+        return med[:, 0].cpu().numpy() * 2.0 / np.sqrt(np.pi)
+
+    def _eval_auto(self, x, p: EvalParams, raw: bool):
+        B = x.shape[0]
+        masks, y, style = self._eval_batch(x, dataclasses.replace(p, diameter=None), raw)
+        d = self.estimate_diameters(masks)
+        redo = [b for b in range(B) if d[b] > 0 and abs(self.diam_mean / d[b] - 1.0) > 1e-3]
+        if redo:
+            idx = torch.tensor(redo, device=x.device)
+            xs = x if len(redo) == B else x[idx].contiguous()
+            m2, y2, s2 = self._eval_batch(xs, dataclasses.replace(p, diameter=[float(d[b]) for b in redo]), raw)
+            bounds = [getattr(m, "label_bound", None) for m in (masks, m2)]
+            masks[idx], y[idx], style[idx] = m2, y2, s2
+            if all(v is not None for v in bounds):
+                masks.label_bound = max(bounds)
+            elif hasattr(masks, "label_bound"):
+                del masks.label_bound
+        masks.diameters = torch.tensor(d, dtype=torch.float32)
+        return masks, y, style
 
     @torch.no_grad()
     def eval_stack(self, stack, p: EvalParams | None = None, **kw):
@@ -388,6 +549,7 @@ class CellposeRunner:
         p = dataclasses.replace(p) if p is not None else EvalParams()
         for k, v in kw.items():
             setattr(p, k, v)
+        _scalar_diameter_only(p, "eval_stack")
         resolve_norm(p)
         if norm_on(p) and p.norm3d and p.normalize.tile_blocksize > 0:
             raise ValueError("tile_norm_blocksize over a whole stack (norm3D) is not supported: give norm3D=False "
@@ -460,6 +622,7 @@ class CellposeRunner:
         p = dataclasses.replace(p) if p is not None else EvalParams()
         for k, v in kw.items():
             setattr(p, k, v)
+        _scalar_diameter_only(p, "eval_3d")
         resolve_norm(p)
         if norm_on(p) and p.normalize.tile_blocksize > 0:
             raise ValueError("tile_norm_blocksize is not supported by eval_3d: the volume is normalised once over all voxels")
@@ -620,7 +783,43 @@ class CellposeRunner:
             return x, True
         return x.float()[:, : self.nchan], False
 
+    def _net_stage_list(self, x, p: EvalParams, raw: bool):
+        """The network stage for the sequence form of ``p.diameter``: ``(y, style, PerImageRescale)``.
+        On the tiled GPU path the whole batch goes through one ragged plan (:meth:`run_net_scaled`),
+        from the raw pixels under the conditions the unscaled path takes them (never from a HIP-graph
+        replay); tile normalisation normalises first and gathers from float32.  Elsewhere (the CPU
+        oracle, ``tile=False``) the images run one by one through the scalar code."""
+        B = x.shape[0]
+        diams = per_image_diameters(p.diameter, B, self.diam_mean)
+        rescale = PerImageRescale([1.0 if d is None else self.diam_mean / d for d in diams], diams)
+        if all(d is None for d in diams):
+            y, style, _ = self._net_stage(x, dataclasses.replace(p, diameter=None), raw)
+            return y, style, rescale
+        if not (self.device.type == "cuda" and p.tile):
+            outs = [self._net_stage(x[b: b + 1].contiguous(), dataclasses.replace(p, diameter=d), raw)
+                    for b, d in enumerate(diams)]
+            return torch.cat([o[0] for o in outs]), torch.cat([o[1] for o in outs]), rescale
+        from .gpu import takes_fused_front
+
+        norm = norm_params(p.normalize)
+        fused = raw and norm.normalize and norm.tile_blocksize == 0 and takes_fused_front(x)
+        if not fused:
+            if raw:
+                x = x.float()[:, : self.nchan]
+            if norm.normalize:
+                with trace.span("cellpose.normalize99", cuda=True, images=B):
+                    x = self._normalize(x, norm)
+        y, style = self.run_net_scaled(x, p, [None if d is None else self.diam_mean / d for d in diams], raw=fused)
+        return y, style, rescale
+
     def _eval_one(self, x, p: EvalParams, raw: bool = False):
+        if diameter_form(p.diameter) == "list":
+            y, style, rescale = self._net_stage_list(x, p, raw)
+            if not p.compute_masks:
+                return None, y, style
+            with trace.span("cellpose.masks", cuda=self.device.type == "cuda", images=x.shape[0]):
+                masks = self.compute_masks(y, p, rescale)
+            return masks, y, style
         x, raw = self._front(x, p, raw)
         B, C, H, W = x.shape
         if not (p.diameter is not None and p.diameter > 0 and abs(self.diam_mean / float(p.diameter) - 1.0) > 1e-3):
@@ -652,6 +851,8 @@ class CellposeRunner:
         return masks, y, style
 
     def _net_stage(self, x, p: EvalParams, raw: bool = False):
+        if diameter_form(p.diameter) == "list":
+            return self._net_stage_list(x, p, raw)
         x, raw = self._front(x, p, raw)
         B, C, H, W = x.shape
         if not (p.diameter is not None and p.diameter > 0 and abs(self.diam_mean / float(p.diameter) - 1.0) > 1e-3):
@@ -683,6 +884,8 @@ class CellposeRunner:
         parts = x.tensor_split(nch)
         ys, styles, masks = [], [], []
         pending = None
+        per_image = diameter_form(p.diameter) == "list"
+        starts = np.cumsum([0] + [part.shape[0] for part in parts])  # the diameters split with the images
 
         def finish(item):
             y, rescale, ev = item
@@ -693,8 +896,9 @@ class CellposeRunner:
                     m = self.compute_masks(y, p, rescale)
             masks.append(m)
 
-        for part in parts:
-            y, style, rescale = self._net_stage(part, p, raw)
+        for i, part in enumerate(parts):
+            pp = dataclasses.replace(p, diameter=list(p.diameter[starts[i]: starts[i + 1]])) if per_image else p
+            y, style, rescale = self._net_stage(part, pp, raw)
             ys.append(y)
             styles.append(style)
             ev = torch.cuda.Event()
@@ -706,7 +910,10 @@ class CellposeRunner:
         main.wait_stream(side)
         for m in masks:
             m.record_stream(main)
-        return torch.cat(masks), torch.cat(ys), torch.cat(styles)
+        out = torch.cat(masks)
+        if per_image:
+            out.diameters = torch.cat([m.diameters for m in masks])
+        return out, torch.cat(ys), torch.cat(styles)
 
     @torch.no_grad()
     def eval_locked(self, images, net_lock, mask_lock, p: EvalParams | None = None, **kw):
@@ -721,8 +928,8 @@ class CellposeRunner:
         for k, v in kw.items():
             setattr(p, k, v)
         resolve_norm(p)
-        if self.device.type != "cuda" or not p.compute_masks:
-            with net_lock:
+        if self.device.type != "cuda" or not p.compute_masks or diameter_form(p.diameter) == "auto":
+            with net_lock:  # "auto" is two dependent passes: it runs whole, as eval() runs it
                 m, y, st = self.eval(images, p)
                 ev = None
                 if self.device.type == "cuda":
@@ -768,8 +975,30 @@ class CellposeRunner:
             return torch.stack([torch.from_numpy(ref.normalize99(x[b].numpy())) for b in range(x.shape[0])])
         return torch.stack([torch.from_numpy(ref.normalize_img(x[b].numpy(), norm)) for b in range(x.shape[0])])
 
-    def compute_masks(self, y: torch.Tensor, p: EvalParams, rescale: float = 1.0) -> torch.Tensor:
-        niter = p.niter if p.niter else int(200 / max(rescale, 1e-3))
+    def compute_masks(self, y: torch.Tensor, p: EvalParams, rescale: "float | PerImageRescale" = 1.0) -> torch.Tensor:
+        """Mask recovery of the flows ``y`` [B, 3, H, W].  ``rescale``: the factor the batch was rescaled
+        by, which sets ``niter`` when ``p.niter`` is unset; a :class:`PerImageRescale` recovers the
+        masks per group of images that share ``int(200 / r_b)``, so every image gets the result it
+        would get alone, and the masks carry ``diameters``."""
+        if isinstance(rescale, PerImageRescale):
+            niters = [p.niter if p.niter else int(200 / max(r, 1e-3)) for r in rescale]
+            if len(set(niters)) == 1:
+                out = self._masks_niter(y, p, niters[0])
+            else:
+                out = torch.zeros(y.shape[0], y.shape[2], y.shape[3], dtype=torch.int32, device=y.device)
+                bounds = []
+                for n in sorted(set(niters)):
+                    idx = torch.tensor([b for b, v in enumerate(niters) if v == n], device=y.device)
+                    m = self._masks_niter(y[idx].contiguous(), p, n)
+                    out[idx] = m.to(torch.int32)
+                    bounds.append(getattr(m, "label_bound", 1))
+                if self.device.type == "cuda":
+                    out.label_bound = max(bounds)
+            out.diameters = torch.tensor(rescale.diameters, dtype=torch.float32)
+            return out
+        return self._masks_niter(y, p, p.niter if p.niter else int(200 / max(rescale, 1e-3)))
+
+    def _masks_niter(self, y: torch.Tensor, p: EvalParams, niter: int) -> torch.Tensor:
         if self.device.type == "cuda":
             from .gpu import compute_masks_gpu
 
@@ -960,7 +1189,8 @@ class _EvalStream:
     def __init__(self, runner: CellposeRunner, p: EvalParams):
         self.r, self.p = runner, resolve_norm(p)
         self.pending = None
-        self.cuda = runner.device.type == "cuda" and p.compute_masks
+        # "auto" is two dependent passes per batch: such a stream evaluates every batch directly
+        self.cuda = runner.device.type == "cuda" and p.compute_masks and diameter_form(p.diameter) != "auto"
         if self.cuda:
             if getattr(runner, "_mask_stream", None) is None:
                 runner._mask_stream = mask_stream(runner.device)

@@ -232,6 +232,63 @@ def make_tiles(img: np.ndarray, bsize: int = 224, overlap: float = 0.1, augment:
     return tiles, ys, xs
 
 
+def scaled_size(L: int, r) -> int:
+    """Length of an axis of ``L`` pixels rescaled by ``r`` (``None``: not rescaled), never below 8."""
+    return int(L) if r is None else max(8, int(round(L * r)))
+
+
+def _fma(a, b, c, dtype):
+    """``a * b + c`` with one rounding for float32 (through float64, where the product is exact), as the
+    kernels' ``fmaf`` and the fused multiply-adds of torch's CPU kernel; plain arithmetic otherwise."""
+    if dtype is np.float32:
+        return (np.asarray(a, np.float64) * np.asarray(b, np.float64) + np.asarray(c, np.float64)).astype(np.float32)
+    return a * b + c
+
+
+def _resize_axis(n_in: int, n_out: int, dtype):
+    """Taps ``i0``, ``i1`` and the weight of ``i1`` for every output index of one axis: half-pixel
+    centres, the source coordinate clamped at 0, the upper neighbour clamped at the edge."""
+    ratio = dtype(n_in) / dtype(n_out)
+    s = _fma(ratio, np.arange(n_out).astype(dtype) + dtype(0.5), dtype(-0.5), dtype)
+    s = np.maximum(s, dtype(0))
+    i0 = np.minimum(s.astype(np.int64), n_in - 1)
+    i1 = np.minimum(i0 + 1, n_in - 1)
+    return i0, i1, (s - i0.astype(dtype)).astype(dtype)
+
+
+def resize_bilinear_ref(img: np.ndarray, size, dtype=np.float32) -> np.ndarray:
+    """img [..., H, W] -> [..., oh, ow] by the bilinear rule of the resize kernels (no antialiasing),
+    coordinates, weights and the lerp ``ly0 * (lx0 * a + lx1 * b) + ly1 * (lx0 * c + lx1 * d)`` all
+    in ``dtype``.  float64 is the yardstick of the float32 kernels.  With float32 the coordinate and
+    the first product of each sum are fused multiply-adds, as in ``be_tiles_gather_scaled``.  That
+    gives the taps and weights of ``F.interpolate(mode="bilinear", align_corners=False)`` on the CPU
+    exactly, and its values bit for bit at many sizes; at others torch's CPU kernel, whose sums the
+    compiler fuses as it sees fit, differs in the last bit or two."""
+    dtype = np.dtype(dtype).type
+    x = np.asarray(img).astype(dtype)
+    oh, ow = int(size[0]), int(size[1])
+    y0, y1, ly1 = _resize_axis(x.shape[-2], oh, dtype)
+    x0, x1, lx1 = _resize_axis(x.shape[-1], ow, dtype)
+    ly1 = ly1[:, None]
+    ly0, lx0 = dtype(1) - ly1, dtype(1) - lx1
+    top, bot = x[..., y0, :], x[..., y1, :]
+    t = _fma(lx0, top[..., x0], lx1 * top[..., x1], dtype)
+    b = _fma(lx0, bot[..., x0], lx1 * bot[..., x1], dtype)
+    return _fma(ly0, t, ly1 * b, dtype)
+
+
+def scaled_tiles(img: np.ndarray, r, bsize: int = 224, overlap: float = 0.1, augment: bool = False, dtype=np.float32):
+    """The tiles the network sees of image ``img`` [C, H, W] rescaled by ``r`` (``None``: as it is):
+    :func:`resize_bilinear_ref` to ``scaled_size`` of both axes, zero padding by :func:`pad_amounts`,
+    then :func:`make_tiles`.  Returns what :func:`make_tiles` returns."""
+    C, H, W = img.shape
+    Hs, Ws = scaled_size(H, r), scaled_size(W, r)
+    x = np.asarray(img).astype(dtype) if (Hs, Ws) == (H, W) else resize_bilinear_ref(img, (Hs, Ws), dtype)
+    ya, yb = pad_amounts(Hs)
+    xa, xb = pad_amounts(Ws)
+    return make_tiles(np.pad(x, ((0, 0), (ya, yb), (xa, xb))), bsize, overlap, augment=augment)
+
+
 def unaugment_tiles(y: np.ndarray, ys, xs) -> np.ndarray:
     """Network outputs ``y`` [nt, nout >= 3, by, bx] (dY, dX, cellprob, ...) of the tiles of
     ``make_tiles(..., augment=True)`` -> the same outputs mirrored back (a new array): tile
