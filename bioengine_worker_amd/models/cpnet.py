@@ -214,10 +214,11 @@ class _FConv:
     def __init__(self, seq: nn.Sequential, relu: bool, device, cin_pad=None, cout_pad_to=None):
         bn, conv = seq[0], seq[-1]
         self.pc = convops.PackedConv.from_weight(conv.weight, conv.bias, cin_pad=cin_pad, cout_pad_to=cout_pad_to).to(device)
-        # fragment-order weights of the 128-channel ping-pong kernel (and of its pooled 64 -> 128 build,
-        # the level-2 entry conv with its 1x1 projection): packed here, not in the first forward
-        if (convops.frag_eligible(self.pc) or convops.frag_eligible_pool(self.pc) or
-                convops.frag_eligible_proj(self.pc)) and torch.device(device).type == "cuda":
+        # fragment-order weights of the 128-channel ping-pong kernel (of its pooled 64 -> 128 build, the
+        # level-2 entry conv with its 1x1 projection, and of its 128 -> 256 build, the level-3 entry conv):
+        # packed here, not in the first forward
+        if (convops.frag_eligible(self.pc) or convops.frag_eligible_pool(self.pc) or convops.frag_eligible_proj(self.pc)
+                or convops.frag_eligible_c256(self.pc)) and torch.device(device).type == "cuda":
             self.pc.frag()
         s, t = _bn_fold(bn, device)
         self.scale = _pad_vec(s, self.pc.cin_pad, 0.0)
@@ -440,10 +441,24 @@ class CPnetEngine:
         ``next_act`` = (scale, shift) of the following up block's first conv, which reads this
         block's output through the igemm path too (written as a second, activated copy)."""
         ig = self.ig
-        proj = e["proj"](src, inmode="pool2")
-        c1, c2, c3 = e["c1"], e["c2"], e["c3"]
-        ha = convops.fused_conv2d(src, e["c0"].pc, scale=e["c0"].scale, shift=e["c0"].shift, relu=True, inmode="pool2",
-                                  post_scale=c1.scale, post_shift=c1.shift, post_relu=True)
+        c0, c1, c2, c3 = e["c0"], e["c1"], e["c2"], e["c3"]
+        entry = convops.pp128_pooled_entry(c0.pc, src)  # the native rules, asked before anything is launched
+        if entry:
+            # level 3 in large calls: the source is pooled once, and the projection and the entry conv read
+            # the pooled tensor with no input transform (bit for bit what the pooled-input loaders form);
+            # the conv runs on the ping-pong kernel's 256-channel build (2) or on the per-layer kernel (1)
+            pooled = convops.pool2_nhwc(src)
+            proj = e["proj"](pooled)
+            if entry == 2:
+                ha = convops.fused_conv2d_c256(pooled, c0.pc, scale=c0.scale, shift=c0.shift, relu=True,
+                                               post_scale=c1.scale, post_shift=c1.shift, post_relu=True)
+            else:
+                ha = convops.fused_conv2d(pooled, c0.pc, scale=c0.scale, shift=c0.shift, relu=True, nw=8,
+                                          post_scale=c1.scale, post_shift=c1.shift, post_relu=True)
+        else:
+            proj = e["proj"](src, inmode="pool2")
+            ha = convops.fused_conv2d(src, c0.pc, scale=c0.scale, shift=c0.shift, relu=True, inmode="pool2",
+                                      post_scale=c1.scale, post_shift=c1.shift, post_relu=True)
         x1, x1a = _igc(ha, ig[("down", n, 1)], residual=proj, ascale=c2.scale, ashift=c2.shift)
         _, h2a = _igc(x1a, ig[("down", n, 2)], want_out=False, ascale=c3.scale, ashift=c3.shift)
         if next_act is None:

@@ -137,7 +137,10 @@ class PackedConv:
         if ``wp`` was replaced or written since).  An engine calls this when it is built; a conv whose
         fragments were never built, or went stale, runs on the per-layer kernel (:meth:`frag_built`)."""
         if self.frag_built() is None:
-            self.wf = pack_frag(self.wp) if self.ks == 3 else pack_frag_1x1(self.wp)
+            if frag_eligible_c256(self):
+                self.wf = pack_frag_c256(self.wp)
+            else:
+                self.wf = pack_frag(self.wp) if self.ks == 3 else pack_frag_1x1(self.wp)
             self.wf_key = self._wp_key()
         return self.wf
 
@@ -165,6 +168,46 @@ def frag_eligible_proj(pc: PackedConv) -> bool:
     """The 1x1 projection that the pooled build can compute beside its 3x3 conv: 64 -> 128 channels
     (CPnet's level-2 residual projection).  Its fragments are :func:`pack_frag_1x1`'s."""
     return pc.ks == 1 and pc.cin_pad == 64 and pc.cout == 128 and pc.cout_pad == 128
+
+
+def frag_eligible_c256(pc: PackedConv) -> bool:
+    """The layer with a 256-channel build of that kernel: 3x3, 128 -> 256 channels (CPnet's level-3
+    entry conv, on the pooled tensor).  Its fragments are :func:`pack_frag_c256`'s."""
+    return pc.ks == 3 and pc.ck == 32 and pc.cin_pad == 128 and pc.cout == 256 and pc.cout_pad == 256
+
+
+def pp128_takes_prepool(pc: PackedConv, x: torch.Tensor) -> bool:
+    """Whether a level whose entry convs (3x3 ``pc``, 128 -> 256, and its 1x1 projection) read the
+    source ``x`` [N, Hs, Ws, 128] through a 2x2 max-pool should pool once (:func:`pool2_nhwc`) and run both
+    on the pooled tensor: the native side's answer (``be_conv_pp128_takes_prepool``: the 256-channel
+    build's size rule and ``BE_CPNET_L3_PREPOOL``) for an even source.  Asked before anything is launched."""
+    if not x.is_cuda or not frag_eligible_c256(pc):
+        return False
+    N, Hs, Ws, _ = x.shape
+    if Hs % 2 or Ws % 2:
+        return False
+    return bool(_native.hip().be_conv_pp128_takes_prepool(N, Hs // 2, Ws // 2))
+
+
+def pp128_takes_c256(pc: PackedConv, x: torch.Tensor) -> bool:
+    """Whether :func:`fused_conv2d_c256` may be called for the conv ``pc`` on ``x`` [N, H, W, 128]: it has
+    its fragment-order weights and the native side (``be_conv_pp128_takes_c256``: the size rule over
+    (tile, half) items, ``BE_CPNET_L3_PREPOOL`` and ``BE_CONV_PP128_C256``) takes a call of ``x``'s geometry."""
+    if not x.is_cuda or not frag_eligible_c256(pc) or pc.frag_built() is None:
+        return False
+    N, H, W, _ = x.shape
+    return bool(_native.hip().be_conv_pp128_takes_c256(N, H, W))
+
+
+def pp128_pooled_entry(pc: PackedConv, x: torch.Tensor) -> int:
+    """How the entry convs of a level that reads ``x`` [N, Hs, Ws, 128] through a 2x2 max-pool run, asked of
+    the native side before anything is launched: 0, both pool in their loaders (small calls, or switched
+    off); 1, ``x`` is pooled once and both read the pooled tensor on the per-layer kernel; 2, as 1 with the
+    3x3 conv ``pc`` on the ping-pong kernel's 256-channel build (:func:`fused_conv2d_c256`)."""
+    if not pp128_takes_prepool(pc, x):
+        return 0
+    N, Hs, Ws, _ = x.shape
+    return 2 if pc.frag_built() is not None and _native.hip().be_conv_pp128_takes_c256(N, Hs // 2, Ws // 2) else 1
 
 
 def pp128_takes_pool(pc: PackedConv, x: torch.Tensor) -> bool:
@@ -214,6 +257,16 @@ def pack_frag(wp: torch.Tensor) -> torch.Tensor:
     nct = cout // 16
     t = wp.reshape(nct, 16, nchunk, 9, 4, 8)        # ct, lrow, chunk, tap, kq, e
     return t.permute(2, 3, 0, 4, 1, 5).contiguous().reshape(nchunk, 9, nct, 64, 8)
+
+
+def pack_frag_c256(wp: torch.Tensor) -> torch.Tensor:
+    """A 3x3, 128 -> 256 conv's ``PackedConv.wp`` ``[256, 4, 288]`` as two 128-channel halves, each in
+    :func:`pack_frag` order: ``[2 halves, 4 chunks, 9 taps, 8 channel tiles, 64 lanes, 8]``.  Half ``h``
+    holds output channels ``128 h .. 128 h + 127``; the 256-channel build of the ping-pong kernel computes
+    one half per work item."""
+    cout, nchunk, kp = wp.shape
+    assert cout == 256 and nchunk == 4 and kp == 288, "fragment packing: a 3x3 conv of 128 -> 256 channels"
+    return torch.stack([pack_frag(wp[:128]), pack_frag(wp[128:])]).contiguous()
 
 
 def unpack_frag(wf: torch.Tensor) -> torch.Tensor:
@@ -439,6 +492,61 @@ def fused_conv2d_pool_proj(x: torch.Tensor, pc: PackedConv, pp: PackedConv, *, s
                  _native.ptr(pc.bias), _native.ptr(out), _native.ptr(proj_scale), _native.ptr(proj_shift), _native.ptr(wpf),
                  _native.ptr(pp.bias), _native.ptr(out2), N, Hs, Ws, _native.stream(x.device))
     return out, out2
+
+
+def pool2_nhwc_ref(x: torch.Tensor) -> torch.Tensor:
+    """2x2 max-pool of an NHWC tensor with even H and W in the kernels' order,
+    ``max(max(r0, r1), max(q0, q1))`` (r: row 2y, q: row 2y + 1; 0 / 1: columns 2x, 2x + 1), where the
+    maximum of a +0 and a -0 is +0 whichever comes first, as the GPU's ``v_max_f32`` has it."""
+    def mx(p, q):
+        return torch.where((p > q) | ((p == q) & ~torch.signbit(p)), p, q)
+
+    return mx(mx(x[:, 0::2, 0::2], x[:, 0::2, 1::2]), mx(x[:, 1::2, 0::2], x[:, 1::2, 1::2])).contiguous()
+
+
+def pool2_nhwc(x: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+    """2x2 max-pool of ``x`` [N, Hs, Ws, C] (even Hs and Ws) -> [N, Hs / 2, Ws / 2, C].  On the GPU ``x``
+    is contiguous bf16 with ``C % 8 == 0`` and the HIP kernel ``be_pool2_nhwc`` runs on the current stream;
+    it forms the pooled value exactly as the conv kernels' pooled-input loaders do, so a conv that reads
+    the result equals the same conv with ``inmode="pool2"`` on ``x`` bit for bit.  CPU tensors take
+    :func:`pool2_nhwc_ref`."""
+    N, Hs, Ws, C = x.shape
+    assert Hs % 2 == 0 and Ws % 2 == 0, "pool2_nhwc needs an even source size"
+    if not x.is_cuda:
+        y = pool2_nhwc_ref(x)
+        if out is not None:
+            out.copy_(y)
+            return out
+        return y
+    assert x.dtype == torch.bfloat16 and x.is_contiguous() and C % 8 == 0, "pool2_nhwc expects contiguous NHWC bf16"
+    if out is None:
+        out = torch.empty(N, Hs // 2, Ws // 2, C, device=x.device, dtype=torch.bfloat16)
+    else:
+        assert out.shape == (N, Hs // 2, Ws // 2, C) and out.dtype == torch.bfloat16 and out.is_contiguous()
+    _native.call("be_pool2_nhwc", _native.ptr(x), _native.ptr(out), N, Hs, Ws, C, _native.stream(x.device))
+    return out
+
+
+def fused_conv2d_c256(x: torch.Tensor, pc: PackedConv, *, scale, shift, relu: bool, post_scale, post_shift,
+                      post_relu: bool) -> torch.Tensor:
+    """``fused_conv2d(x, pc, scale=scale, shift=shift, relu=relu, post_scale=post_scale,
+    post_shift=post_shift, post_relu=post_relu)`` of a 3x3, 128 -> 256 conv on the ping-pong kernel's
+    256-channel build (``be_conv_pp128_c256``), bit for bit.  ``x`` is [N, H, W, 128] bf16 on the GPU;
+    ``shift`` may be per image, the post-activation vectors are shared [256].  Ask
+    :func:`pp128_takes_c256` first: a call the kernel does not take is an error, not a fallback."""
+    N, H, W, Cin = x.shape
+    assert x.is_cuda and x.dtype == torch.bfloat16 and x.is_contiguous() and Cin == 128 == pc.cin_pad
+    assert frag_eligible_c256(pc)
+    wf = pc.frag_built()
+    assert wf is not None, "fragment-order weights are packed when the engine is built"
+    for q in (post_scale, post_shift):
+        assert q is not None and q.dtype == torch.float32 and q.is_contiguous() and q.dim() == 1 and q.numel() == 256
+    out = torch.empty(N, H, W, 256, device=x.device, dtype=torch.bfloat16)
+    _native.call("be_conv_pp128_c256", _native.ptr(x), _native.ptr(scale), _native.ptr(shift),
+                 _affine_stride(shift, N, Cin), _affine_stride(scale, N, Cin), int(bool(relu)) | (2 if post_relu else 0),
+                 _native.ptr(wf), _native.ptr(pc.bias), _native.ptr(out), _native.ptr(post_scale), _native.ptr(post_shift),
+                 N, H, W, _native.stream(x.device))
+    return out
 
 
 def depth_to_space2(y: torch.Tensor, c: int) -> torch.Tensor:

@@ -105,6 +105,10 @@ struct Args {
   // diagnostics (STAMP instantiation only, tools/pp128_phase_profile.py): [grid][2 groups][16] cycle
   // counts of wave 0 of each group
   unsigned long long* stamps;
+  // C256 build: `out` is [N, H, W, 256]; wf, bias and the post-activation vectors hold both halves
+  const float* qs = nullptr;  // post-activation scale [256]
+  const float* qt = nullptr;  // post-activation shift [256]
+  int qrelu = 0;              // ReLU after the post-activation
 };
 
 struct TileXY {
@@ -453,14 +457,74 @@ __device__ __forceinline__ void epilogue(const Args& a, TileXY t, const f32x4 (&
   }
 }
 
+// C256: P3 of one 128-channel half (`half` 0 / 1) of a 256-channel output with the per-layer kernel's
+// post-activation (post_affine in conv2d_nhwc.hip): (acc + bias) rounded to bf16, fmaf(v, qs[co],
+// qt[co]), one more rounding, ReLU (a.qrelu).  No residual, so the +0.0f goes to the bias as in
+// epilogue<0>.  The output pixel stride is 256 channels and this half's channels start at 128 half;
+// bias, qs and qt are [256].  FULL and the dropped out-of-range offsets as in epilogue().
+template <bool FULL>
+__device__ __forceinline__ void epilogue_c256(const Args& a, TileXY t, int half, const f32x4 (&acc)[2][NF], int cp, int lrow,
+                                              int kq, bool act) {
+  constexpr int CO = 2 * C;
+  const int ly = lrow >> 2, lx = lrow & 3;
+  const int co = half * C + cp * 32 + kq * 4;
+  const int img_b = a.H * a.W * CO * 2;  // host-checked: < 2^31
+  const __amdgpu_buffer_rsrc_t ro =
+      __builtin_amdgcn_make_buffer_rsrc(a.out + (size_t)t.n * a.H * a.W * CO, (short)0, img_b, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc(
+      const_cast<float*>(a.bias ? a.bias : a.qs), (short)0, a.bias ? CO * 4 : 0, 0x00020000);  // null: loads give 0
+  const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.qs), (short)0, CO * 4, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rt = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.qt), (short)0, CO * 4, 0x00020000);
+  auto voff = [&](int j, int y, int x) {
+    if constexpr (FULL) return (((t.ty0 + y) * a.W + t.tx0 + x) * CO + co) * 2;
+    const int py = t.ty0 + 4 * (j / FC) + y, px = t.tx0 + 4 * (j % FC) + x;
+    return (py < a.H && px < a.W) ? ((py * a.W + px) * CO + co) * 2 : 0x7ffffff0;
+  };
+  auto soff = [&](int j) { return FULL ? ((j / FC) * 4 * a.W + (j % FC) * 4) * CO * 2 : 0; };
+  f32x4 bias[2], qs[2], qt[2];
+#pragma unroll
+  for (int ct = 0; ct < 2; ++ct) {
+    bias[ct] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rb, (co + ct * 16) * 4, 0, 0));
+    qs[ct] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, (co + ct * 16) * 4, 0, 0));
+    qt[ct] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rt, (co + ct * 16) * 4, 0, 0));
+    bias[ct] = bias[ct] + (f32x4){0.f, 0.f, 0.f, 0.f};
+  }
+  const bool qrelu = a.qrelu != 0;
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int j = 0; j < NF; ++j) {
+    const int o = act ? voff(j, ly, lx) : 0x7ffffff0;
+#pragma unroll
+    for (int ct = 0; ct < 2; ++ct) {
+      const uint32_t p0 = pack2bf(acc[ct][j][0] + bias[ct][0], acc[ct][j][1] + bias[ct][1]);
+      const uint32_t p1 = pack2bf(acc[ct][j][2] + bias[ct][2], acc[ct][j][3] + bias[ct][3]);
+      u32x2 st;
+      st[0] = pack2bf(fmaf(lo_bf(p0), qs[ct][0], qt[ct][0]), fmaf(hi_bf(p0), qs[ct][1], qt[ct][1]));
+      st[1] = pack2bf(fmaf(lo_bf(p1), qs[ct][2], qt[ct][2]), fmaf(hi_bf(p1), qs[ct][3], qt[ct][3]));
+      if (qrelu) {
+        st[0] = relu_bf16x2(st[0]);
+        st[1] = relu_bf16x2(st[1]);
+      }
+      __builtin_amdgcn_raw_buffer_store_b64(st, ro, o + ct * 32, soff(j), 0);
+    }
+  }
+}
+
 // POOL: the level-2 entry conv, 64 -> 128 channels: x is [N, 2 H, 2 W, 64] and is read through a 2 x 2
 // max-pool (conv2d_nhwc_kernel's INMODE 2), two 32-channel chunks (six phases per tile), weights
 // [2 chunks][9 taps][8 ct] in the same fragment order, no residual.  PROJ (with POOL): the level's 1x1
 // projection of the same pooled pixels as a second output (Args::out2), computed after the epilogue on
 // the freed accumulators.
-template <bool STAMP = false, bool POOL = false, bool PROJ = false>
+//
+// C256 (without POOL): 128 -> 256 channels as two 128-channel halves (CPnet's level-3 entry conv on the
+// pooled tensor, conv2d_nhwc_kernel<3, 32, 64, 0, ...> with its post-activation bit for bit).  A work
+// item is (tile, half): item i is half i & 1 of tile i >> 1, so the two halves of a tile are consecutive
+// items, one per group, and the second finds the input in the cache.  Weights are [2 halves][4 chunks]
+// [9 taps][8 ct] (each half in the 128 -> 128 fragment order); the epilogue is epilogue_c256.
+template <bool STAMP = false, bool POOL = false, bool PROJ = false, bool C256 = false>
 __global__ __launch_bounds__(NTP, 2) void conv_pp128_kernel(Args a) {
   static_assert(POOL || !PROJ, "the projection reads the pooled input");
+  static_assert(!(POOL && C256), "the 256-channel build reads a plain 128-channel input");
   constexpr int NC = POOL ? 2 : NCH;
   // STAMP: as conv_pair_pp64_kernel; slots: commit / MFMA of chunk 0, of chunks 1..3 together, epilogue;
   // work cycles of slot i at i, the wait at its closing barrier at 8 + i, iterations at 15
@@ -483,7 +547,8 @@ __global__ __launch_bounds__(NTP, 2) void conv_pp128_kernel(Args a) {
   auto slot = [](int c) { return c > 0 ? 2 : 0; };
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid0 = threadIdx.x;
-  const int total = a.N * a.tiles_x * a.tiles_y;
+  const int total = a.N * a.tiles_x * a.tiles_y * (C256 ? 2 : 1);  // work items
+  auto tile_at = [&](int item) { return tile_of(a, C256 ? item >> 1 : item); };
   const int t0 = (int)(((long long)blockIdx.x * total) / gridDim.x);
   const int t1 = (int)(((long long)(blockIdx.x + 1) * total) / gridDim.x);
   if (t0 >= t1) return;  // workgroup-uniform
@@ -492,8 +557,8 @@ __global__ __launch_bounds__(NTP, 2) void conv_pp128_kernel(Args a) {
   unsigned char* reg = smem + grp * IN_B;
   unsigned char* rpj = PROJ ? smem + LDS + grp * PJ_B : nullptr;
   Halo<POOL> halo;
-  issue_halo(a, tile_of(a, min(t0 + grp, t1 - 1)), 0, gt0, halo);
-  if constexpr (POOL) issue_halo_b(a, tile_of(a, min(t0 + grp, t1 - 1)), 0, gt0, halo);
+  issue_halo(a, tile_at(min(t0 + grp, t1 - 1)), 0, gt0, halo);
+  if constexpr (POOL) issue_halo_b(a, tile_at(min(t0 + grp, t1 - 1)), 0, gt0, halo);
   if constexpr (PROJ) issue_affp(a, 0, gt0, halo);
   if (grp == 1) __builtin_amdgcn_s_barrier();  // the stagger: group 1 runs one phase behind
   const int iters = (t1 - t0 + 1) >> 1;
@@ -505,8 +570,8 @@ __global__ __launch_bounds__(NTP, 2) void conv_pp128_kernel(Args a) {
     // a group without a tile in the last iteration (odd range) recomputes the range's last tile and
     // stores nothing
     const bool act = t < t1;
-    const TileXY cur = tile_of(a, act ? t : t1 - 1);
-    const bf16_t* wl = w_lane(a.wf, cp, lane);
+    const TileXY cur = tile_at(act ? t : t1 - 1);
+    const bf16_t* wl = w_lane(C256 ? a.wf + ((act ? t : t1 - 1) & 1) * (NCH * 9 * WSTEP) : a.wf, cp, lane);
     int A0[3];
 #pragma unroll
     for (int dx = 0; dx < 3; ++dx) {
@@ -551,7 +616,7 @@ __global__ __launch_bounds__(NTP, 2) void conv_pp128_kernel(Args a) {
       if (c + 1 < NC)
         issue_halo(a, cur, c + 1, gc, halo);
       else
-        issue_halo(a, tile_of(a, min(t + 2, t1 - 1)), 0, gc, halo);
+        issue_halo(a, tile_at(min(t + 2, t1 - 1)), 0, gc, halo);
       issue_w(wl + c * 9 * WSTEP, wpre);
       pre(slot(c));
       __syncthreads();
@@ -572,7 +637,7 @@ __global__ __launch_bounds__(NTP, 2) void conv_pp128_kernel(Args a) {
       // the second half of the next tile's first halo travels during the epilogue and the barrier wait
       // (PROJ: during the barrier wait only; the projection needs the accumulators' registers once more)
       if constexpr (!PROJ) {
-        issue_halo_b(a, tile_of(a, min(t + 2, t1 - 1)), 0, g3, halo);
+        issue_halo_b(a, tile_at(min(t + 2, t1 - 1)), 0, g3, halo);
         __builtin_amdgcn_sched_barrier(0);
       }
       if (full)
@@ -592,9 +657,15 @@ __global__ __launch_bounds__(NTP, 2) void conv_pp128_kernel(Args a) {
         else
           epilogue<0, false>(b, cur, acc, cp, g4 & 15, (g4 & 63) >> 4, act);
         __builtin_amdgcn_sched_barrier(0);
-        issue_halo_b(a, tile_of(a, min(t + 2, t1 - 1)), 0, g4, halo);
+        issue_halo_b(a, tile_at(min(t + 2, t1 - 1)), 0, g4, halo);
         issue_affp(a, 0, g4, halo);
       }
+    } else if constexpr (C256) {
+      const int half = (act ? t : t1 - 1) & 1;
+      if (full)
+        epilogue_c256<true>(a, cur, half, acc, cp, g3 & 15, (g3 & 63) >> 4, act);
+      else
+        epilogue_c256<false>(a, cur, half, acc, cp, g3 & 15, (g3 & 63) >> 4, act);
     } else if (a.res != nullptr && a.res_up2) {
       if (full)
         epilogue<2, true>(a, cur, acc, cp, g3 & 15, (g3 & 63) >> 4, act);
@@ -658,6 +729,21 @@ int g_pp128_pool_proj = [] {
   return e ? atoi(e) : 1;
 }();
 
+// BE_CPNET_L3_PREPOOL (default 1, A/B): 0 makes be_conv_pp128_takes_prepool answer 0, so CPnet's level-3
+// entry keeps its two pooled-input launches of the per-layer kernel
+int g_l3_prepool = [] {
+  const char* e = getenv("BE_CPNET_L3_PREPOOL");
+  return e ? atoi(e) : 1;
+}();
+
+// BE_CONV_PP128_C256 (default 1, A/B): 0 makes be_conv_pp128_takes_c256 answer 0, so the 128 -> 256
+// entry conv of a pre-pooled level stays on conv2d_nhwc_kernel
+int g_pp128_c256 = [] {
+  const char* e = getenv("BE_CONV_PP128_C256");
+  return e ? atoi(e) : 1;
+}();
+
+int g_pp128_c256_launches = 0;  // be_conv_pp128_c256_launches
 int g_pp128_grid = 0;      // be_conv_pp128_set_grid (0 = one workgroup per CU)
 int g_pp128_launches = 0;  // be_conv_pp128_launches
 int g_pp128_pool_launches = 0;  // be_conv_pp128_pool_launches
@@ -667,10 +753,12 @@ int g_pp128_stamps_cap = 0;                    // workgroups the stamp buffer ho
 // The size rule, in one place: the grid on which a 3x3 128 -> 128 call of N images of H x W runs on
 // conv_pp128_kernel, or 0 when it stays on the per-layer kernel (switched off, too few tiles for the
 // grid that is not forced, or too large for 32-bit offsets).
-int pp128_grid_for(int N, int H, int W, int* tiles_x, int* tiles_y) {
-  if (!g_pp128 || N <= 0 || H <= 0 || W <= 0 || (long long)H * W * 256 >= (1LL << 31) - 64) return 0;
+// halves = 2: the 256-channel build, whose work items are (tile, 128-channel half) and whose output
+// image is twice as large; the rule then counts items where it counts tiles.
+int pp128_grid_for(int N, int H, int W, int* tiles_x, int* tiles_y, int halves = 1) {
+  if (!g_pp128 || N <= 0 || H <= 0 || W <= 0 || (long long)H * W * 256 * halves >= (1LL << 31) - 64) return 0;
   const int tx = (W + pp128::TW - 1) / pp128::TW, ty = (H + pp128::TH - 1) / pp128::TH;
-  const long long tiles = (long long)N * tx * ty;
+  const long long tiles = (long long)N * tx * ty * halves;
   const bool forced = g_pp128_grid > 0;
   const int g = forced ? (int)(tiles < g_pp128_grid ? tiles : g_pp128_grid) : 256;
   if (!(forced || tiles >= 2LL * g) || tiles >= (1LL << 30)) return 0;
@@ -848,6 +936,66 @@ int be_conv_pp128_pool_proj(const void* x, const float* pscale, const float* psh
     return BE_CHECK_LAUNCH();
   }
   hipLaunchKernelGGL((pp128::conv_pp128_kernel<false, true, true>), dim3(g), dim3(pp128::NTP), pp128::LDS_PROJ, stream, a);
+  return BE_CHECK_LAUNCH();
+}
+
+// The size rule of the 256-channel build, in one place: pp128_grid_for with the item count (tiles x 2
+// halves) in place of the tile count.
+static int pp128_c256_grid_for(int N, int H, int W, int* tiles_x, int* tiles_y) {
+  return pp128_grid_for(N, H, W, tiles_x, tiles_y, 2);
+}
+
+// 1 if a level whose entry convs read a 2x2 max-pool of N source images (pooled size H x W, 128
+// channels) should pool once into a tensor of its own (be_pool2_nhwc) and run both entry convs on it:
+// the size rule of the 256-channel build and BE_CPNET_L3_PREPOOL.  Small calls (batch-1 requests) keep
+// the pooled-input launches of the per-layer kernel.
+int be_conv_pp128_takes_prepool(int N, int H, int W) {
+  return g_l3_prepool && pp128_c256_grid_for(N, H, W, nullptr, nullptr) > 0 ? 1 : 0;
+}
+
+// 1 if be_conv_pp128_c256 takes N images of H x W now: be_conv_pp128_takes_prepool and BE_CONV_PP128_C256.
+int be_conv_pp128_takes_c256(int N, int H, int W) { return g_pp128_c256 && be_conv_pp128_takes_prepool(N, H, W); }
+
+// Tests / A/B runs in one process: the two switches that BE_CPNET_L3_PREPOOL and BE_CONV_PP128_C256 set
+// when the library is loaded.
+int be_conv_pp128_set_c256(int prepool, int c256) {
+  g_l3_prepool = prepool;
+  g_pp128_c256 = c256;
+  return 0;
+}
+
+// Launches of the 256-channel build by this process so far; neither be_conv_pp128_launches nor
+// be_conv_pp128_pool_launches counts them.
+int be_conv_pp128_c256_launches() { return g_pp128_c256_launches; }
+
+// 3x3 conv, 128 -> 256 channels, of x [N, H, W, 128] bf16 NHWC with the consumer's pre-activation applied
+// to the stored value (CPnet's level-3 entry conv on the pooled tensor):
+//   out = relu?( bf16( conv3x3( relu?( x * pscale + pshift[n] ) ) + bias ) * qscale + qshift )   [N, H, W, 256]
+// bit for bit what be_conv2d_nhwc gives (INMODE 0, ck 32) with the same qscale / qshift [256] and prelu
+// (bit 0: input ReLU, bit 1: output ReLU).  wfrag: the two 128-channel halves of the conv, each in
+// pack_frag order, [2][4][9][8][64][8] (ops/conv.py, pack_frag_c256).  The caller asks
+// be_conv_pp128_takes_c256 first: a call the kernel does not take is an error (-34), not a fallback.
+int be_conv_pp128_c256(const void* x, const float* pscale, const float* pshift, int pshift_ns, int pscale_ns, int prelu,
+                       const void* wfrag, const float* bias, void* out, const float* qscale, const float* qshift, int N,
+                       int H, int W, hipStream_t stream) {
+  if (!x || !wfrag || !out || x == out || !qscale || !qshift || (prelu & ~3)) return -34;
+  if (!be_conv_pp128_takes_c256(N, H, W)) return -34;
+  pp128::Args a;
+  const int g = pp128_c256_grid_for(N, H, W, &a.tiles_x, &a.tiles_y);
+  a.x = (const bf16_t*)x; a.sa = pscale; a.ta = pshift; a.sa_ns = pscale_ns; a.ta_ns = pshift_ns;
+  a.wf = (const bf16_t*)wfrag; a.bias = bias; a.res = nullptr; a.out = (bf16_t*)out;
+  a.N = N; a.H = H; a.W = W; a.relu = prelu & 1;
+  a.res_up2 = 0;
+  a.sp = a.tp = a.bias_p = nullptr; a.wpf = nullptr; a.out2 = nullptr;
+  a.qs = qscale; a.qt = qshift; a.qrelu = (prelu >> 1) & 1;
+  a.stamps = g_pp128_stamps;
+  ++g_pp128_c256_launches;
+  if (g_pp128_stamps != nullptr) {  // diagnostics: be_conv_pp128_set_stamps
+    if (g > g_pp128_stamps_cap) return -30;
+    hipLaunchKernelGGL((pp128::conv_pp128_kernel<true, false, false, true>), dim3(g), dim3(pp128::NTP), pp128::LDS, stream, a);
+    return BE_CHECK_LAUNCH();
+  }
+  hipLaunchKernelGGL((pp128::conv_pp128_kernel<false, false, false, true>), dim3(g), dim3(pp128::NTP), pp128::LDS, stream, a);
   return BE_CHECK_LAUNCH();
 }
 

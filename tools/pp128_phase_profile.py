@@ -7,7 +7,9 @@ One call at the headline's level-2 shape (288 tiles of 56^2 x 128 channels), wit
 residual; one JSON line each with cycles per iteration (= 2 tiles of 8 x 28 pixels; mean over
 workgroups).  commit1 / mma1 are the chunks 1..3 together.  --pool: the pooled 64 -> 128 builds instead
 (the level-2 entry conv from 288 x 112^2 x 64, alone and with the 1x1 projection inside; commit1 / mma1
-are chunk 1, epi includes the projection).  Usage: python tools/pp128_phase_profile.py [--pool]"""
+are chunk 1, epi includes the projection).  --c256: the 128 -> 256 build (the level-3 entry conv on the
+pooled tensor, 288 x 28^2 x 128; an iteration is the two halves of one tile).
+Usage: python tools/pp128_phase_profile.py [--pool | --c256]"""
 from __future__ import annotations
 
 import argparse
@@ -31,11 +33,14 @@ def main():
     ap.add_argument("--tiles", type=int, default=288)
     ap.add_argument("--hw", type=int, default=56)
     ap.add_argument("--pool", action="store_true")
+    ap.add_argument("--c256", action="store_true")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
     if args.pool:
         return pool(args, dev)
+    if args.c256:
+        return c256(args, dev)
     pc = PackedConv.from_weight(torch.randn(128, 128, 3, 3) / 34.0, 0.1 * torch.randn(128)).to(dev)
     pc.frag()
     x = torch.randn(args.tiles, args.hw, args.hw, 128, device=dev).bfloat16()
@@ -100,6 +105,34 @@ def pool(args, dev):
         if _native.hip().be_conv_pp128_pool_launches() - n0 != 2:
             raise SystemExit("the call did not reach the pooled build")
         report({"build": name}, buf, cap)
+
+
+def c256(args, dev):
+    pc = PackedConv.from_weight(torch.randn(256, 128, 3, 3) / 34.0, 0.1 * torch.randn(256)).to(dev)
+    pc.frag()
+    hw = 28 if args.hw == 56 else args.hw
+    x = torch.randn(args.tiles, hw, hw, 128, device=dev).bfloat16()
+    aff = [(1 + 0.1 * torch.randn(c, device=dev)).float() for c in (128, 128, 256, 256)]
+    if not cv.pp128_takes_c256(pc, x):
+        raise SystemExit("the native side does not take the 256-channel call at this size")
+
+    def fn():
+        return cv.fused_conv2d_c256(x, pc, scale=aff[0], shift=aff[1], relu=True, post_scale=aff[2], post_shift=aff[3],
+                                    post_relu=True)
+
+    cap = 1024
+    buf = torch.zeros(cap * 32, dtype=torch.int64, device=dev)
+    n0 = _native.hip().be_conv_pp128_c256_launches()
+    fn()  # warm
+    _native.call("be_conv_pp128_set_stamps", _native.ptr(buf), cap)
+    try:
+        fn()
+        torch.cuda.synchronize()
+    finally:
+        _native.call("be_conv_pp128_set_stamps", None, 0)
+    if _native.hip().be_conv_pp128_c256_launches() - n0 != 2:
+        raise SystemExit("the call did not reach the 256-channel build")
+    report({"build": "c256", "hw": hw}, buf, cap)
 
 
 if __name__ == "__main__":
