@@ -179,6 +179,30 @@ def measurement_items(table: dict, json_safe: bool) -> dict:
     return {"measurements": table, "diameter_px": float(table["diameter_px"])}
 
 
+OUTLINE_FORMATS = ("rings", "geojson")
+
+
+def outline_items(rings: dict, fmt: str, z: int | None = None):
+    """The ``outlines`` entry of one image (or plane ``z``) of an ``infer`` result, plain Python values
+    either way.  ``"rings"``: one ``{label, rings, area2}`` per label, ``rings`` the label's closed
+    rings as lists of ``[x, y]`` pixel corners (turn vertices only, the first not repeated) and
+    ``area2`` their signed doubled areas (positive: outer ring, negative: hole); for a plane of a
+    stack the list is wrapped as ``{z, outlines}``.  ``"geojson"``: the ``FeatureCollection`` of
+    :func:`reference.rings_to_geojson` (``z`` in every feature's properties)."""
+    from bioengine_worker_amd.cellpose import reference as ref
+
+    if fmt == "geojson":
+        return ref.rings_to_geojson(rings, z)
+    off, verts = rings["ring_offsets"].tolist(), rings["verts"][:, ::-1].tolist()
+    out = []
+    for r, (lab, a2) in enumerate(zip(rings["ring_label"].tolist(), rings["ring_area2"].tolist())):
+        if not out or out[-1]["label"] != lab:
+            out.append({"label": lab, "rings": [], "area2": []})
+        out[-1]["rings"].append(verts[off[r]:off[r + 1]])
+        out[-1]["area2"].append(a2)
+    return out if z is None else {"z": int(z), "outlines": out}
+
+
 def _diameter_arg(diameter):
     """The ``diameter`` of a request: ``None``, a float, or the string ``"auto"``."""
     diameter = _opt(diameter)
@@ -356,8 +380,9 @@ class CellposeFinetune:
     # ------------------------------------------------------------------ inference (continuous batching)
     @serve.batch(max_batch_size=32, batch_wait_timeout_s=0.005, max_concurrent_batches=2)
     async def _segment_batch(self, reqs: list) -> list:
-        """reqs: [(model_id, image CHW, params dict, want_flows[, want_measure])] -> [(masks, flows | None,
-        measurement table | None)], with the diameter used as a fourth entry under ``diameter="auto"``.
+        """reqs: [(model_id, image CHW, params dict, want_flows[, want_measure[, want_outlines]])] -> [(masks,
+        flows | None, measurement table | None, outline rings | None)], with the diameter used as a fifth
+        entry under ``diameter="auto"``.
 
         A numeric ``diameter`` is not part of the grouping key: requests that differ only in it share
         a batch, and the runner gets the list of their diameters (the one number when they all agree,
@@ -384,6 +409,7 @@ class CellposeFinetune:
             flows_needed = any(reqs[i][3] for i in idxs)
             # like want_flows, not part of the grouping key: the batch measures if any request asks
             measure_needed = any(len(reqs[i]) > 4 and reqs[i][4] for i in idxs)
+            outline_needed = any(len(reqs[i]) > 5 and reqs[i][5] for i in idxs)  # the same rule
 
             def run():
                 import torch
@@ -410,7 +436,8 @@ class CellposeFinetune:
                 with trace.span("app.d2h", images=len(idxs)):
                     if not m.is_cuda:
                         tabs = runner.measure(m, batch) if measure_needed else None
-                        return m.numpy(), (f.numpy() if flows_needed else None), tabs
+                        rings = runner.outlines(m) if outline_needed else None
+                        return m.numpy(), (f.numpy() if flows_needed else None), tabs, rings
                     if getattr(self, "_d2h_stream", None) is None:
                         self._d2h_stream = torch.cuda.Stream(m.device)
                     st = self._d2h_stream
@@ -444,22 +471,40 @@ class CellposeFinetune:
                             rh = {k: v.to("cpu", non_blocking=True) for k, v in raws.items()}
                             for t in list(raws.values()) + [batch]:
                                 t.record_stream(st)
+                        oh_rings = None
+                        if outline_needed:
+                            # traced where the measurements run: on the copy stream, behind the masks'
+                            # ready event, outside the network lock.  Its two reads (vertex and ring
+                            # count) wait for this stream only; the arrays come back with the masks.
+                            from bioengine_worker_amd.cellpose.pipeline import outline_launch
+
+                            oraws = outline_launch(m, nlab=getattr(m, "label_bound", None))
+                            oh_rings = {k: v.to("cpu", non_blocking=True) for k, v in oraws.items()}
+                            for t in oraws.values():
+                                t.record_stream(st)
                         for t in (m, m16) + ((over,) if over is not None else ()) + ((f,) if f is not None else ()):
                             t.record_stream(st)
                     st.synchronize()
+                    rings = None
+                    if oh_rings is not None:
+                        from bioengine_worker_amd.cellpose.pipeline import outline_rings
+
+                        rings = outline_rings(oh_rings)
                     tabs = None
                     if rh is not None:
                         from bioengine_worker_amd.cellpose.pipeline import measure_tables
 
                         tabs = measure_tables(rh)
                     if oh is not None and bool(oh[0]):  # more than 65535 objects in an image: int32 labels
-                        return m.cpu().numpy(), (fh.numpy() if fh is not None else None), tabs
-                    return mh.numpy().view(np.uint16), (fh.numpy() if fh is not None else None), tabs
+                        return m.cpu().numpy(), (fh.numpy() if fh is not None else None), tabs, rings
+                    return mh.numpy().view(np.uint16), (fh.numpy() if fh is not None else None), tabs, rings
 
-            masks, flows, tabs = await offload(run)
+            masks, flows, tabs, rings = await offload(run)
             for j, i in enumerate(idxs):
                 want = tabs is not None and len(reqs[i]) > 4 and reqs[i][4]
-                out[i] = (masks[j], flows[j] if flows is not None and reqs[i][3] else None, tabs[j] if want else None)
+                want_rings = rings is not None and len(reqs[i]) > 5 and reqs[i][5]
+                out[i] = (masks[j], flows[j] if flows is not None and reqs[i][3] else None, tabs[j] if want else None,
+                          rings[j] if want_rings else None)
                 if auto:
                     out[i] += (used["d"][j],)
         return out
@@ -531,8 +576,13 @@ class CellposeFinetune:
                                                                 "cellpose's keys (percentile, lowhigh, invert, "
                                                                 "tile_norm_blocksize, norm3D). Default: what the "
                                                                 "session named as model was trained with, else True."),
+        return_outlines: bool = Field(False, description="Also return every cell's outline as polygon rings of "
+                                                         "pixel-corner coordinates (exactly the mask's boundary)."),
+        outline_format: str = Field("rings", description="Form of the outlines: 'rings' (per label: rings of [x, y] "
+                                                         "and their signed doubled areas) or 'geojson' (a "
+                                                         "FeatureCollection of Polygon / MultiPolygon features)."),
     ) -> list:
-        """Segment images; returns one {input_path, output(, flows)(, measurements, diameter_px)} per image.  With ``z_axis``,
+        """Segment images; returns one {input_path, output(, flows)(, measurements, diameter_px)(, outlines)} per image.  With ``z_axis``,
         ``stitch_threshold > 0`` or ``do_3D`` every input array is one z-stack and ``output`` is
         [Z, H, W].  ``do_3D`` with ``return_flows``: ``flows`` is [per-plane RGB of (dY, dX), dP
         [3, Z', H, W] (dZ, dY, dX), cellprob [Z', H, W]], ``Z'`` the depth after ``anisotropy``.
@@ -546,7 +596,11 @@ class CellposeFinetune:
         key: requests that differ only in it share a batch, each image rescaled by its own.
         ``diameter="auto"`` (plane mode only; its own batching group) estimates every image's diameter
         from a first pass and segments the images that need it again at that size; each item then
-        carries ``diameter_px``, the diameter used, with or without ``return_measurements``."""
+        carries ``diameter_px``, the diameter used, with or without ``return_measurements``.
+        ``return_outlines``: ``outlines`` holds the cells' outlines in ``outline_format`` (see
+        :func:`outline_items`), the same with and without ``json_safe``; for a z-stack a list with one
+        entry per plane, ``z`` recorded.  Like ``return_measurements`` it is not in the batching key:
+        a batch traces if any of its requests asks and only those get the field."""
         if isinstance(artifact, dict):
             w = artifact
             artifact = w.get("artifact", w.get("artifact_id", w.get("id")))
@@ -560,7 +614,13 @@ class CellposeFinetune:
             do_3D, anisotropy = w.get("do_3D", do_3D), w.get("anisotropy", anisotropy)
             return_measurements = w.get("return_measurements", return_measurements)
             augment, normalize = w.get("augment", augment), w.get("normalize", normalize)
+            return_outlines = w.get("return_outlines", return_outlines)
+            outline_format = w.get("outline_format", outline_format)
         return_measurements = bool(_opt(return_measurements) or False)
+        return_outlines = bool(_opt(return_outlines) or False)
+        outline_format = _opt(outline_format) or "rings"
+        if outline_format not in OUTLINE_FORMATS:
+            raise ValueError(f"outline_format must be one of {OUTLINE_FORMATS}, got {outline_format!r}")
         stitch_threshold = float(_opt(stitch_threshold) or 0.0)
         z_axis = _opt(z_axis)
         if not 0.0 <= stitch_threshold <= 1.0:
@@ -598,7 +658,8 @@ class CellposeFinetune:
                "augment": bool(_opt(augment) or False), **self._norm_prm(model_id, normalize)}
         if stack_mode:
             out = await self._infer_stacks(runner, names, images, prm, stitch_threshold, int(z_axis or 0),
-                                           bool(return_flows), bool(json_safe), do_3D, anisotropy, return_measurements)
+                                           bool(return_flows), bool(json_safe), do_3D, anisotropy, return_measurements,
+                                           outline_format if return_outlines else None)
             if self._weights.get(model_id) == "random" and out:
                 out[0]["weights"] = "random"
             return out
@@ -606,15 +667,18 @@ class CellposeFinetune:
         chw = [image_for_batch(im, runner.nchan, on_gpu) for im in images]
         with trace.span("app.batched", images=len(chw)):
             if len(chw) == 1:
-                res = [await self._segment_batch((model_id, chw[0], prm, bool(return_flows), return_measurements))]
+                res = [await self._segment_batch((model_id, chw[0], prm, bool(return_flows), return_measurements,
+                                                  return_outlines))]
             else:
                 res = await asyncio.gather(*[self._segment_batch((model_id, c, prm, bool(return_flows),
-                                                                  return_measurements)) for c in chw])
+                                                                  return_measurements, return_outlines)) for c in chw])
         out = []
-        for name, (m, f, tab, *used) in zip(names, res):
+        for name, (m, f, tab, rings, *used) in zip(names, res):
             item = {"input_path": name, "output": mask_png_payload(m) if json_safe else m}
             if return_measurements:
                 item.update(measurement_items(tab, bool(json_safe)))
+            if return_outlines:
+                item["outlines"] = outline_items(rings, outline_format)
             if used:  # diameter="auto": the diameter this image was segmented at
                 item["diameter_px"] = float(used[0])
             if return_flows:
@@ -627,7 +691,8 @@ class CellposeFinetune:
 
     async def _infer_stacks(self, runner, names: list, stacks: list, prm: dict, stitch_threshold: float, z_axis: int,
                             return_flows: bool, json_safe: bool, do_3D: bool = False,
-                            anisotropy: float | None = None, return_measurements: bool = False) -> list:
+                            anisotropy: float | None = None, return_measurements: bool = False,
+                            outline_format: str | None = None) -> list:
         """Stack mode of :meth:`infer`: every array is one z-stack ([Z,H,W], [Z,C,H,W] or [Z,H,W,C] once
         ``z_axis`` is moved to the front); its planes are one batch of ``runner.eval_stack`` (no
         continuous batching across requests), stitched on the device.  ``do_3D`` routes the stack to
@@ -652,15 +717,19 @@ class CellposeFinetune:
                         m, f, _ = runner.eval_stack(a, stitch_threshold=stitch_threshold, **prm)
                     # the final labels as one volume, against the stack as given (not resampled)
                     tab = runner.measure(m, a, volume=True) if return_measurements else None
+                    # per plane, with the volume's labels (None: outlines were not asked for)
+                    rings = runner.outlines(m, volume=True) if outline_format else None
                     m = m.cpu().numpy()
-                    return m, (f.cpu().numpy() if return_flows else None), tab
+                    return m, (f.cpu().numpy() if return_flows else None), tab, rings
 
             with trace.span("app.stack_eval", planes=int(a.shape[0])):
-                m, f, tab = await offload(run)
+                m, f, tab, rings = await offload(run)
             m = m.astype(np.uint16) if int(m.max(initial=0)) < 65536 else m.astype(np.int32)
             item = {"input_path": name, "output": [mask_png_payload(pl) for pl in m] if json_safe else m}
             if return_measurements:
                 item.update(measurement_items(tab, json_safe))
+            if rings is not None:
+                item["outlines"] = [outline_items(r, outline_format, z) for z, r in enumerate(rings)]
             if return_flows:
                 if do_3D:  # f [4, Z', H, W] (dZ, dY, dX, cellprob)
                     fl = [np.stack([flow_rgb(f[1:3, z]) for z in range(f.shape[1])]), f[:3], f[3]]

@@ -1,6 +1,6 @@
 """GPU (HIP) implementation of Cellpose pre/post-processing on batches of images.
 
-Every heavy step is a kernel in ``csrc/kernels/{tiles,cellpose_dynamics,cellpose_dynamics3d,cellpose_masks,cellpose_stitch,cellpose_measure,cellpose_ap}.hip``;
+Every heavy step is a kernel in ``csrc/kernels/{tiles,cellpose_dynamics,cellpose_dynamics3d,cellpose_masks,cellpose_stitch,cellpose_measure,cellpose_ap,cellpose_rings}.hip``;
 torch is only used for tiny bookkeeping (sorting the seed keys, prefix sums over labels, building
 per-mask job lists).  The semantics are those of :mod:`bioengine_worker_amd.cellpose.reference`
 (the CPU oracle), which the GPU tests compare against.
@@ -1412,6 +1412,112 @@ def measure_masks_gpu(M: torch.Tensor, img: torch.Tensor | None = None, nlab: in
     if outlines:
         res["outlines"] = edge.bool()
     return res
+
+
+# ------------------------------------------------------------------ outlines: polygon rings
+
+
+def _check_rings(B: int, H: int, W: int) -> None:
+    """Vertex coordinates and the ``area2`` terms ``x * y`` stay far inside their types up to 2^15
+    rows and columns; the corner pass indexes the batch's ``B (H + 1)(W + 1)`` corners in 32 bits."""
+    if max(H, W) > 2 ** 15:
+        raise ValueError(f"mask_rings_gpu: image {H} x {W} is too large (H and W must not exceed 2^15)")
+    if B * (H + 1) * (W + 1) >= 2 ** 31:
+        raise ValueError(f"mask_rings_gpu: batch {B} x {H} x {W} is too large (B*(H+1)*(W+1) must be below 2^31)")
+
+
+def _rings_result(verts, off, lab, area2, img, per_image) -> dict:
+    return {"verts": verts, "ring_offsets": off, "ring_label": lab, "ring_area2": area2, "ring_image": img,
+            "image_rings": per_image}
+
+
+def _rings_empty(B: int, dev) -> dict:
+    z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)
+    return _rings_result(z((0, 2), torch.int32), z(1, torch.int64), z(0, torch.int32), z(0, torch.int64),
+                         z(0, torch.int32), z(B + 1, torch.int64))
+
+
+def _rings_oracle(M: torch.Tensor, K: int) -> dict:
+    """CPU tensors: :func:`reference.mask_rings` per image, joined into the batch's arrays."""
+    parts, nv, counts = [], 0, [0]
+    for b, m in enumerate(M.numpy()):
+        r = ref.mask_rings(np.where(m > K, 0, m))
+        n = r["ring_label"].shape[0]
+        parts.append((r["verts"], r["ring_offsets"][:-1] + nv, r["ring_label"], r["ring_area2"], np.full(n, b, np.int32)))
+        nv += r["verts"].shape[0]
+        counts.append(counts[-1] + n)
+    v, off, lab, a2, img = (np.concatenate([p[j] for p in parts]) for j in range(5))
+    off = np.concatenate([off, [nv]]).astype(np.int64)
+    return _rings_result(*(torch.from_numpy(np.ascontiguousarray(x)) for x in (v, off, lab, a2, img)),
+                         torch.tensor(counts, dtype=torch.int64))
+
+
+def _host_ints(t: torch.Tensor) -> list:
+    """One device-to-host read of a small integer tensor (waits for the current stream)."""
+    return [int(v) for v in t.tolist()]
+
+
+def mask_rings_gpu(M: torch.Tensor, nlab: int | None = None, volume: bool = False) -> dict:
+    """Outlines of label images as closed rings of pixel-corner coordinates, traced on the device:
+    HIP implementation of :func:`reference.mask_rings` (``csrc/kernels/cellpose_rings.hip``), equal
+    to it in every array and bit-identical from run to run.
+
+    ``M`` [B, H, W] labels; with ``volume=True`` ``M`` is one [Z, H, W] volume read as Z planes:
+    outlines are per plane, with the volume's labels.  Returns device tensors for the whole batch:
+    the oracle's ``verts`` int32 [V, 2] (y, x), ``ring_offsets`` int64 [R + 1], ``ring_label`` int32
+    [R] and ``ring_area2`` int64 [R], plus ``ring_image`` int32 [R] (the image, or z) and
+    ``image_rings`` int64 [B + 1] (image ``b`` owns rings ``image_rings[b]:image_rings[b + 1]``);
+    rings are ordered by (image, label, start).  ``nlab``: optional upper bound on the labels + 1, as
+    the sibling wrappers take it (saves the ``M.max()`` sync; labels above the bound are not
+    traced).  Two values are read back, ``V`` after the count and ``R`` (with the error word) after
+    the trace; an empty batch, ``K = 0`` and ``V = 0`` return before the reads they do not need.
+    Raises ``RuntimeError`` when a walk ran out of its counted edges, vertices or ring slots (labels
+    that changed under the kernel).  Runs on the current stream.  CPU tensors run the oracle."""
+    if M.dim() != 3:
+        raise ValueError(f"mask_rings_gpu expects [B, H, W] masks (or one [Z, H, W] volume), got {tuple(M.shape)}")
+    B, H, W = M.shape
+    _check_rings(B, H, W)
+    dev = M.device
+    if M.numel() == 0:
+        return _rings_empty(B, dev)
+    if nlab is None:
+        nlab = int(M.max().item()) + 1
+    K = max(int(nlab) - 1, 0)
+    if K == 0:
+        return _rings_empty(B, dev)
+    if dev.type != "cuda":
+        return _rings_oracle(M, K)
+    Mc = M.to(torch.int32).contiguous()
+    n = B * K
+    # per label: corner box, vertices, rings | its segments of verts and of the ring table, its first
+    # ring in the result, then the totals (V, ring table size, R, error word)
+    w32 = torch.empty(6 * n, dtype=torch.int32, device=dev)
+    bbox, nvert, nrings = w32[:4 * n], w32[4 * n:5 * n], w32[5 * n:]
+    w64 = torch.empty(3 * n + 4, dtype=torch.int64, device=dev)
+    voff, roff, rstart, totals = w64[:n], w64[n:2 * n], w64[2 * n:3 * n], w64[3 * n:]
+    sp = _native.stream(dev)
+    _native.call("be_cp_rings_count", _native.ptr(Mc), B, H, W, K, _native.ptr(bbox), _native.ptr(nvert), _native.ptr(voff),
+                 _native.ptr(roff), _native.ptr(totals), sp)
+    V, = _host_ints(totals[:1])
+    if V == 0:
+        return _rings_empty(B, dev)
+    cap = V // 4  # a ring has at least 4 vertices
+    verts = torch.empty(V, 2, dtype=torch.int32, device=dev)
+    o64 = torch.empty(4 * cap + 1 + B + 1, dtype=torch.int64, device=dev)
+    first, tab_a2, off, area2, per_image = o64.split([cap, cap, cap + 1, cap, B + 1])
+    o32 = torch.empty(2 * cap, dtype=torch.int32, device=dev)
+    nz = (B * H * W + 3) // 4 * 4  # "top edge traced" marks of the boxes beyond 64 x 64, then the error word
+    zeroed = torch.zeros(nz + 4, dtype=torch.uint8, device=dev)
+    err = zeroed[nz:].view(torch.int32)
+    _native.call("be_cp_rings_trace", _native.ptr(Mc), B, H, W, K, _native.ptr(bbox), _native.ptr(nvert), _native.ptr(voff),
+                 _native.ptr(roff), _native.ptr(zeroed), _native.ptr(verts), _native.ptr(first), _native.ptr(tab_a2),
+                 _native.ptr(nrings), _native.ptr(rstart), _native.ptr(err), _native.ptr(totals), _native.ptr(off),
+                 _native.ptr(area2), _native.ptr(o32[:cap]), _native.ptr(o32[cap:]), _native.ptr(per_image), sp)
+    R, e = _host_ints(totals[2:])
+    if e:
+        raise RuntimeError(f"be_cp_rings_trace: a walk left its counted bounds (error word {e}): the labels changed "
+                           "while they were traced")
+    return _rings_result(verts, off[:R + 1], o32[:R], area2[:R], o32[cap:cap + R], per_image)
 
 
 # ------------------------------------------------------------------ evaluation: average precision

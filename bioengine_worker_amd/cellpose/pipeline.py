@@ -1038,6 +1038,28 @@ class CellposeRunner:
         raws = measure_launch(m, img, volume=volume)
         return measure_tables(raws, volume)
 
+    # ---------------------------------------------------------------- outlines
+    def outlines(self, masks, volume: bool = False, nlab: int | None = None):
+        """Cell outlines as polygon rings (:func:`reference.mask_rings`): closed rings of pixel-corner
+        coordinates whose polygon is exactly the mask.
+
+        ``masks``: [B, H, W] (or one [H, W] image), as :meth:`eval` returns them; with ``volume=True``
+        one [Z, H, W] volume, as :meth:`eval_stack` / :meth:`eval_3d` return it, outlined plane by
+        plane with the volume's labels.  Returns one rings dict of numpy arrays per image (``verts``
+        int32 [V, 2] (y, x), ``ring_offsets`` int64 [R + 1], ``ring_label`` int32 [R], ``ring_area2``
+        int64 [R]; :func:`reference.rings_to_geojson` turns one into GeoJSON), or the list of the Z
+        planes' dicts for a volume.  ``nlab``: an upper bound on the labels + 1; by default the
+        ``label_bound`` the mask stage left on ``masks``, else ``masks.max() + 1``.  Masks on the GPU
+        are traced by the HIP kernels (:func:`gpu.mask_rings_gpu`), everything else by the oracle."""
+        m = masks if torch.is_tensor(masks) else torch.as_tensor(np.asarray(masks))
+        if m.dim() == 2 and not volume:
+            m = m[None]
+        if m.dim() != 3:
+            raise ValueError(f"outlines expects [B, H, W] masks or one [Z, H, W] volume, got shape {tuple(m.shape)}")
+        if nlab is None:
+            nlab = getattr(masks, "label_bound", None)
+        return outline_rings(outline_launch(m, nlab=nlab, volume=volume))
+
     # ---------------------------------------------------------------- evaluation
     def score(self, masks_true, masks_pred, thresholds=(0.5, 0.75, 0.9), volume: bool = False) -> dict:
         """Average precision of predicted labels against ground truth (:func:`metrics.average_precision`).
@@ -1113,6 +1135,31 @@ def measure_tables(raws: dict, volume: bool = False):
         kb = int(present[-1]) + 1 if present.size else 0
         tables.append(ref.derive_measurements({k: (v[b] if k == "outlines" else v[b, :kb]) for k, v in host.items()}))
     return tables[0] if volume else tables
+
+
+def outline_launch(m: torch.Tensor, nlab: int | None = None, volume: bool = False) -> dict:
+    """Outline rings of masks ``m`` [B, H, W] (or one [Z, H, W] volume, traced per plane) as the
+    batch arrays of :func:`gpu.mask_rings_gpu`, on the masks' device: the HIP kernels on the GPU (on
+    the current stream, which is waited for twice: for the vertex and for the ring count), the numpy
+    oracle elsewhere."""
+    from .gpu import mask_rings_gpu
+
+    return mask_rings_gpu(m, nlab=nlab, volume=volume)
+
+
+def outline_rings(raws: dict) -> list:
+    """Host side of :meth:`CellposeRunner.outlines`: the batch arrays of :func:`outline_launch`
+    (tensors or arrays) -> one rings dict per image, in the form of :func:`reference.mask_rings`
+    (``verts``, ``ring_offsets`` starting at 0, ``ring_label``, ``ring_area2``)."""
+    host = {k: (v.cpu().numpy() if torch.is_tensor(v) else np.asarray(v)) for k, v in raws.items()}
+    off, per = host["ring_offsets"], host["image_rings"]
+    out = []
+    for b in range(per.shape[0] - 1):
+        r0, r1 = int(per[b]), int(per[b + 1])
+        v0, v1 = int(off[r0]), int(off[r1])
+        out.append({"verts": host["verts"][v0:v1].copy(), "ring_offsets": off[r0:r1 + 1] - v0,
+                    "ring_label": host["ring_label"][r0:r1].copy(), "ring_area2": host["ring_area2"][r0:r1].copy()})
+    return out
 
 
 def mask_stream(device) -> "torch.cuda.Stream":

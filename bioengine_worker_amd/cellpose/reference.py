@@ -863,3 +863,214 @@ def derive_measurements(raw: dict) -> dict:
     out["n_cells"] = int(present.sum())
     out["diameter_px"] = float(np.median(np.sqrt(area[present])) * 2.0 / np.sqrt(np.pi)) if present.any() else 0.0
     return out
+
+
+# ------------------------------------------------------------------ outlines: polygon rings
+
+#: direction codes of the crack-following tracer: 0 = +x (top edge), 1 = +y (right edge),
+#: 2 = -x (bottom edge), 3 = -y (left edge); (dy, dx) per code.  Turning right is ``d + 1``, left ``d - 1``.
+_RING_DIRS = ((0, 1), (1, 0), (0, -1), (-1, 0))
+#: tail vertex of a pixel's edge, relative to the pixel, per direction
+_RING_TAIL = ((0, 0), (0, 1), (1, 1), (1, 0))
+
+
+def _empty_rings() -> dict:
+    return {"verts": np.zeros((0, 2), np.int32), "ring_offsets": np.zeros(1, np.int64),
+            "ring_label": np.zeros(0, np.int32), "ring_area2": np.zeros(0, np.int64)}
+
+
+def mask_rings(masks) -> dict:
+    """Outlines of a label image as closed rings of pixel-corner coordinates: the specification of
+    ``csrc/kernels/cellpose_rings.hip``, which the GPU tests compare with exactly.  (cellpose's
+    ``utils.outlines_list``, OpenCV and scikit-image are not installed and not compared against: the
+    rules below are this project's own.)
+
+    ``masks``: [H, W] integer labels (0 = background; negative values are background too).  The
+    outline of a label is the exact boundary of its pixel set (crack following), not a chain of
+    pixel centres, so the polygon *is* the mask: :func:`rings_to_labels` inverts it.
+
+    Directed edges.  A pixel ``(y, x)`` of label ``l`` owns one unit edge per side whose 4-neighbour
+    lies outside the array or carries another label.  Edges run clockwise on screen (x right, y
+    down), the label on the right hand: top ``+x`` from ``(y, x)``, right ``+y`` from ``(y, x+1)``,
+    bottom ``-x`` from ``(y+1, x+1)``, left ``-y`` from ``(y+1, x)``.
+
+    Successor.  At the head of an edge of pixel ``P`` with direction ``d``, with ``A = P + d`` and
+    ``B = A + left(d)``: if ``A`` is not ``l`` turn right and stay on ``P``; else if ``B`` is ``l``
+    turn left onto ``B``; else go straight onto ``A``.  ``A`` is tested first, so labels are
+    4-connected: pixels that touch only diagonally are separate rings, and a ring may pass through
+    one corner twice (a saddle whose two pixels are joined elsewhere).
+
+    Rings.  Only turn vertices are kept (the tail of every edge whose predecessor has another
+    direction).  A ring starts at the tail of its raster-first top edge; the rings of an image are
+    ordered by label, then by the raster position of that edge.  ``area2 = sum(x_i * y_{i+1} -
+    x_{i+1} * y_i)`` in int64: positive for outer rings, negative for holes, and a label's rings sum
+    to twice its area.
+
+    Returns ``verts`` int32 [V, 2] as (y, x), ``ring_offsets`` int64 [R + 1], ``ring_label`` int32
+    [R] and ``ring_area2`` int64 [R]."""
+    m = np.asarray(masks)
+    if m.ndim != 2:
+        raise ValueError(f"mask_rings expects [H, W] labels, got shape {m.shape}")
+    H, W = m.shape
+    P = np.zeros((H + 2, W + 2), np.int64)
+    P[1:-1, 1:-1] = m
+    P[P < 0] = 0
+    top = (P[1:-1, 1:-1] > 0) & (P[1:-1, 1:-1] != P[:-2, 1:-1])
+    ys, xs = np.nonzero(top)
+    if ys.size == 0:
+        return _empty_rings()
+    seen = np.zeros((H, W), bool)
+    Pl = P.tolist()  # plain ints: the walk is a Python loop
+    rings = []  # (label, start raster index, vertices, area2)
+    for y0, x0 in zip(ys.tolist(), xs.tolist()):
+        if seen[y0, x0]:
+            continue
+        lab = Pl[y0 + 1][x0 + 1]
+        py, px, d = y0, x0, 0
+        verts = [(y0, x0)]
+        while True:
+            if d == 0:
+                seen[py, px] = True
+            dy, dx = _RING_DIRS[d]
+            ay, ax = py + dy, px + dx
+            nd = d
+            if Pl[ay + 1][ax + 1] != lab:
+                nd = (d + 1) & 3
+            else:
+                ly, lx = _RING_DIRS[(d + 3) & 3]
+                if Pl[ay + ly + 1][ax + lx + 1] == lab:
+                    py, px, nd = ay + ly, ax + lx, (d + 3) & 3
+                else:
+                    py, px = ay, ax
+            if (py, px, nd) == (y0, x0, 0):
+                break
+            if nd != d:
+                ty, tx = _RING_TAIL[nd]
+                verts.append((py + ty, px + tx))
+            d = nd
+        v = np.asarray(verts, np.int64)
+        nxt = np.roll(v, -1, 0)
+        rings.append((lab, y0 * W + x0, v, int((v[:, 1] * nxt[:, 0] - nxt[:, 1] * v[:, 0]).sum())))
+    rings.sort(key=lambda r: (r[0], r[1]))
+    return {"verts": np.concatenate([r[2] for r in rings]).astype(np.int32),
+            "ring_offsets": np.concatenate([[0], np.cumsum([len(r[2]) for r in rings])]).astype(np.int64),
+            "ring_label": np.asarray([r[0] for r in rings], np.int32),
+            "ring_area2": np.asarray([r[3] for r in rings], np.int64)}
+
+
+def ring_vertex_counts(masks) -> np.ndarray:
+    """Turn vertices per label ``1..K`` of :func:`mask_rings`, int64 [K], counted locally: at each of
+    the ``(H + 1)(W + 1)`` pixel corners a label with one or three members in the corner's 2 x 2
+    block has one vertex there, with two diagonal members two, otherwise none.  This is what sizes
+    every label's segment of ``verts`` on the GPU before anything is traced."""
+    m = np.asarray(masks)
+    H, W = m.shape
+    K = max(int(m.max()), 0) if m.size else 0
+    P = np.zeros((H + 2, W + 2), np.int64)
+    P[1:-1, 1:-1] = m
+    a, b, c, d = P[:-1, :-1], P[:-1, 1:], P[1:, :-1], P[1:, 1:]
+    out = np.zeros(K + 1, np.int64)
+    for q in (a, b, c, d):  # every member of the block votes for its own label
+        n = (q == a).astype(np.int64) + (q == b) + (q == c) + (q == d)
+        diag = (n == 2) & (((q == a) & (q == d)) | ((q == b) & (q == c)))
+        # a label with n members in the block is seen n times: in sixths of a vertex, each sighting
+        # adds 6 / n of the corner's count (1 vertex for n = 1 or 3, 2 for a diagonal pair)
+        np.add.at(out, q[(n == 1) & (q > 0)], 6)
+        np.add.at(out, q[(n == 3) & (q > 0)], 2)
+        np.add.at(out, q[diag & (q > 0)], 6)
+    return out[1:] // 6
+
+
+def _ring_list(rings: dict):
+    off = np.asarray(rings["ring_offsets"]).astype(np.int64)
+    v = np.asarray(rings["verts"]).astype(np.int64).reshape(-1, 2)
+    labs = np.asarray(rings["ring_label"]).astype(np.int64)
+    if off.shape[0] != labs.shape[0] + 1 or (off.size and (off[0] != 0 or off[-1] != v.shape[0])):
+        raise ValueError("rings: ring_offsets does not fit verts / ring_label")
+    return [(int(labs[r]), v[off[r]:off[r + 1]]) for r in range(labs.shape[0])]
+
+
+def rings_to_labels(rings: dict, shape) -> np.ndarray:
+    """The exact inverse of :func:`mask_rings`: int32 labels of ``shape`` (H, W) from a rings dict, by
+    a signed scanline over the vertical edges of each label's rings (an edge running ``-y`` opens the
+    label at its column, one running ``+y`` closes it).  Raises ``ValueError`` when the rings of two
+    labels cover one pixel, a winding other than 0 / 1 appears, or a vertex lies outside the shape."""
+    H, W = int(shape[0]), int(shape[1])
+    out = np.zeros((H, W), np.int32)
+    by_label: dict = {}
+    for lab, v in _ring_list(rings):
+        if lab <= 0:
+            raise ValueError(f"rings_to_labels: ring label {lab} is not positive")
+        if v.shape[0] and (v.min() < 0 or v[:, 0].max() > H or v[:, 1].max() > W):
+            raise ValueError(f"rings_to_labels: a vertex of label {lab} lies outside {H} x {W}")
+        by_label.setdefault(lab, []).append(v)
+    for lab in sorted(by_label):
+        vs = by_label[lab]
+        allv = np.concatenate(vs)
+        y0, x0, y1, x1 = allv[:, 0].min(), allv[:, 1].min(), allv[:, 0].max(), allv[:, 1].max()
+        D = np.zeros((y1 - y0, x1 - x0 + 1), np.int64)
+        for v in vs:
+            nxt = np.roll(v, -1, 0)
+            for (ya, xa), (yb, xb) in zip(v.tolist(), nxt.tolist()):
+                if xa != xb and ya != yb:
+                    raise ValueError(f"rings_to_labels: label {lab} has an edge that is not axis-parallel")
+                if ya < yb:
+                    D[ya - y0:yb - y0, xa - x0] -= 1
+                elif yb < ya:
+                    D[yb - y0:ya - y0, xa - x0] += 1
+        wind = np.cumsum(D, 1)[:, :-1]
+        if wind.size and (wind.min() < 0 or wind.max() > 1 or D.sum(1).any()):
+            raise ValueError(f"rings_to_labels: label {lab} has a winding other than 0 / 1")
+        sub = out[y0:y1, x0:x1]
+        inside = wind == 1
+        if (sub[inside] != 0).any():
+            raise ValueError(f"rings_to_labels: label {lab} covers a pixel of another label")
+        sub[inside] = lab
+    return out
+
+
+def _ring_contains2(v: np.ndarray, py2: int, px2: int) -> bool:
+    """Even-odd test of the point (py2 / 2, px2 / 2), both odd, against the closed ring ``v`` (y, x):
+    crossings of the ray towards +x with the ring's vertical edges, in doubled integer coordinates."""
+    nxt = np.roll(v, -1, 0)
+    vert = v[:, 1] == nxt[:, 1]
+    lo, hi = 2 * np.minimum(v[:, 0], nxt[:, 0]), 2 * np.maximum(v[:, 0], nxt[:, 0])
+    return bool((vert & (2 * v[:, 1] > px2) & (lo < py2) & (py2 < hi)).sum() & 1)
+
+
+def rings_to_geojson(rings: dict, z: int | None = None) -> dict:
+    """A rings dict of :func:`mask_rings` as a GeoJSON ``FeatureCollection`` (plain Python values):
+    one ``Feature`` per label with ``properties`` ``{label, area, n_rings}`` (plus ``z`` when given),
+    geometry ``Polygon`` when the label has one outer ring and ``MultiPolygon`` otherwise.
+    Coordinates are ``[x, y]`` pixel corners, every ring closed by repeating its first vertex.  A hole
+    belongs to the outer ring of its label that contains it, to the one of smallest ``area2`` when
+    several do; the test point is the centre of the hole pixel above the hole ring's first top edge
+    (even-odd crossings in doubled integers, no floats).  The rings' orientation is already RFC
+    7946's: exteriors counter-clockwise in the numeric (x, y) plane, holes clockwise.  (No GIS
+    library is installed or compared against; the tests check the structure and the containment.)"""
+    area2 = np.asarray(rings["ring_area2"]).astype(np.int64)
+    by_label: dict = {}
+    for r, (lab, v) in enumerate(_ring_list(rings)):
+        by_label.setdefault(lab, []).append((int(area2[r]), v))
+    feats = []
+    for lab in sorted(by_label):
+        rs = by_label[lab]
+        outers = [(a, v, []) for a, v in rs if a > 0]
+        for a, v in rs:
+            if a > 0:
+                continue
+            py2, px2 = 2 * int(v[0, 0]) - 1, 2 * int(v[0, 1]) + 1
+            inside = [o for o in outers if _ring_contains2(o[1], py2, px2)]
+            if not inside:
+                raise ValueError(f"rings_to_geojson: a hole of label {lab} lies in none of its outer rings")
+            min(inside, key=lambda o: o[0])[2].append(v)
+        polys = []
+        for _, v, holes in outers:
+            polys.append([[[int(x), int(y)] for y, x in np.concatenate([q, q[:1]]).tolist()] for q in [v] + holes])
+        props = {"label": int(lab), "area": int(sum(a for a, _ in rs) // 2), "n_rings": len(rs)}
+        if z is not None:
+            props["z"] = int(z)
+        geom = {"type": "Polygon", "coordinates": polys[0]} if len(polys) == 1 else \
+            {"type": "MultiPolygon", "coordinates": polys}
+        feats.append({"type": "Feature", "properties": props, "geometry": geom})
+    return {"type": "FeatureCollection", "features": feats}
