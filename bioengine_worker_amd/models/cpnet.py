@@ -17,11 +17,12 @@ Default channel plan: ``nbase = [2, 32, 64, 128, 256]``, 3 outputs (dY, dX, cell
 """
 from __future__ import annotations
 
+import os
+from dataclasses import dataclass
+
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
-
-import os
 
 from ..ops import conv as convops
 from ..ops import conv_pair as pairops
@@ -214,11 +215,9 @@ class _FConv:
     def __init__(self, seq: nn.Sequential, relu: bool, device, cin_pad=None, cout_pad_to=None):
         bn, conv = seq[0], seq[-1]
         self.pc = convops.PackedConv.from_weight(conv.weight, conv.bias, cin_pad=cin_pad, cout_pad_to=cout_pad_to).to(device)
-        # fragment-order weights of the 128-channel ping-pong kernel (of its pooled 64 -> 128 build, the
-        # level-2 entry conv with its 1x1 projection, and of its 128 -> 256 build, the level-3 entry conv):
-        # packed here, not in the first forward
-        if (convops.frag_eligible(self.pc) or convops.frag_eligible_pool(self.pc) or convops.frag_eligible_proj(self.pc)
-                or convops.frag_eligible_c256(self.pc)) and torch.device(device).type == "cuda":
+        # fragment-order weights of the 128-channel ping-pong kernel's builds (convops.PP128_BUILDS): packed
+        # here, not in the first forward
+        if convops.pp128_build(self.pc) is not None and torch.device(device).type == "cuda":
             self.pc.frag()
         s, t = _bn_fold(bn, device)
         self.scale = _pad_vec(s, self.pc.cin_pad, 0.0)
@@ -235,14 +234,13 @@ class _FConv:
 class _PPConv:
     """A 3x3 conv on the ping-pong implicit-GEMM kernel (ops/gemm_pp.py): weights [Cout][3][3][Cin]."""
 
-    def __init__(self, conv: nn.Conv2d, device):
+    def __init__(self, conv: nn.Conv2d, device, cfg: int | None = None):
         from ..ops import gemm_pp as ppops
 
         self.cout = conv.weight.shape[0]
         self.wp = ppops.pack_conv3(conv.weight).to(device)
         self.bias = None if conv.bias is None else conv.bias.detach().float().to(device).contiguous()
-        cfg = os.environ.get("BE_CPNET_PP_CFG")
-        self.cfg = None if cfg is None else int(cfg)
+        self.cfg = cfg
 
 
 def _igc(x, pk, **kw):
@@ -256,15 +254,40 @@ def _igc(x, pk, **kw):
     return igops.conv3_igemm(x, pk, **kw)
 
 
+@dataclass(frozen=True)
+class CPnetEngineOptions:
+    """The kernels a :class:`CPnetEngine` is built for (A/B switches, one ``BE_CPNET_*`` variable each)."""
+
+    pair: bool = True                            # PAIR: the fused two-conv kernels (ops/conv_pair.py) ...
+    pair_levels: tuple[int, ...] = (0, 1)        # PAIR_LEVELS: ... on these levels (0 = 32 ch at full res, 1 = 64 ch)
+    igemm: str = "1"                             # IGEMM: "1" ops/conv_igemm.py, "pp" ops/gemm_pp.py, else neither ...
+    # IGEMM_LEVELS: ... on these down levels and the up blocks at their resolution (up block i writes level
+    # i's, the last one the deepest level's); None (the variable set but empty): no restriction
+    igemm_levels: tuple[int, ...] | None = (3,)
+    head: bool = True                            # HEAD: the output layer in the last half-block's epilogue
+    pp_cfg: int | None = None                    # PP_CFG: ops/gemm_pp.py's kernel configuration (None: its own choice)
+
+    @classmethod
+    def from_env(cls) -> "CPnetEngineOptions":
+        env = os.environ.get
+        levels = lambda s: tuple(sorted({int(v) for v in s.split(",") if v.strip()}))
+        ig_levels, cfg = env("BE_CPNET_IGEMM_LEVELS", "3"), env("BE_CPNET_PP_CFG")
+        return cls(pair=env("BE_CPNET_PAIR", "1") != "0", pair_levels=levels(env("BE_CPNET_PAIR_LEVELS", "0,1")),
+                   igemm=env("BE_CPNET_IGEMM", "1"), igemm_levels=levels(ig_levels) if ig_levels else None,
+                   head=env("BE_CPNET_HEAD", "1") != "0", pp_cfg=None if cfg is None else int(cfg))
+
+
 class CPnetEngine:
     """Inference engine for an eval-mode (BatchNorm) :class:`CPnet`.
 
     ``forward(x)``: ``x`` NHWC bf16 [B, H, W, cin_pad] (H, W multiples of 8) ->
     (flows+cellprob NCHW fp32 [B, nout, H, W], style fp32 [B, nbase[-1]]).
+    ``options``: None reads the ``BE_CPNET_*`` variables now (:meth:`CPnetEngineOptions.from_env`).
     """
 
-    def __init__(self, net: CPnet, device):
+    def __init__(self, net: CPnet, device, options: CPnetEngineOptions | None = None):
         net = net.eval()
+        self.options = opt = CPnetEngineOptions.from_env() if options is None else options
         self.device = torch.device(device)
         self.nout = net.nout
         self.nchan = net.nchan
@@ -307,17 +330,17 @@ class CPnetEngine:
         self.style_b = torch.cat(bs, 0).contiguous()
         self.style_s = torch.cat(ss, 0).contiguous()
         self.style_t = torch.cat(ts, 0).contiguous()
-        self.pair = self._build_pairs(net) if os.environ.get("BE_CPNET_PAIR", "1") != "0" else {}
+        self.pair = self._build_pairs(net) if opt.pair else {}
         # deepest level on the implicit-GEMM kernels (BE_CPNET_IGEMM=1, BE_CPNET_IGEMM_LEVELS=3 by
         # default): whole-network A/B on MI355X 14.38 vs 14.62 ms per 288 tiles for the per-layer
         # path (profiles/r04/conv/engine_ab_L3.jsonl).  On both deep levels the producer-side
         # activated copies cost more HBM traffic than the DMA-fed main loop saves at 56^2 (14.68;
         # engine_ab_v2.jsonl); BE_CPNET_IGEMM=0 / pp select the per-layer / ping-pong kernels
-        self.ig_kind = os.environ.get("BE_CPNET_IGEMM", "1")
+        self.ig_kind = opt.igemm
         self.ig = self._build_igemm(net) if self.ig_kind in ("1", "pp") else {}
         # output layer fused into the last half-block's epilogue (ops/conv_pair.py HeadSpec)
         self.head = None
-        if ("up", 0, 1) in self.pair and self.out.relu and self.nout <= 16 and os.environ.get("BE_CPNET_HEAD", "1") != "0":
+        if ("up", 0, 1) in self.pair and self.out.relu and self.nout <= 16 and opt.head:
             self.head = pairops.HeadSpec.build(self.out.scale, self.out.shift, net.output[-1].weight.to(d),
                                                None if net.output[-1].bias is None else net.output[-1].bias.to(d))
 
@@ -365,10 +388,7 @@ class CPnetEngine:
                     prev = e["c0"] if k == 1 else e["c2"]
                     if prev.pc.bias is not None:
                         self.style_t[off: off + c] += self.style_s[off: off + c] * prev.pc.bias[:c].to(self.device)
-        # BE_CPNET_PAIR_LEVELS (default "0,1"): the levels (0 = 32 ch at full res, 1 = 64 ch) that
-        # run on the fused pair kernels; the others fall to the igemm / per-layer paths (A/B)
-        keep = {int(v) for v in os.environ.get("BE_CPNET_PAIR_LEVELS", "0,1").split(",") if v.strip()}
-        pairs = {k: v for k, v in pairs.items() if k[1] in keep}
+        pairs = {k: v for k, v in pairs.items() if k[1] in self.options.pair_levels}
         for key, sp in pairs.items():
             has_x2 = key[0] == "up" and key[2] == 0
             res = "none" if sp.pp is not None else ("up2" if has_x2 else "full")
@@ -395,7 +415,7 @@ class CPnetEngine:
             cout, cin, kh, _ = conv.weight.shape
             if self.ig_kind == "pp":
                 if kh == 3 and ppops.conv3_supported(cin, cout):
-                    ig[key] = _PPConv(conv, self.device)
+                    ig[key] = _PPConv(conv, self.device, self.options.pp_cfg)
             elif kh == 3 and cin % 16 == 0 and cout % 64 == 0:
                 ig[key] = igops.IgemmConv.from_weight(conv.weight, conv.bias).to(self.device)
 
@@ -412,17 +432,12 @@ class CPnetEngine:
                 add(("up", i, 0), blk.conv[0][-1])
             for k in (1, 2, 3):
                 add(("up", i, k), blk.conv[k].conv[-1])
-        # a level runs on the igemm path only when all of its 3x3 convs do; BE_CPNET_IGEMM_LEVELS
-        # (e.g. "3") restricts it to the listed down levels and the up blocks at their resolution
+        # a level runs on the igemm path only when all of its 3x3 convs do, and options.igemm_levels names it
         levels = {}
         for (kind, idx, k) in ig:
             levels.setdefault((kind, idx), set()).add(k)
-        full = {lv for lv, ks in levels.items() if ks >= {1, 2, 3}}
-        only = os.environ.get("BE_CPNET_IGEMM_LEVELS", "3")
-        if only:
-            keep = {int(v) for v in only.split(",") if v.strip()}
-            # up block i writes level i's resolution (the last one stays at the deepest level's)
-            full = {lv for lv in full if lv[1] in keep}
+        keep = self.options.igemm_levels
+        full = {lv for lv, ks in levels.items() if ks >= {1, 2, 3} and (keep is None or lv[1] in keep)}
         return {key: v for key, v in ig.items() if (key[0], key[1]) in full}
 
     def _ig_level(self, kind: str, idx: int, x: torch.Tensor, H: int, W: int) -> bool:
@@ -435,11 +450,45 @@ class CPnetEngine:
             return True  # no halo budget: any image geometry
         return igops.supported(x.shape[0], H, W, pk.cout, pk.bn)
 
-    def _down_ig(self, n: int, e: dict, src: torch.Tensor, next_act=None) -> torch.Tensor:
+    # ------------------------------------------------------------------ one method per route
+    def _down_route(self, n: int, src: torch.Tensor) -> str:
+        """The route level ``n`` takes on ``src``: "ig" (:meth:`_down_ig`), "pair" or "layer"."""
+        if n > 0 and ("down", n, 1) in self.ig and self._ig_level("down", n, src, src.shape[1] // 2, src.shape[2] // 2):
+            return "ig"
+        return "pair" if ("down", n, 0) in self.pair else "layer"
+
+    def _down_pair(self, n: int, e: dict, src: torch.Tensor) -> torch.Tensor:
+        """resdown as two fused half-blocks (ops/conv_pair.py)."""
+        P = self.pair
+        if n == 0 or P[("down", n, 0)].pp is not None:
+            # the stem computes its projection inside the fused kernel (K concatenation); level 1's spec carries
+            # it: inside the ping-pong kernel in large calls, else two launches (ops/conv_pair.py decides)
+            x1 = pairops.conv_pair(src, P[("down", n, 0)])
+        else:
+            x1 = pairops.conv_pair(src, P[("down", n, 0)], res=e["proj"](src, inmode="pool2"), res_mode="full")
+        return pairops.conv_pair(x1, P[("down", n, 1)], res=x1, res_mode="full")
+
+    def _down_layer(self, n: int, e: dict, src: torch.Tensor) -> torch.Tensor:
+        """resdown with one launch per conv."""
+        im = "pool2" if n > 0 else "none"
+        if n > 0 and convops.pp128_takes_pool_proj(e["c0"].pc, e["proj"].pc, src):
+            # level 2 in large calls: the entry conv and the projection of the same pooled pixels
+            # in one launch of the ping-pong kernel's pooled build (the native side decides)
+            c0, pj = e["c0"], e["proj"]
+            h, proj = convops.fused_conv2d_pool_proj(src, c0.pc, pj.pc, scale=c0.scale, shift=c0.shift, relu=c0.relu,
+                                                     proj_scale=pj.scale, proj_shift=pj.shift)
+        else:
+            proj = e["proj"](src, inmode=im)
+            h = e["c0"](src, inmode=im)
+        x1 = e["c1"](h, residual=proj)
+        h = e["c2"](x1)
+        return e["c3"](h, residual=x1)
+
+    def _down_ig(self, n: int, e: dict, src: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor | None]:
         """resdown on the igemm path: every conv's output is written already activated for its
         consumer (producer-side pre-activation), so the 3x3 convs stage their inputs by DMA.
-        ``next_act`` = (scale, shift) of the following up block's first conv, which reads this
-        block's output through the igemm path too (written as a second, activated copy)."""
+        Returns (out, activated copy or None): the deepest level, when the following up block's first
+        conv reads its output through the igemm path too, writes a second copy activated for that conv."""
         ig = self.ig
         c0, c1, c2, c3 = e["c0"], e["c1"], e["c2"], e["c3"]
         entry = convops.pp128_pooled_entry(c0.pc, src)  # the native rules, asked before anything is launched
@@ -461,10 +510,48 @@ class CPnetEngine:
                                       post_scale=c1.scale, post_shift=c1.shift, post_relu=True)
         x1, x1a = _igc(ha, ig[("down", n, 1)], residual=proj, ascale=c2.scale, ashift=c2.shift)
         _, h2a = _igc(x1a, ig[("down", n, 2)], want_out=False, ascale=c3.scale, ashift=c3.shift)
-        if next_act is None:
-            xd, _ = _igc(h2a, ig[("down", n, 3)], residual=x1)
-            return xd, None
-        return _igc(h2a, ig[("down", n, 3)], residual=x1, ascale=next_act[0], ashift=next_act[1])
+        if n == len(self.down) - 1 and ("up", len(self.up) - 1, 0) in ig:
+            nxt = self.up[-1]["c0"]
+            return _igc(h2a, ig[("down", n, 3)], residual=x1, ascale=nxt.scale, ashift=nxt.shift)
+        xd, _ = _igc(h2a, ig[("down", n, 3)], residual=x1)
+        return xd, None
+
+    def _up_route(self, i: int, xcur: torch.Tensor, top_act: torch.Tensor | None) -> str:
+        """As :meth:`_down_route` for up block ``i``; an igemm ``c0`` needs ``top_act`` (:meth:`_down_ig`)."""
+        same = i == len(self.up) - 1  # the last block stays at the deepest level's resolution
+        H, W = (xcur.shape[1], xcur.shape[2]) if same else (2 * xcur.shape[1], 2 * xcur.shape[2])
+        if ("up", i, 1) in self.ig and (("up", i, 0) not in self.ig or top_act is not None) and \
+                self._ig_level("up", i, xcur, H, W):
+            return "ig"
+        return "pair" if ("up", i, 0) in self.pair else "layer"
+
+    def _up_pair(self, i: int, e: dict, xcur: torch.Tensor, y: torch.Tensor, shifts: dict) -> torch.Tensor:
+        """resup as two fused half-blocks; at level 0 with the fused head, the network's output instead."""
+        P = self.pair
+        # 1x1 projection commutes with nearest upsampling: run it at half resolution and
+        # let the fused kernel read it through an up2 residual
+        proj_lr = e["proj"](xcur)
+        x1 = pairops.conv_pair(xcur, P[("up", i, 0)], tb=shifts[(i, 1)], x2=y, res=proj_lr, res_mode="up2")
+        if i == 0 and self.head is not None:
+            return pairops.conv_pair_head(x1, P[("up", 0, 1)], self.head, ta=shifts[(0, 2)], tb=shifts[(0, 3)], res=x1)
+        return pairops.conv_pair(x1, P[("up", i, 1)], ta=shifts[(i, 2)], tb=shifts[(i, 3)], res=x1, res_mode="full")
+
+    def _up_layer(self, i: int, e: dict, xcur: torch.Tensor, y: torch.Tensor, shifts: dict) -> torch.Tensor:
+        """resup with one launch per conv."""
+        im = "none" if i == len(self.up) - 1 else "up2"
+        # the skip add (conv1's input is c0(x) + y) runs in c0's residual epilogue, so conv1
+        # reads one tensor instead of two (the two-input variant was ~1.7x slower per layer)
+        h0 = e["c0"](xcur, inmode=im, residual=y)
+        # as on the pair levels, the projection runs at half resolution where conv1's kernel can
+        # read it through an up2 residual (the 128-channel ping-pong kernel at 56^2: a quarter of
+        # the projection's work and of the bytes written and read back); asked of the native side
+        # per call, so small batches keep the full-resolution projection on the per-layer kernel
+        if im == "up2" and xcur.is_cuda and convops.pp128_takes_res_up2(e["c1"].pc, h0):
+            x1 = e["c1"](h0, shift=shifts[(i, 1)], residual=e["proj"](xcur), residual_mode="up2")
+        else:
+            x1 = e["c1"](h0, shift=shifts[(i, 1)], residual=e["proj"](xcur, inmode=im))
+        h2 = e["c2"](x1, shift=shifts[(i, 2)])
+        return e["c3"](h2, shift=shifts[(i, 3)], residual=x1)
 
     def _up_ig(self, i: int, e: dict, xcur: torch.Tensor, y: torch.Tensor, shifts: dict, xcur_act=None):
         ig = self.ig
@@ -496,83 +583,33 @@ class CPnetEngine:
     @torch.no_grad()
     def forward(self, x: torch.Tensor):
         xd = []
-        h = x
-        P = self.pair
         nup = len(self.up)
         top_act = None  # the deepest level's output, activated for up[nup-1].c0 (igemm path)
         for n, e in enumerate(self.down):
-            im = "pool2" if n > 0 else "none"
             src = x if n == 0 else xd[-1]
-            if n > 0 and ("down", n, 1) in self.ig and self._ig_level("down", n, src, src.shape[1] // 2,
-                                                                       src.shape[2] // 2):
-                last = n == len(self.down) - 1 and ("up", nup - 1, 0) in self.ig
-                nxt = (self.up[nup - 1]["c0"].scale, self.up[nup - 1]["c0"].shift) if last else None
-                xdn, top_act = self._down_ig(n, e, src, nxt)
-                xd.append(xdn)
-                continue
-            if ("down", n, 0) in P:
-                if n == 0:  # stem: projection computed inside the fused kernel (K concatenation)
-                    x1 = pairops.conv_pair(src, P[("down", 0, 0)])
-                elif P[("down", n, 0)].pp is not None:
-                    # level 1: the spec carries the projection; large calls compute it inside the
-                    # ping-pong kernel, small ones as today's two launches (ops/conv_pair.py decides)
-                    x1 = pairops.conv_pair(src, P[("down", n, 0)])
-                else:
-                    x1 = pairops.conv_pair(src, P[("down", n, 0)], res=e["proj"](src, inmode=im), res_mode="full")
-                xd.append(pairops.conv_pair(x1, P[("down", n, 1)], res=x1, res_mode="full"))
-                continue
-            if n > 0 and convops.pp128_takes_pool_proj(e["c0"].pc, e["proj"].pc, src):
-                # level 2 in large calls: the entry conv and the projection of the same pooled pixels
-                # in one launch of the ping-pong kernel's pooled build (the native side decides)
-                c0, pj = e["c0"], e["proj"]
-                h, proj = convops.fused_conv2d_pool_proj(src, c0.pc, pj.pc, scale=c0.scale, shift=c0.shift, relu=c0.relu,
-                                                         proj_scale=pj.scale, proj_shift=pj.shift)
+            route = self._down_route(n, src)
+            if route == "ig":
+                out, top_act = self._down_ig(n, e, src)
             else:
-                proj = e["proj"](src, inmode=im)
-                h = e["c0"](src, inmode=im)
-            x1 = e["c1"](h, residual=proj)
-            h = e["c2"](x1)
-            xd.append(e["c3"](h, residual=x1))
+                out = self._down_pair(n, e, src) if route == "pair" else self._down_layer(n, e, src)
+            xd.append(out)
         style, shifts_all = styleops.style_and_shifts(xd[-1], self.style_w, self.style_b, self.style_s, self.style_t,
                                                       self.style_on)
         shifts = self._split_shifts(shifts_all)
         xcur = xd[-1]
         for i in range(nup - 1, -1, -1):
             e = self.up[i]
-            im = "none" if i == nup - 1 else "up2"
             y = xd[i] if i < nup - 1 else xd[-1]
-            H2, W2 = (xcur.shape[1], xcur.shape[2]) if i == nup - 1 else (2 * xcur.shape[1], 2 * xcur.shape[2])
-            if ("up", i, 1) in self.ig and (("up", i, 0) not in self.ig or top_act is not None) and \
-                    self._ig_level("up", i, xcur, H2, W2):
+            route = self._up_route(i, xcur, top_act)
+            if route == "ig":
                 xcur = self._up_ig(i, e, xcur, y, shifts, top_act if i == nup - 1 else None)
-                continue
-            if ("up", i, 0) in P:
-                # 1x1 projection commutes with nearest upsampling: run it at half resolution and
-                # let the fused kernel read it through an up2 residual
-                proj_lr = e["proj"](xcur)
-                x1 = pairops.conv_pair(xcur, P[("up", i, 0)], tb=shifts[(i, 1)], x2=y, res=proj_lr, res_mode="up2")
-                if i == 0 and self.head is not None:
-                    y = pairops.conv_pair_head(x1, P[("up", 0, 1)], self.head, ta=shifts[(0, 2)], tb=shifts[(0, 3)],
-                                               res=x1)
-                    return y, style
-                xcur = pairops.conv_pair(x1, P[("up", i, 1)], ta=shifts[(i, 2)], tb=shifts[(i, 3)], res=x1,
-                                         res_mode="full")
-                continue
-            # the skip add (conv1's input is c0(x) + y) runs in c0's residual epilogue, so conv1
-            # reads one tensor instead of two (the two-input variant was ~1.7x slower per layer)
-            h0 = e["c0"](xcur, inmode=im, residual=y)
-            # as on the pair levels, the projection runs at half resolution where conv1's kernel can
-            # read it through an up2 residual (the 128-channel ping-pong kernel at 56^2: a quarter of
-            # the projection's work and of the bytes written and read back); asked of the native side
-            # per call, so small batches keep the full-resolution projection on the per-layer kernel
-            if im == "up2" and xcur.is_cuda and convops.pp128_takes_res_up2(e["c1"].pc, h0):
-                x1 = e["c1"](h0, shift=shifts[(i, 1)], residual=e["proj"](xcur), residual_mode="up2")
+            elif route == "pair":
+                xcur = self._up_pair(i, e, xcur, y, shifts)
+                if i == 0 and self.head is not None:  # _up_pair ran the output layer in its last epilogue
+                    return xcur, style
             else:
-                x1 = e["c1"](h0, shift=shifts[(i, 1)], residual=e["proj"](xcur, inmode=im))
-            h2 = e["c2"](x1, shift=shifts[(i, 2)])
-            xcur = e["c3"](h2, shift=shifts[(i, 3)], residual=x1)
-        y = self.out(xcur, out_nchw_f32=True, cout_valid=self.nout)
-        return y, style
+                xcur = self._up_layer(i, e, xcur, y, shifts)
+        return self.out(xcur, out_nchw_f32=True, cout_valid=self.nout), style
 
     __call__ = forward
 

@@ -53,7 +53,7 @@ class PackedConv:
     kp: int
     wp: torch.Tensor | None = None
     #: ``wp`` once more in MFMA-fragment order (:func:`pack_frag`), built by :meth:`frag` for the
-    #: layers :func:`frag_eligible` names, and the (address, version) of the ``wp`` it was packed from
+    #: layers :func:`pp128_build` names, and the (address, version) of the ``wp`` it was packed from
     wf: torch.Tensor | None = None
     wf_key: tuple | None = None
 
@@ -137,10 +137,8 @@ class PackedConv:
         if ``wp`` was replaced or written since).  An engine calls this when it is built; a conv whose
         fragments were never built, or went stale, runs on the per-layer kernel (:meth:`frag_built`)."""
         if self.frag_built() is None:
-            if frag_eligible_c256(self):
-                self.wf = pack_frag_c256(self.wp)
-            else:
-                self.wf = pack_frag(self.wp) if self.ks == 3 else pack_frag_1x1(self.wp)
+            pack = pack_frag_c256 if pp128_build(self) == "c256" else pack_frag if self.ks == 3 else pack_frag_1x1
+            self.wf = pack(self.wp)
             self.wf_key = self._wp_key()
         return self.wf
 
@@ -152,28 +150,57 @@ class PackedConv:
         return None
 
 
+#: (ks, cin_pad, cout) -> the build of the 128-channel ping-pong kernel (``csrc/kernels/conv_pp128.hip``)
+#: that reads the layer's fragment-order weights: the plain convs, CPnet's level-2 entry conv (read through
+#: a 2x2 max-pool) and the projection computed beside it, CPnet's level-3 entry conv (on the pooled tensor)
+PP128_BUILDS = {(3, 128, 128): "c128", (3, 64, 128): "pool", (1, 64, 128): "proj", (3, 128, 256): "c256"}
+
+
+def pp128_build(pc: PackedConv) -> str | None:
+    """The name of ``pc``'s ping-pong build (:data:`PP128_BUILDS`), or None: whole output channel tiles
+    (``cout_pad == cout``) and, for the 3x3 builds, 32-channel K chunks."""
+    if pc.cout_pad != pc.cout or (pc.ks == 3 and pc.ck != 32):
+        return None
+    return PP128_BUILDS.get((pc.ks, pc.cin_pad, pc.cout))
+
+
 def frag_eligible(pc: PackedConv) -> bool:
-    """The layers with a ping-pong build that reads fragment-order weights
-    (``csrc/kernels/conv_pp128.hip``): 3x3, 128 -> 128 channels."""
-    return pc.ks == 3 and pc.ck == 32 and pc.cin_pad == 128 and pc.cout == 128 and pc.cout_pad == 128
+    """The 3x3, 128 -> 128 layers; their fragments are :func:`pack_frag`'s."""
+    return pp128_build(pc) == "c128"
 
 
 def frag_eligible_pool(pc: PackedConv) -> bool:
-    """The layer with a pooled-input build of that kernel: 3x3, 64 -> 128 channels, read through a
-    2x2 max-pool (CPnet's level-2 entry conv).  Its fragments are ``[2 chunks, 9 taps, 8 channel tiles]``."""
-    return pc.ks == 3 and pc.ck == 32 and pc.cin_pad == 64 and pc.cout == 128 and pc.cout_pad == 128
+    """The pooled build's 3x3, 64 -> 128 layer; its fragments are ``[2 chunks, 9 taps, 8 channel tiles]``."""
+    return pp128_build(pc) == "pool"
 
 
 def frag_eligible_proj(pc: PackedConv) -> bool:
-    """The 1x1 projection that the pooled build can compute beside its 3x3 conv: 64 -> 128 channels
-    (CPnet's level-2 residual projection).  Its fragments are :func:`pack_frag_1x1`'s."""
-    return pc.ks == 1 and pc.cin_pad == 64 and pc.cout == 128 and pc.cout_pad == 128
+    """The 1x1, 64 -> 128 projection of the pooled build; its fragments are :func:`pack_frag_1x1`'s."""
+    return pp128_build(pc) == "proj"
 
 
 def frag_eligible_c256(pc: PackedConv) -> bool:
-    """The layer with a 256-channel build of that kernel: 3x3, 128 -> 256 channels (CPnet's level-3
-    entry conv, on the pooled tensor).  Its fragments are :func:`pack_frag_c256`'s."""
-    return pc.ks == 3 and pc.ck == 32 and pc.cin_pad == 128 and pc.cout == 256 and pc.cout_pad == 256
+    """The 256-channel build's 3x3, 128 -> 256 layer; its fragments are :func:`pack_frag_c256`'s."""
+    return pp128_build(pc) == "c256"
+
+
+def _pp128_takes(rule: str, x: torch.Tensor, *convs: tuple[PackedConv, str], pooled: bool = False,
+                 frags: bool = True) -> bool:
+    """What every ``pp128_takes_*`` predicate asks: ``x`` [N, H, W, C] is on the GPU, each ``(conv, build)``
+    is that build's layer with (``frags``) its fragment-order weights built, and the native side's
+    ``be_conv_pp128_takes_<rule>`` takes N images of H x W -- ``pooled``: of H/2 x W/2, from an even
+    source.  The native side is asked last and once."""
+    if not x.is_cuda:
+        return False
+    for pc, build in convs:
+        if pp128_build(pc) != build or (frags and pc.frag_built() is None):
+            return False
+    N, H, W, _ = x.shape
+    if pooled:
+        if H % 2 or W % 2:
+            return False
+        H, W = H // 2, W // 2
+    return bool(getattr(_native.hip(), "be_conv_pp128_takes_" + rule)(N, H, W))
 
 
 def pp128_takes_prepool(pc: PackedConv, x: torch.Tensor) -> bool:
@@ -181,22 +208,14 @@ def pp128_takes_prepool(pc: PackedConv, x: torch.Tensor) -> bool:
     source ``x`` [N, Hs, Ws, 128] through a 2x2 max-pool should pool once (:func:`pool2_nhwc`) and run both
     on the pooled tensor: the native side's answer (``be_conv_pp128_takes_prepool``: the 256-channel
     build's size rule and ``BE_CPNET_L3_PREPOOL``) for an even source.  Asked before anything is launched."""
-    if not x.is_cuda or not frag_eligible_c256(pc):
-        return False
-    N, Hs, Ws, _ = x.shape
-    if Hs % 2 or Ws % 2:
-        return False
-    return bool(_native.hip().be_conv_pp128_takes_prepool(N, Hs // 2, Ws // 2))
+    return _pp128_takes("prepool", x, (pc, "c256"), pooled=True, frags=False)
 
 
 def pp128_takes_c256(pc: PackedConv, x: torch.Tensor) -> bool:
     """Whether :func:`fused_conv2d_c256` may be called for the conv ``pc`` on ``x`` [N, H, W, 128]: it has
     its fragment-order weights and the native side (``be_conv_pp128_takes_c256``: the size rule over
     (tile, half) items, ``BE_CPNET_L3_PREPOOL`` and ``BE_CONV_PP128_C256``) takes a call of ``x``'s geometry."""
-    if not x.is_cuda or not frag_eligible_c256(pc) or pc.frag_built() is None:
-        return False
-    N, H, W, _ = x.shape
-    return bool(_native.hip().be_conv_pp128_takes_c256(N, H, W))
+    return _pp128_takes("c256", x, (pc, "c256"))
 
 
 def pp128_pooled_entry(pc: PackedConv, x: torch.Tensor) -> int:
@@ -206,8 +225,7 @@ def pp128_pooled_entry(pc: PackedConv, x: torch.Tensor) -> int:
     3x3 conv ``pc`` on the ping-pong kernel's 256-channel build (:func:`fused_conv2d_c256`)."""
     if not pp128_takes_prepool(pc, x):
         return 0
-    N, Hs, Ws, _ = x.shape
-    return 2 if pc.frag_built() is not None and _native.hip().be_conv_pp128_takes_c256(N, Hs // 2, Ws // 2) else 1
+    return 2 if _pp128_takes("c256", x, (pc, "c256"), pooled=True) else 1
 
 
 def pp128_takes_pool(pc: PackedConv, x: torch.Tensor) -> bool:
@@ -215,10 +233,7 @@ def pp128_takes_pool(pc: PackedConv, x: torch.Tensor) -> bool:
     ping-pong kernel's pooled build: the conv has its fragment-order weights and the native side
     (``be_conv_pp128_takes_pool``: even source size, the kernel's size rule, ``BE_CONV_PP128_POOL``)
     takes a call of ``x``'s geometry."""
-    if not x.is_cuda or not frag_eligible_pool(pc) or pc.frag_built() is None:
-        return False
-    N, Hs, Ws, _ = x.shape
-    return bool(_native.hip().be_conv_pp128_takes_pool(N, Hs, Ws))
+    return _pp128_takes("pool", x, (pc, "pool"))
 
 
 def pp128_takes_pool_proj(pc: PackedConv, pp: PackedConv, x: torch.Tensor) -> bool:
@@ -226,12 +241,14 @@ def pp128_takes_pool_proj(pc: PackedConv, pp: PackedConv, x: torch.Tensor) -> bo
     projection ``pp`` on the source ``x``: both have their fragment-order weights and the native side
     (``be_conv_pp128_takes_pool_proj``: the pooled build's rule and ``BE_CONV_PP128_POOL_PROJ``) takes a
     call of ``x``'s geometry.  Asked before anything is launched."""
-    if not x.is_cuda or not frag_eligible_pool(pc) or not frag_eligible_proj(pp):
-        return False
-    if pc.frag_built() is None or pp.frag_built() is None:
-        return False
-    N, Hs, Ws, _ = x.shape
-    return bool(_native.hip().be_conv_pp128_takes_pool_proj(N, Hs, Ws))
+    return _pp128_takes("pool_proj", x, (pc, "pool"), (pp, "proj"))
+
+
+def pp128_takes_res_up2(pc: PackedConv, x: torch.Tensor) -> bool:
+    """Whether ``fused_conv2d(x, pc, residual=r, residual_mode="up2")`` may be called: the conv has its
+    fragment-order weights and the native side (``be_conv_pp128_takes_res_up2``, the ping-pong
+    kernel's own size rule and switches) takes a call of ``x``'s geometry.  Always true on the CPU."""
+    return not x.is_cuda or _pp128_takes("res_up2", x, (pc, "c128"))
 
 
 def pack_frag_1x1(wp: torch.Tensor) -> torch.Tensor:
@@ -366,16 +383,14 @@ def _affine_stride(t: torch.Tensor | None, N: int, C: int) -> int:
     return 0
 
 
-def pp128_takes_res_up2(pc: PackedConv, x: torch.Tensor) -> bool:
-    """Whether ``fused_conv2d(x, pc, residual=r, residual_mode="up2")`` may be called: the conv has its
-    fragment-order weights and the native side (``be_conv_pp128_takes_res_up2``, the ping-pong
-    kernel's own size rule and switches) takes a call of ``x``'s geometry.  Always true on the CPU."""
-    if not x.is_cuda:
-        return True
-    if not frag_eligible(pc) or pc.frag_built() is None:
-        return False
-    N, H, W, _ = x.shape
-    return bool(_native.hip().be_conv_pp128_takes_res_up2(N, H, W))
+def out_hw(x: torch.Tensor, inmode: str) -> tuple[int, int]:
+    """Output size of a conv that reads NHWC ``x`` through ``inmode``."""
+    _, Hs, Ws, _ = x.shape
+    if inmode == "up2":
+        return 2 * Hs, 2 * Ws
+    if inmode == "pool2":
+        return Hs // 2, Ws // 2
+    return Hs, Ws
 
 
 def fused_conv2d(x: torch.Tensor, pc: PackedConv, *, x2=None, scale=None, shift=None, relu=False, residual=None,
@@ -394,12 +409,7 @@ def fused_conv2d(x: torch.Tensor, pc: PackedConv, *, x2=None, scale=None, shift=
     pre-activation to the stored value (``y = bf16(y) * post_scale + post_shift``, then ``post_relu``):
     the producer-side activation that feeds :func:`~.conv_igemm.conv3_igemm`."""
     N, Hs, Ws, Cin = x.shape
-    if inmode == "up2":
-        H, W = Hs * 2, Ws * 2
-    elif inmode == "pool2":
-        H, W = Hs // 2, Ws // 2
-    else:
-        H, W = Hs, Ws
+    H, W = out_hw(x, inmode)
     assert residual_mode in ("full", "up2")
     up2 = residual is not None and residual_mode == "up2"
     if up2:
@@ -454,7 +464,8 @@ def fused_conv2d(x: torch.Tensor, pc: PackedConv, *, x2=None, scale=None, shift=
         assert post_scale.dtype == torch.float32 and post_scale.is_contiguous() and post_scale.numel() == pc.cout
     # the layers with a ping-pong build also pass their fragment-order weights; the entry point picks
     # the kernel (csrc/kernels/conv_pp128.hip, be_conv2d_nhwc_frag)
-    wf = pc.frag_built() if frag_eligible(pc) or (inmode == "pool2" and frag_eligible_pool(pc)) else None
+    build = pp128_build(pc)
+    wf = pc.frag_built() if build == "c128" or (build == "pool" and inmode == "pool2") else None
     args = (
         _native.ptr(x), _native.ptr(x2), _native.ptr(scale), _native.ptr(shift), pshift_ns, pscale_ns,
         int(bool(relu)) | (2 if post_relu else 0),

@@ -22,7 +22,7 @@ import torch
 import torch.nn.functional as F
 
 from . import _native
-from .conv import INMODES, PackedConv, _act_ref, _affine_stride, fused_conv2d, fused_conv2d_ref
+from .conv import INMODES, PackedConv, _act_ref, _affine_stride, fused_conv2d, fused_conv2d_ref, out_hw
 
 #: (Cin, CM, inmode, x2, proj, res) combinations the kernel is instantiated for (CPnet levels 0/1)
 SUPPORTED = {
@@ -165,15 +165,6 @@ def fold_bias(shift: torch.Tensor, scale: torch.Tensor, bias: torch.Tensor | Non
     return out
 
 
-def _out_hw(x: torch.Tensor, inmode: str) -> tuple[int, int]:
-    Hs, Ws = x.shape[1], x.shape[2]
-    if inmode == "up2":
-        return 2 * Hs, 2 * Ws
-    if inmode == "pool2":
-        return Hs // 2, Ws // 2
-    return Hs, Ws
-
-
 def conv_pair_ref(x, spec: PairSpec, *, ta=None, tb=None, x2=None, res=None, res_mode="none"):
     """fp32 PyTorch oracle with the kernel's two bf16 rounding points (activated input, h)."""
     ta = spec.ta if ta is None else ta
@@ -228,7 +219,7 @@ def conv_pair(x: torch.Tensor, spec: PairSpec, *, ta=None, tb=None, x2=None, res
             return out
         return y
     N, Hs, Ws, Cin = x.shape
-    H, W = _out_hw(x, spec.inmode)
+    H, W = out_hw(x, spec.inmode)
     CM = spec.cm
     assert x.dtype == torch.bfloat16 and x.is_contiguous(), "conv_pair expects contiguous NHWC bf16"
     assert Cin == spec.cin, f"input channels {Cin} != packed {spec.cin}"
@@ -269,13 +260,13 @@ def proj_fused(x: torch.Tensor, spec: PairSpec) -> bool:
     ping-pong kernel.  The native side decides (``be_conv_pair_proj_takes``: the ping-pong kernel's own
     size rule, ``BE_PAIR_PP64``, the forced grid and the fusion's switch ``BE_PAIR_PP64_PROJ``)
     before anything is launched."""
-    H, W = _out_hw(x, spec.inmode)
+    H, W = out_hw(x, spec.inmode)
     return x.is_cuda and bool(_native.hip().be_conv_pair_proj_takes(x.shape[0], H, W))
 
 
 def _conv_pair_proj(x, spec: PairSpec, ta, tb, out):
     N, Hs, Ws, Cin = x.shape
-    H, W = _out_hw(x, spec.inmode)
+    H, W = out_hw(x, spec.inmode)
     if not proj_fused(x, spec):
         # small calls (batch-1 latency, default-grid tests): the per-layer projection, then the pair
         proj = fused_conv2d(x, spec.pp, scale=spec.sp, shift=spec.tp, inmode=spec.inmode)

@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <cstdio>
+#include <cstdlib>
 
 typedef uint16_t bf16_t;
 typedef __attribute__((ext_vector_type(8))) short bf16x8;   // MFMA A/B fragment (8 bf16)
@@ -64,6 +65,13 @@ __device__ __forceinline__ int xcd_remap(int orig, int nwg) {
 }
 
 #define BE_CHECK_LAUNCH() ((int)hipGetLastError())
+
+// An integer switch from the environment: atoi of `name`, or `dflt` when it is unset.  The kernels'
+// A/B switches initialise file-scope variables with it, so it runs when the library is loaded.
+inline int be_env_int(const char* name, int dflt) {
+  const char* e = getenv(name);
+  return e ? atoi(e) : dflt;
+}
 
 // ---- per-device host state ---------------------------------------------------------------------
 // A process may drive several GPUs (the 3-D EM slab path, multi-GPU replicas in one process): the

@@ -89,16 +89,9 @@ int g_pair_stamps_cap = 0;                    // workgroups the stamp buffer hol
 // per tile on the three CM = 64 pairs, +0.4 % headline; ROLL on top: stage A -8..-23 %, tiles
 // -2.6..-6.2 %, +0.3 % headline; EARLY on top: halo commit -2..-9 %, tiles -1.1..-2.4 %, +0.4 %
 // headline; two alternating runs each (profiles/r04/conv/pair_{late_epi,roll,early_aff}_ab.txt).
-static int g_pair_var = [] {
-  const char* l = getenv("BE_PAIR_LATE_EPI");
-  const char* r = getenv("BE_PAIR_ROLL");
-  const char* e = getenv("BE_PAIR_EARLY_AFF");
-  const char* p = getenv("BE_PAIR_EPIA");
-  const char* q = getenv("BE_PAIR_SEPS");
-  const char* te = getenv("BE_PAIR_TOPEPI");
-  return ((l ? atoi(l) : 1) ? 1 : 0) | ((r ? atoi(r) : 1) ? 2 : 0) | ((e ? atoi(e) : 1) ? 4 : 0) |
-         ((p && atoi(p)) ? 8 : 0) | ((q && atoi(q)) ? 16 : 0) | ((te && atoi(te)) ? 32 : 0);
-}();
+static int g_pair_var = (be_env_int("BE_PAIR_LATE_EPI", 1) ? 1 : 0) | (be_env_int("BE_PAIR_ROLL", 1) ? 2 : 0) |
+                        (be_env_int("BE_PAIR_EARLY_AFF", 1) ? 4 : 0) | (be_env_int("BE_PAIR_EPIA", 0) ? 8 : 0) |
+                        (be_env_int("BE_PAIR_SEPS", 0) ? 16 : 0) | (be_env_int("BE_PAIR_TOPEPI", 0) ? 32 : 0);
 
 template <int CK, int CM, int INMODE, bool X2, bool PROJ, int RES, int NCA, bool HEAD, bool STAMP, int VAR>
 int launch_pair_l(PairArgs a, int g, hipStream_t s) {
@@ -989,22 +982,13 @@ int launch_pair_pp64(PairArgs a, int grid_cap, hipStream_t s) {
 }  // namespace
 
 // tuning override (0 = one workgroup per CU); BE_PAIR_GRID sets it for A/B runs
-static int g_pair_grid = [] {
-  const char* e = getenv("BE_PAIR_GRID");
-  return e ? atoi(e) : 0;
-}();
+static int g_pair_grid = be_env_int("BE_PAIR_GRID", 0);
 
 // BE_PAIR_PP (default 1): the level-0 32 -> 32 half-blocks (+ the head) on the ping-pong kernel
-static int g_pair_pp = [] {
-  const char* e = getenv("BE_PAIR_PP");
-  return e ? atoi(e) : 1;
-}();
+static int g_pair_pp = be_env_int("BE_PAIR_PP", 1);
 
 // BE_PAIR_PP_STEM (default 1): the stem (8 -> 32 + projection) on the ping-pong kernel as well
-static int g_pair_pp_stem = [] {
-  const char* e = getenv("BE_PAIR_PP_STEM");
-  return e ? atoi(e) : 1;
-}();
+static int g_pair_pp_stem = be_env_int("BE_PAIR_PP_STEM", 1);
 
 // The ping-pong kernel pays off when each workgroup has tiles for both groups: with fewer than two
 // tiles per workgroup (batch-1 latency calls) the second group would only recompute a dummy tile,
@@ -1019,10 +1003,7 @@ static bool pp_ok(const PairArgs& a, int grid_cap) {
 // BE_PAIR_PP64 (default 1, A/B): the level-1 (CM = 64) half-blocks on the CM = 64 ping-pong kernel
 // (conv_pair_pp64.inc).  As pp_ok: only when every workgroup has a tile for each of its two groups
 // (16 x 16 tiles here) and the caller passed the fragment-order weights.
-static int g_pair_pp64 = [] {
-  const char* e = getenv("BE_PAIR_PP64");
-  return e ? atoi(e) : 1;
-}();
+static int g_pair_pp64 = be_env_int("BE_PAIR_PP64", 1);
 
 // the size rule by itself: N images of H x W outputs
 static bool pp64_size_ok(int N, int H, int W, int grid_cap) {
@@ -1037,10 +1018,7 @@ static bool pp64_ok(const PairArgs& a, int grid_cap) { return a.waf && a.wbf && 
 // BE_PAIR_PP64_PROJ (default 1, A/B; be_conv_pair_set_proj_fusion at run time): the level-1 pool2
 // half-block computes the block's 1x1 projection inside the ping-pong kernel (be_conv_pair_proj)
 // instead of reading it as a residual that a launch of its own wrote
-static int g_pair_pp64_proj = [] {
-  const char* e = getenv("BE_PAIR_PP64_PROJ");
-  return e ? atoi(e) : 1;
-}();
+static int g_pair_pp64_proj = be_env_int("BE_PAIR_PP64_PROJ", 1);
 
 extern "C" {
 

@@ -53,8 +53,6 @@
 // conv2d_nhwc_kernel<1, 64, 64, 2, ...> bit for bit) of the same pooled pixels as a second output: the
 // commits write the projection's input of the tile's centre pixels to a second LDS image per group, and
 // after the epilogue the freed accumulators take two 32-deep K-steps per fragment from zero.
-#include <cstdlib>
-
 #include "common.h"
 
 namespace {
@@ -84,27 +82,27 @@ static_assert(LDS_PROJ <= 128 * 1024, "LDS budget of the ping-pong kernels");
 static_assert(BD < BR, "ring");
 
 struct Args {
-  const bf16_t* x;     // [N, H, W, 128]; POOL: [N, 2 H, 2 W, 64]
-  const float* sa;     // scale [128] (sa_ns 0) or [N, sa_ns], or null (1)
-  const float* ta;     // shift likewise, or null (0)
-  const bf16_t* wf;    // fragment-order weights
-  const float* bias;   // [128] or null
-  const bf16_t* res;   // [N, H, W, 128] (may be `out`), [N, H/2, W/2, 128] (res_up2), or null
-  bf16_t* out;         // [N, H, W, 128]
-  int N, H, W;
-  int sa_ns, ta_ns;
-  int relu;
-  int res_up2;         // the residual is at half resolution, read through nearest 2x up-sampling (even H, W)
-  int tiles_x, tiles_y;
+  const bf16_t* x = nullptr;     // [N, H, W, 128]; POOL: [N, 2 H, 2 W, 64]
+  const float* sa = nullptr;     // scale [128] (sa_ns 0) or [N, sa_ns], or null (1)
+  const float* ta = nullptr;     // shift likewise, or null (0)
+  const bf16_t* wf = nullptr;    // fragment-order weights
+  const float* bias = nullptr;   // [128] or null
+  const bf16_t* res = nullptr;   // [N, H, W, 128] (may be `out`), [N, H/2, W/2, 128] (res_up2), or null
+  bf16_t* out = nullptr;         // [N, H, W, 128]
+  int N = 0, H = 0, W = 0;
+  int sa_ns = 0, ta_ns = 0;
+  int relu = 0;
+  int res_up2 = 0;     // the residual is at half resolution, read through nearest 2x up-sampling (even H, W)
+  int tiles_x = 0, tiles_y = 0;
   // PROJ build: out2 = conv1x1( pool(x) * sp + tp ) + bias_p, [N, H, W, 128]
-  const float* sp;     // scale [64]
-  const float* tp;     // shift [64]
-  const bf16_t* wpf;   // fragment-order projection weights [2 K-steps][8 ct][64 lanes][8]
-  const float* bias_p; // [128] or null
-  bf16_t* out2;
+  const float* sp = nullptr;     // scale [64]
+  const float* tp = nullptr;     // shift [64]
+  const bf16_t* wpf = nullptr;   // fragment-order projection weights [2 K-steps][8 ct][64 lanes][8]
+  const float* bias_p = nullptr; // [128] or null
+  bf16_t* out2 = nullptr;
   // diagnostics (STAMP instantiation only, tools/pp128_phase_profile.py): [grid][2 groups][16] cycle
   // counts of wave 0 of each group
-  unsigned long long* stamps;
+  unsigned long long* stamps = nullptr;
   // C256 build: `out` is [N, H, W, 256]; wf, bias and the post-activation vectors hold both halves
   const float* qs = nullptr;  // post-activation scale [256]
   const float* qt = nullptr;  // post-activation shift [256]
@@ -704,44 +702,26 @@ __global__ __launch_bounds__(NTP, 2) void conv_pp128_kernel(Args a) {
 }  // namespace pp128
 
 // BE_CONV_PP128 (default 1, A/B): 0 keeps every call on conv2d_nhwc_kernel
-int g_pp128 = [] {
-  const char* e = getenv("BE_CONV_PP128");
-  return e ? atoi(e) : 1;
-}();
+int g_pp128 = be_env_int("BE_CONV_PP128", 1);
 
 // BE_CONV_PP128_RES_UP2 (default 1, A/B): 0 makes be_conv_pp128_takes_res_up2 answer 0, so callers
 // keep a full-resolution residual
-int g_pp128_res_up2 = [] {
-  const char* e = getenv("BE_CONV_PP128_RES_UP2");
-  return e ? atoi(e) : 1;
-}();
+int g_pp128_res_up2 = be_env_int("BE_CONV_PP128_RES_UP2", 1);
 
 // BE_CONV_PP128_POOL (default 1, A/B): 0 keeps the pooled 64 -> 128 entry conv on conv2d_nhwc_kernel
-int g_pp128_pool = [] {
-  const char* e = getenv("BE_CONV_PP128_POOL");
-  return e ? atoi(e) : 1;
-}();
+int g_pp128_pool = be_env_int("BE_CONV_PP128_POOL", 1);
 
 // BE_CONV_PP128_POOL_PROJ (default 1, A/B): 0 makes be_conv_pp128_takes_pool_proj answer 0, so the
 // level's 1x1 projection stays a launch of its own beside the pooled build
-int g_pp128_pool_proj = [] {
-  const char* e = getenv("BE_CONV_PP128_POOL_PROJ");
-  return e ? atoi(e) : 1;
-}();
+int g_pp128_pool_proj = be_env_int("BE_CONV_PP128_POOL_PROJ", 1);
 
 // BE_CPNET_L3_PREPOOL (default 1, A/B): 0 makes be_conv_pp128_takes_prepool answer 0, so CPnet's level-3
 // entry keeps its two pooled-input launches of the per-layer kernel
-int g_l3_prepool = [] {
-  const char* e = getenv("BE_CPNET_L3_PREPOOL");
-  return e ? atoi(e) : 1;
-}();
+int g_l3_prepool = be_env_int("BE_CPNET_L3_PREPOOL", 1);
 
 // BE_CONV_PP128_C256 (default 1, A/B): 0 makes be_conv_pp128_takes_c256 answer 0, so the 128 -> 256
 // entry conv of a pre-pooled level stays on conv2d_nhwc_kernel
-int g_pp128_c256 = [] {
-  const char* e = getenv("BE_CONV_PP128_C256");
-  return e ? atoi(e) : 1;
-}();
+int g_pp128_c256 = be_env_int("BE_CONV_PP128_C256", 1);
 
 int g_pp128_c256_launches = 0;  // be_conv_pp128_c256_launches
 int g_pp128_grid = 0;      // be_conv_pp128_set_grid (0 = one workgroup per CU)
@@ -765,6 +745,44 @@ int pp128_grid_for(int N, int H, int W, int* tiles_x, int* tiles_y, int halves =
   if (tiles_x) *tiles_x = tx;
   if (tiles_y) *tiles_y = ty;
   return g;
+}
+
+// The fields every build shares; an entry point sets on top only what is its own (tiles_x / tiles_y come
+// from pp128_grid_for, everything else stays at Args' defaults).
+pp128::Args pp128_args(const void* x, const float* pscale, const float* pshift, int pshift_ns, int pscale_ns, int prelu,
+                       const void* wfrag, const float* bias, void* out, int N, int H, int W) {
+  pp128::Args a;
+  a.x = (const bf16_t*)x; a.sa = pscale; a.ta = pshift; a.sa_ns = pscale_ns; a.ta_ns = pshift_ns;
+  a.wf = (const bf16_t*)wfrag; a.bias = bias; a.out = (bf16_t*)out;
+  a.N = N; a.H = H; a.W = W; a.relu = prelu & 1;
+  a.stamps = g_pp128_stamps;
+  return a;
+}
+
+// One launch of the <POOL, PROJ, C256> build on `grid` workgroups: the phase-stamped instantiation when a
+// stamp buffer is set (diagnostics: be_conv_pp128_set_stamps; -30 if it is too small for the grid), the
+// PROJ build's larger LDS with its once-per-device attribute (-33).
+template <bool POOL, bool PROJ, bool C256>
+int pp128_launch(const pp128::Args& a, int grid, hipStream_t stream) {
+  constexpr int lds = PROJ ? pp128::LDS_PROJ : pp128::LDS;
+  if constexpr (PROJ) {
+    static bool attr_set[BE_MAX_DEV] = {};
+    if (!attr_set[be_cur_dev()]) {
+      if (hipFuncSetAttribute(reinterpret_cast<const void*>(&pp128::conv_pp128_kernel<false, POOL, PROJ, C256>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess ||
+          hipFuncSetAttribute(reinterpret_cast<const void*>(&pp128::conv_pp128_kernel<true, POOL, PROJ, C256>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)
+        return -33;
+      attr_set[be_cur_dev()] = true;
+    }
+  }
+  if (a.stamps != nullptr) {
+    if (grid > g_pp128_stamps_cap) return -30;
+    hipLaunchKernelGGL((pp128::conv_pp128_kernel<true, POOL, PROJ, C256>), dim3(grid), dim3(pp128::NTP), lds, stream, a);
+  } else {
+    hipLaunchKernelGGL((pp128::conv_pp128_kernel<false, POOL, PROJ, C256>), dim3(grid), dim3(pp128::NTP), lds, stream, a);
+  }
+  return BE_CHECK_LAUNCH();
 }
 
 }  // namespace
@@ -813,46 +831,25 @@ int be_conv2d_nhwc_frag_res(const void* x, const void* x2, const float* pscale, 
                             int N, int H, int W, int Hs, int Ws, int Cin, int Cout, int cout_valid, int ks, int ck,
                             int tco, int inmode, int out_f32_nchw, int nw, const float* qscale, const float* qshift,
                             int qshift_ns, const void* wfrag, int res_up2, hipStream_t stream) {
-  const bool shape_ok = wfrag && ks == 3 && ck == 32 && inmode == 0 && !x2 && !out_f32_nchw && Cin == 128 &&
-                        Cout == 128 && Hs == H && Ws == W && !(prelu & 2) && !qscale && !qshift && x && out;
+  // what the plain and the pooled call have in common
+  const bool frag_ok = wfrag && ks == 3 && ck == 32 && !x2 && !out_f32_nchw && Cout == 128 && !(prelu & 2) && !qscale &&
+                       !qshift && x && out;
+  const bool shape_ok = frag_ok && inmode == 0 && Cin == 128 && Hs == H && Ws == W;
   if (res_up2 && !(shape_ok && res && H % 2 == 0 && W % 2 == 0)) return -31;
   // the pooled entry conv: 3x3, 64 -> 128, INMODE 2 from an even source, no residual
-  const bool pool_ok = g_pp128_pool && wfrag && ks == 3 && ck == 32 && inmode == 2 && !x2 && !out_f32_nchw && Cin == 64 &&
-                       Cout == 128 && Hs == 2 * H && Ws == 2 * W && !(prelu & 2) && !qscale && !qshift && !res && x && out;
+  const bool pool_ok = frag_ok && g_pp128_pool && inmode == 2 && Cin == 64 && Hs == 2 * H && Ws == 2 * W && !res;
   if (shape_ok || pool_ok) {
-    pp128::Args a;
+    pp128::Args a = pp128_args(x, pscale, pshift, pshift_ns, pscale_ns, prelu, wfrag, bias, out, N, H, W);
     const int g = pp128_grid_for(N, H, W, &a.tiles_x, &a.tiles_y);
     if (g > 0 && pool_ok) {
-      a.x = (const bf16_t*)x; a.sa = pscale; a.ta = pshift; a.sa_ns = pscale_ns; a.ta_ns = pshift_ns;
-      a.wf = (const bf16_t*)wfrag; a.bias = bias; a.res = nullptr; a.out = (bf16_t*)out;
-      a.N = N; a.H = H; a.W = W; a.relu = prelu & 1;
-      a.res_up2 = 0;
-      a.sp = a.tp = a.bias_p = nullptr; a.wpf = nullptr; a.out2 = nullptr;
-      a.stamps = g_pp128_stamps;
       ++g_pp128_pool_launches;
-      if (g_pp128_stamps != nullptr) {
-        if (g > g_pp128_stamps_cap) return -30;
-        hipLaunchKernelGGL((pp128::conv_pp128_kernel<true, true>), dim3(g), dim3(pp128::NTP), pp128::LDS, stream, a);
-        return BE_CHECK_LAUNCH();
-      }
-      hipLaunchKernelGGL((pp128::conv_pp128_kernel<false, true>), dim3(g), dim3(pp128::NTP), pp128::LDS, stream, a);
-      return BE_CHECK_LAUNCH();
+      return pp128_launch<true, false, false>(a, g, stream);
     }
     if (g > 0) {
-      a.x = (const bf16_t*)x; a.sa = pscale; a.ta = pshift; a.sa_ns = pscale_ns; a.ta_ns = pshift_ns;
-      a.wf = (const bf16_t*)wfrag; a.bias = bias; a.res = (const bf16_t*)res; a.out = (bf16_t*)out;
-      a.N = N; a.H = H; a.W = W; a.relu = prelu & 1;
+      a.res = (const bf16_t*)res;
       a.res_up2 = res_up2 ? 1 : 0;
-      a.sp = a.tp = a.bias_p = nullptr; a.wpf = nullptr; a.out2 = nullptr;
-      a.stamps = g_pp128_stamps;
       ++g_pp128_launches;
-      if (g_pp128_stamps != nullptr) {
-        if (g > g_pp128_stamps_cap) return -30;
-        hipLaunchKernelGGL(pp128::conv_pp128_kernel<true>, dim3(g), dim3(pp128::NTP), pp128::LDS, stream, a);
-        return BE_CHECK_LAUNCH();
-      }
-      hipLaunchKernelGGL(pp128::conv_pp128_kernel<false>, dim3(g), dim3(pp128::NTP), pp128::LDS, stream, a);
-      return BE_CHECK_LAUNCH();
+      return pp128_launch<false, false, false>(a, g, stream);
     }
   }
   if (res_up2) return -31;
@@ -912,31 +909,11 @@ int be_conv_pp128_pool_proj(const void* x, const float* pscale, const float* psh
                             hipStream_t stream) {
   if (!x || !wfrag || !out || !sp || !tp || !wpfrag || !out2 || out == out2 || (prelu & ~1)) return -32;
   if (!be_conv_pp128_takes_pool_proj(N, Hs, Ws)) return -32;
-  pp128::Args a;
+  pp128::Args a = pp128_args(x, pscale, pshift, pshift_ns, pscale_ns, prelu, wfrag, bias, out, N, Hs / 2, Ws / 2);
   const int g = pp128_grid_for(N, Hs / 2, Ws / 2, &a.tiles_x, &a.tiles_y);
-  a.x = (const bf16_t*)x; a.sa = pscale; a.ta = pshift; a.sa_ns = pscale_ns; a.ta_ns = pshift_ns;
-  a.wf = (const bf16_t*)wfrag; a.bias = bias; a.res = nullptr; a.out = (bf16_t*)out;
-  a.N = N; a.H = Hs / 2; a.W = Ws / 2; a.relu = prelu & 1;
-  a.res_up2 = 0;
   a.sp = sp; a.tp = tp; a.wpf = (const bf16_t*)wpfrag; a.bias_p = bias_p; a.out2 = (bf16_t*)out2;
-  a.stamps = g_pp128_stamps;
-  static bool attr_set[BE_MAX_DEV] = {};
-  if (!attr_set[be_cur_dev()]) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&pp128::conv_pp128_kernel<false, true, true>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, pp128::LDS_PROJ) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&pp128::conv_pp128_kernel<true, true, true>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, pp128::LDS_PROJ) != hipSuccess)
-      return -33;
-    attr_set[be_cur_dev()] = true;
-  }
   ++g_pp128_pool_launches;
-  if (g_pp128_stamps != nullptr) {  // diagnostics: be_conv_pp128_set_stamps
-    if (g > g_pp128_stamps_cap) return -30;
-    hipLaunchKernelGGL((pp128::conv_pp128_kernel<true, true, true>), dim3(g), dim3(pp128::NTP), pp128::LDS_PROJ, stream, a);
-    return BE_CHECK_LAUNCH();
-  }
-  hipLaunchKernelGGL((pp128::conv_pp128_kernel<false, true, true>), dim3(g), dim3(pp128::NTP), pp128::LDS_PROJ, stream, a);
-  return BE_CHECK_LAUNCH();
+  return pp128_launch<true, true, false>(a, g, stream);
 }
 
 // The size rule of the 256-channel build, in one place: pp128_grid_for with the item count (tiles x 2
@@ -980,23 +957,11 @@ int be_conv_pp128_c256(const void* x, const float* pscale, const float* pshift, 
                        int H, int W, hipStream_t stream) {
   if (!x || !wfrag || !out || x == out || !qscale || !qshift || (prelu & ~3)) return -34;
   if (!be_conv_pp128_takes_c256(N, H, W)) return -34;
-  pp128::Args a;
+  pp128::Args a = pp128_args(x, pscale, pshift, pshift_ns, pscale_ns, prelu, wfrag, bias, out, N, H, W);
   const int g = pp128_c256_grid_for(N, H, W, &a.tiles_x, &a.tiles_y);
-  a.x = (const bf16_t*)x; a.sa = pscale; a.ta = pshift; a.sa_ns = pscale_ns; a.ta_ns = pshift_ns;
-  a.wf = (const bf16_t*)wfrag; a.bias = bias; a.res = nullptr; a.out = (bf16_t*)out;
-  a.N = N; a.H = H; a.W = W; a.relu = prelu & 1;
-  a.res_up2 = 0;
-  a.sp = a.tp = a.bias_p = nullptr; a.wpf = nullptr; a.out2 = nullptr;
   a.qs = qscale; a.qt = qshift; a.qrelu = (prelu >> 1) & 1;
-  a.stamps = g_pp128_stamps;
   ++g_pp128_c256_launches;
-  if (g_pp128_stamps != nullptr) {  // diagnostics: be_conv_pp128_set_stamps
-    if (g > g_pp128_stamps_cap) return -30;
-    hipLaunchKernelGGL((pp128::conv_pp128_kernel<true, false, false, true>), dim3(g), dim3(pp128::NTP), pp128::LDS, stream, a);
-    return BE_CHECK_LAUNCH();
-  }
-  hipLaunchKernelGGL((pp128::conv_pp128_kernel<false, false, false, true>), dim3(g), dim3(pp128::NTP), pp128::LDS, stream, a);
-  return BE_CHECK_LAUNCH();
+  return pp128_launch<false, false, true>(a, g, stream);
 }
 
 // 1 if such a call may also hand its residual over at half resolution (be_conv2d_nhwc_frag_res).

@@ -6,8 +6,8 @@ half-block.  Prints JSON lines."""
 from __future__ import annotations
 
 import argparse
+import dataclasses
 import json
-import os
 import sys
 import time
 from pathlib import Path
@@ -16,7 +16,8 @@ sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 
 import torch  # noqa: E402
 
-from bioengine_worker_amd.models.cpnet import CPnet, CPnetEngine  # noqa: E402
+from bioengine_worker_amd.models.cpnet import CPnet, CPnetEngine, CPnetEngineOptions  # noqa: E402
+from bioengine_worker_amd.ops import conv as cv  # noqa: E402
 from bioengine_worker_amd.ops import conv_pair as cp  # noqa: E402
 
 
@@ -44,10 +45,9 @@ def main():
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     net = CPnet().randomize_(0).eval()
-    eng_pair = CPnetEngine(net, dev)
-    os.environ["BE_CPNET_PAIR"] = "0"
-    eng_layer = CPnetEngine(net, dev)
-    os.environ["BE_CPNET_PAIR"] = "1"
+    opt = CPnetEngineOptions.from_env()
+    eng_pair = CPnetEngine(net, dev, opt)
+    eng_layer = CPnetEngine(net, dev, dataclasses.replace(opt, pair=False))
     x = torch.randn(args.tiles, 224, 224, 8, device=dev).bfloat16()
     x[..., 2:] = 0
     res = {"pair": [], "layer": []}
@@ -79,7 +79,7 @@ def main():
     for key, (hs, cin, hx2, res) in shp.items():
         spec = P[key]
         xs = torch.randn(N, hs, hs, cin, device=dev).bfloat16()
-        H, W = cp._out_hw(xs, spec.inmode)
+        H, W = cv.out_hw(xs, spec.inmode)
         cm = spec.cm
         x2 = torch.randn(N, H, W, cm, device=dev).bfloat16() if hx2 else None
         rr = None
