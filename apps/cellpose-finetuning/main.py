@@ -46,6 +46,7 @@ from bioengine_worker_amd.cellpose.datasets import (  # noqa: F401  (re-exported
     create_dataset_split,
     decode_image,
     decode_labels,
+    is_outline_file,
     list_artifact_files,
     list_artifact_files_recursive,
     list_matching_artifact_paths,
@@ -54,6 +55,7 @@ from bioengine_worker_amd.cellpose.datasets import (  # noqa: F401  (re-exported
     match_image_annotation_pairs,
     read_image,
     read_labels,
+    read_outlines,
 )
 from bioengine_worker_amd.cellpose.model_store import BUILTIN_MODELS
 from bioengine_worker_amd.profiling import trace
@@ -745,9 +747,14 @@ class CellposeFinetune:
         self,
         artifact: str | None = Field(None, description="Artifact 'workspace/alias' containing images and annotations."),
         image_paths: list | None = Field(None, description="Artifact-relative image paths to segment."),
-        annotation_paths: list | None = Field(None, description="Artifact-relative label images, one per image."),
+        annotation_paths: list | None = Field(None, description="Artifact-relative annotations, one per image: label "
+                                                                "images, or polygons as .geojson / .json files."),
         input_arrays: list | None = Field(None, description="Images as arrays ([H,W], [H,W,C] or [C,H,W])."),
         label_arrays: list | None = Field(None, description="Ground-truth label images [H,W], one per input array."),
+        label_outlines: list | None = Field(None, description="Ground-truth polygons instead of label_arrays, one "
+                                                              "document per input array: GeoJSON (FeatureCollection, "
+                                                              "features, Polygon / MultiPolygon), or the 'rings' "
+                                                              "outlines that infer returns."),
         model: str = Field("cpsam", description="Built-in model ('cpsam', 'cyto3'), a session id of a fine-tuned "
                                                 "model, or a published model artifact id."),
         diameter: float | str | None = Field(None, description="Approximate object diameter (rescale to the model's 30 px), "
@@ -771,12 +778,21 @@ class CellposeFinetune:
         {input_path, ap, tp, fp, fn, n_true, n_pred} per image (lists over the thresholds; ``ap`` is
         None where both images are empty), and ``instance_metrics``, the image-mean document a
         training session reports.  Images of one shape are evaluated together, in chunks of 32; the
-        predicted masks are scored on the device and not returned.  2-D images only."""
+        predicted masks are scored on the device and not returned.  2-D images only.
+
+        The ground truth is a label image per input, or polygons: ``label_outlines`` (one document per
+        input array, any form ``cellpose.reference.outlines_to_rings`` accepts, so the ``outlines`` of
+        an ``infer`` result -- corrected in an annotation tool or not -- can be handed back) or
+        ``annotation_paths`` naming ``.geojson`` / ``.json`` files.  Polygons are rasterised at their
+        image's size on the device the masks are on (``cellpose.reference.rasterize_rings``: pixel
+        centres, even-odd, top-left ties, the largest label wins) and never cross the request path as
+        a label image.  ``label_arrays`` together with ``label_outlines`` is a ``ValueError``."""
         if isinstance(artifact, dict):
             w = artifact
             artifact = w.get("artifact", w.get("artifact_id", w.get("id")))
             image_paths, annotation_paths = w.get("image_paths", image_paths), w.get("annotation_paths", annotation_paths)
             input_arrays, label_arrays = w.get("input_arrays", input_arrays), w.get("label_arrays", label_arrays)
+            label_outlines = w.get("label_outlines", label_outlines)
             model, diameter = w.get("model", model), w.get("diameter", diameter)
             flow_threshold = w.get("flow_threshold", flow_threshold)
             cellprob_threshold = w.get("cellprob_threshold", cellprob_threshold)
@@ -784,7 +800,10 @@ class CellposeFinetune:
             thresholds, augment = w.get("thresholds", thresholds), w.get("augment", augment)
             normalize = w.get("normalize", normalize)
         from bioengine_worker_amd.cellpose.metrics import DEFAULT_THRESHOLDS, metrics_document
+        from bioengine_worker_amd.cellpose.reference import outlines_to_rings, unwrap_outlines
 
+        if _opt(label_arrays) is not None and _opt(label_outlines) is not None:
+            raise ValueError("Provide label_arrays or label_outlines, not both")
         ths = [float(t) for t in (_opt(thresholds) or DEFAULT_THRESHOLDS)]
         if len(ths) > 8 or not all(0.0 < t <= 1.0 for t in ths):
             raise ValueError(f"thresholds must be at most 8 values in (0, 1], got {ths}")
@@ -792,16 +811,21 @@ class CellposeFinetune:
         model_id = await self.resolve_model_id(model)
         if _opt(input_arrays) is not None:
             images = [np.asarray(a) for a in input_arrays]
-            labels = [decode_labels(np.asarray(a)) for a in (_opt(label_arrays) or [])]
+            if _opt(label_outlines) is not None:  # polygons dicts: rasterised with their chunk, on its device
+                labels = [outlines_to_rings(unwrap_outlines(d)) for d in label_outlines]
+            else:
+                labels = [decode_labels(np.asarray(a)) for a in (_opt(label_arrays) or [])]
             names = [f"input_arrays[{i}]" for i in range(len(images))]
         elif _opt(artifact) is not None:
             names = list(image_paths or [])
             if len(names) != len(annotation_paths or []):
                 raise ValueError(f"{len(names)} image_paths but {len(annotation_paths or [])} annotation_paths")
             images = await self._images_from_artifact(artifact, names)
-            labels = await self._images_from_artifact(artifact, list(annotation_paths), reader=read_labels)
+            labels = await self._images_from_artifact(
+                artifact, list(annotation_paths), reader=lambda p: read_outlines(p) if is_outline_file(p) else read_labels(p))
         else:
-            raise ValueError("Provide input_arrays + label_arrays or artifact + image_paths + annotation_paths")
+            raise ValueError("Provide input_arrays + label_arrays (or label_outlines) or artifact + image_paths + "
+                             "annotation_paths")
         if len(images) != len(labels):
             raise ValueError(f"{len(images)} images but {len(labels)} label images")
         if _opt(enable_clahe):
@@ -813,10 +837,10 @@ class CellposeFinetune:
         chw = [image_chw(im, runner.nchan) for im in images]
         groups: dict = {}
         for i, (name, c, lab) in enumerate(zip(names, chw, labels)):
-            if lab.ndim != 2 or tuple(lab.shape) != tuple(c.shape[1:]):
+            if not isinstance(lab, dict) and (lab.ndim != 2 or tuple(lab.shape) != tuple(c.shape[1:])):
                 raise ValueError(f"{name}: label image of shape {tuple(lab.shape)} does not fit the image's "
                                  f"{tuple(c.shape[1:])}")
-            groups.setdefault((c.shape, c.dtype.str), []).append(i)
+            groups.setdefault((c.shape, c.dtype.str, isinstance(lab, dict)), []).append(i)
         K = len(ths)
         ap = np.full((len(chw), K), np.nan, np.float32)
         cnt = {k: np.zeros((len(chw), K), np.int64) for k in ("tp", "fp", "fn")}
@@ -827,8 +851,9 @@ class CellposeFinetune:
 
                 def run(part=part):
                     with self._gpu_lock:
-                        res = runner.evaluate(np.stack([chw[i] for i in part]), np.stack([labels[i] for i in part]),
-                                              thresholds=ths, **prm)
+                        truth = [labels[i] for i in part]
+                        res = runner.evaluate(np.stack([chw[i] for i in part]),
+                                              truth if isinstance(truth[0], dict) else np.stack(truth), thresholds=ths, **prm)
                     res.pop("masks")
                     return res
 
@@ -859,7 +884,13 @@ class CellposeFinetune:
                 for i, (im, lab) in enumerate(zip(arrays.get(f"{split}_images") or [], arrays.get(f"{split}_labels") or [])):
                     ip, lp = data / f"{split}_{i:04d}_img.npy", data / f"{split}_{i:04d}_masks.npy"
                     np.save(ip, np.asarray(im))
-                    np.save(lp, np.asarray(lab).astype(np.int32))
+                    if isinstance(lab, dict) or (isinstance(lab, (list, tuple)) and all(isinstance(x, dict) for x in lab)):
+                        # polygons (GeoJSON, 'rings' items or a polygons dict): kept as they are and
+                        # rasterised at the image's size when the session loads its pairs
+                        lp = lp.with_name(f"{split}_{i:04d}_masks.geojson")
+                        lp.write_text(json.dumps(lab, default=lambda o: o.tolist()))
+                    else:
+                        np.save(lp, np.asarray(lab).astype(np.int32))
                     pairs[split].append({"image": str(ip), "annotation": str(lp)})
         else:
             aid = params["artifact_id"]
@@ -942,12 +973,21 @@ class CellposeFinetune:
         batch_size: int = Field(1, description="Crops per optimisation step and GPU (reference: 1)."),
         n_gpus: int = Field(1, description="Data-parallel GPUs (a gang of one process per GPU, RCCL all-reduce)."),
         train_arrays: list | None = Field(None, description="Training images as arrays (instead of an artifact)."),
-        label_arrays: list | None = Field(None, description="Instance label arrays for train_arrays."),
+        label_arrays: list | None = Field(None, description="Instance labels for train_arrays: a label array per "
+                                                            "image, or polygons (a GeoJSON dict / a list of features "
+                                                            "or 'rings' outlines), rasterised at the image's size."),
         test_arrays: list | None = Field(None, description="Test images as arrays."),
-        test_label_arrays: list | None = Field(None, description="Instance label arrays for test_arrays."),
+        test_label_arrays: list | None = Field(None, description="Instance labels for test_arrays, as label_arrays."),
         context: dict | None = Field(None, description="Authentication context (injected)."),
     ) -> dict:
-        """Start asynchronous fine-tuning; returns the initial session status with its ``session_id``."""
+        """Start asynchronous fine-tuning; returns the initial session status with its ``session_id``.
+
+        Annotations are label images or polygons.  With arrays, an entry of ``label_arrays`` /
+        ``test_label_arrays`` that is a dict or a list of dicts is a polygon document
+        (``cellpose.reference.outlines_to_rings``) and is stored as ``*_masks.geojson`` instead of
+        ``.npy``; artifact annotations ending in ``.geojson`` / ``.json`` are polygons too.  Either way
+        they are rasterised at their image's size when the session loads its pairs, on the training
+        device, and train as label images do."""
         if isinstance(artifact, dict):
             w = artifact
             artifact = w.get("artifact", w.get("artifact_id", w.get("id")))

@@ -416,11 +416,53 @@ def decode_labels(arr: np.ndarray) -> np.ndarray:
     return np.asarray(a).astype(np.int32)
 
 
-def read_labels(path: str | Path) -> np.ndarray:
-    return decode_labels(read_image(path))
+OUTLINE_SUFFIXES = (".geojson", ".json")
+
+
+def is_outline_file(path: str | Path) -> bool:
+    """Whether an annotation file holds polygons (GeoJSON or the app's ``"rings"`` form) and not a
+    label image: by its suffix, ``.geojson`` or ``.json``."""
+    return str(path).lower().endswith(OUTLINE_SUFFIXES)
+
+
+def read_outlines(path: str | Path) -> dict:
+    """The polygons dict (:func:`reference.outlines_to_rings`) of a ``.geojson`` / ``.json`` annotation."""
+    import json
+
+    from .reference import outlines_to_rings, unwrap_outlines
+
+    try:
+        doc = json.loads(Path(path).read_bytes())
+    except ValueError as e:
+        raise ValueError(f"annotation {path} is not valid JSON: {e}") from None
+    return outlines_to_rings(unwrap_outlines(doc))
+
+
+def read_labels(path: str | Path, shape=None, device=None) -> np.ndarray:
+    """Instance labels int32 of an annotation file.  Label images are decoded as they are
+    (:func:`decode_labels`).  Files ending in ``.geojson`` or ``.json`` hold polygons in one of the
+    forms :func:`reference.outlines_to_rings` accepts and are rasterised at ``shape`` (H, W)
+    (:func:`reference.rasterize_rings`; on ``device`` by the HIP kernel when that is a GPU);
+    without ``shape`` that is a ``ValueError``."""
+    if not is_outline_file(path):
+        return decode_labels(read_image(path))
+    if shape is None:
+        raise ValueError(f"annotation {path} holds polygons: read_labels needs the image's shape (H, W) to rasterise them")
+    from .gpu import rasterize_rings_gpu
+
+    polys = read_outlines(path)
+    H, W = int(shape[0]), int(shape[1])
+    polys = dict(polys, ring_image=np.zeros(np.asarray(polys["ring_label"]).shape[0], np.int32))
+    return rasterize_rings_gpu(polys, 1, H, W, "cpu" if device is None else device)[0].cpu().numpy()
 
 
 def has_foreground(path: str | Path) -> bool:
+    if is_outline_file(path):  # without rasterising: some ring has at least three vertices
+        try:
+            return bool((np.diff(np.asarray(read_outlines(path)["ring_offsets"])) >= 3).any())
+        except Exception as e:  # noqa: BLE001
+            log.warning("skipping unreadable annotation %s: %s", path, e)
+            return False
     try:
         lab = read_labels(path)
     except Exception as e:  # noqa: BLE001

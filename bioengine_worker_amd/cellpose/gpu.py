@@ -1,6 +1,6 @@
 """GPU (HIP) implementation of Cellpose pre/post-processing on batches of images.
 
-Every heavy step is a kernel in ``csrc/kernels/{tiles,cellpose_dynamics,cellpose_dynamics3d,cellpose_masks,cellpose_stitch,cellpose_measure,cellpose_ap,cellpose_rings}.hip``;
+Every heavy step is a kernel in ``csrc/kernels/{tiles,cellpose_dynamics,cellpose_dynamics3d,cellpose_masks,cellpose_stitch,cellpose_measure,cellpose_ap,cellpose_rings,cellpose_raster}.hip``;
 torch is only used for tiny bookkeeping (sorting the seed keys, prefix sums over labels, building
 per-mask job lists).  The semantics are those of :mod:`bioengine_worker_amd.cellpose.reference`
 (the CPU oracle), which the GPU tests compare against.
@@ -1518,6 +1518,156 @@ def mask_rings_gpu(M: torch.Tensor, nlab: int | None = None, volume: bool = Fals
         raise RuntimeError(f"be_cp_rings_trace: a walk left its counted bounds (error word {e}): the labels changed "
                            "while they were traced")
     return _rings_result(verts, off[:R + 1], o32[:R], area2[:R], o32[cap:cap + R], per_image)
+
+
+# ------------------------------------------------------------------ polygons -> labels
+
+RASTER_BAND = 64    # rows of a job of cellpose_raster.hip: one per lane
+RASTER_CHUNK = 256  # columns of a job: 64 * CW of cellpose_raster.hip
+
+
+def _host_array(x) -> np.ndarray:
+    """A polygons-dict array on the host.  A device tensor is copied there, which waits for the
+    current stream: that serves round trips from :func:`mask_rings_gpu` only."""
+    return x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x)
+
+
+def _raster_inputs(polys: dict, B: int, H: int, W: int):
+    """Every check of :func:`rasterize_rings_gpu`, on the host: the quantised vertices int64 [V, 2],
+    the ring offsets, labels and images (int64 [R])."""
+    B, H, W = int(B), int(H), int(W)
+    if min(B, H, W) < 0:
+        raise ValueError(f"rasterize_rings_gpu: negative size {B} x {H} x {W}")
+    if max(H, W) > 2 ** 15:
+        raise ValueError(f"rasterize_rings_gpu: image {H} x {W} is too large (H and W must not exceed 2^15)")
+    if B * H * W >= 2 ** 31:
+        raise ValueError(f"rasterize_rings_gpu: batch {B} x {H} x {W} is too large (B*H*W must be below 2^31)")
+    host = {k: _host_array(polys[k]) for k in ("verts", "ring_offsets", "ring_label")}
+    q, off, labs = ref.polygon_arrays(host, "rasterize_rings_gpu")
+    R = labs.shape[0]
+    if q.shape[0] >= 2 ** 31:
+        raise ValueError("rasterize_rings_gpu: 2^31 vertices or more are not supported")
+    if polys.get("ring_image") is not None:
+        img = _host_array(polys["ring_image"]).astype(np.int64).reshape(-1)
+        if img.shape[0] != R:
+            raise ValueError(f"rasterize_rings_gpu: ring_image has {img.shape[0]} entries for {R} rings")
+    elif polys.get("image_rings") is not None:
+        per = _host_array(polys["image_rings"]).astype(np.int64).reshape(-1)
+        if per.shape[0] != B + 1 or per[0] != 0 or per[-1] != R or (np.diff(per) < 0).any():
+            raise ValueError(f"rasterize_rings_gpu: image_rings does not fit {B} images and {R} rings")
+        img = np.repeat(np.arange(B, dtype=np.int64), np.diff(per))
+    else:
+        raise ValueError("rasterize_rings_gpu: a batch of polygons needs ring_image [R] or image_rings [B + 1]")
+    if R and (img.min() < 0 or img.max() >= B):
+        raise ValueError(f"rasterize_rings_gpu: ring_image must lie in [0, {B}), got {int(img.min())} .. {int(img.max())}")
+    return q, off, labs, img
+
+
+def _raster_plan(q, off, labs, img, H: int, W: int):
+    """The edge list and the job table of ``csrc/kernels/cellpose_raster.hip``, in vectorised numpy.
+
+    Rings are sorted by (image, label), so that a *group* -- one label of one image -- is a
+    contiguous run of edges int32 [E, 4] (Y0, X0, Y1, X1).  A group's pixel box holds the rows and
+    columns whose centre lies inside its vertex range (no pixel outside it can be inside the
+    polygon), clipped to the image; a job int32 [8] is (first edge, edges, image, label, first row,
+    rows <= 64, first column, columns <= 256).  Returns ``(edges, jobs)``, or None without jobs."""
+    n = np.diff(off)
+    order = np.lexsort((labs, img))
+    order = order[n[order] > 0]
+    if order.size == 0:
+        return None
+    cnt, start = n[order], off[:-1][order]
+    eoff = np.concatenate([[0], np.cumsum(cnt)])
+    if (np.diff(order) > 0).all():  # already in (image, label) order, the usual case: the vertices stay where they are
+        src = q
+    else:
+        ring = np.repeat(np.arange(order.size), cnt)
+        src = q[np.arange(eoff[-1]) + (start - eoff[:-1])[ring]]
+    # edge i runs from vertex i to vertex i + 1, the last one of a ring back to the ring's first
+    edges = np.empty((int(eoff[-1]), 4), np.int32)
+    edges[:, :2] = src
+    edges[:-1, 2:] = src[1:]
+    edges[eoff[1:] - 1, 2:] = src[eoff[:-1]]
+    gi, gl = img[order], labs[order]
+    first = np.flatnonzero(np.concatenate([[True], (gi[1:] != gi[:-1]) | (gl[1:] != gl[:-1])]))
+    e0 = eoff[first]
+    ne = np.diff(np.concatenate([e0, eoff[-1:]]))
+    lo = np.stack([np.minimum.reduceat(edges[:, c], e0) for c in (0, 1)], 1).astype(np.int64)
+    hi = np.stack([np.maximum.reduceat(edges[:, c], e0) for c in (0, 1)], 1).astype(np.int64)
+    half, sub = ref.RASTER_SUBPIX // 2, ref.RASTER_SUBPIX
+    p0 = np.maximum(-((half - lo) // sub), 0)                 # first centre at or beyond the minimum
+    p1 = np.minimum(-((half - hi) // sub) - 1, (H - 1, W - 1))  # last centre before the maximum
+    ok = (p0 <= p1).all(1)
+    nb = np.where(ok, (p1[:, 0] - p0[:, 0]) // RASTER_BAND + 1, 0)
+    nc = np.where(ok, (p1[:, 1] - p0[:, 1]) // RASTER_CHUNK + 1, 0)
+    nj = nb * nc
+    J = int(nj.sum())
+    if J == 0:
+        return None
+    if J >= 2 ** 31:
+        raise ValueError(f"rasterize_rings_gpu: {J} jobs are too many for one launch")
+    g = np.repeat(np.arange(first.size), nj)
+    k = np.arange(J) - (np.cumsum(nj) - nj)[g]
+    y0 = p0[g, 0] + RASTER_BAND * (k // nc[g])
+    x0 = p0[g, 1] + RASTER_CHUNK * (k % nc[g])
+    jobs = np.stack([e0[g], ne[g], gi[first][g], gl[first][g], y0, np.minimum(p1[g, 0] - y0 + 1, RASTER_BAND),
+                     x0, np.minimum(p1[g, 1] - x0 + 1, RASTER_CHUNK)], 1).astype(np.int32)
+    return edges, jobs
+
+
+def _raster_oracle(q, off, labs, img, B: int, H: int, W: int) -> np.ndarray:
+    out = np.zeros((B, H, W), np.int32)
+    n = np.diff(off)
+    for b in np.unique(img).tolist():
+        rs = np.flatnonzero(img == b)
+        # the quantised vertices go back as exact multiples of 1 / 256: quantising them again is the identity
+        verts = np.concatenate([q[off[r]:off[r + 1]] for r in rs]).astype(np.float64) / ref.RASTER_SUBPIX
+        out[b] = ref.rasterize_rings({"verts": verts, "ring_offsets": np.concatenate([[0], np.cumsum(n[rs])]),
+                                      "ring_label": labs[rs]}, (H, W))
+    return out
+
+
+def rasterize_rings_gpu(polys: dict, B: int, H: int, W: int, device) -> torch.Tensor:
+    """Label images of a batch of polygons, rasterised on the device: HIP implementation of
+    :func:`reference.rasterize_rings` (``csrc/kernels/cellpose_raster.hip``), equal to it in every
+    pixel, bit-identical from run to run and independent of the launch geometry.
+
+    ``polys``: a polygons dict for the whole batch -- ``verts`` [V, 2] (y, x) of any integer or float
+    dtype, ``ring_offsets`` int64 [R + 1], ``ring_label`` int32 [R], and either ``ring_image`` int32
+    [R] or ``image_rings`` int64 [B + 1], as :func:`mask_rings_gpu` returns them.  The arrays are
+    host arrays; device tensors are copied to the host first, which waits for the current stream
+    (that serves the round trip from :func:`mask_rings_gpu` only).  Returns int32 [B, H, W] on
+    ``device`` with ``label_bound`` (the largest label + 1, known on the host) set on the tensor, as
+    :func:`compute_masks_gpu` sets it.
+
+    Everything is checked on the host before any launch: the oracle's checks (offsets, positive
+    labels, finite coordinates inside [-32768, 65536] px), ``H, W <= 2^15``, ``B*H*W < 2^31``,
+    ``ring_image`` in ``[0, B)``.  The host also quantises the vertices, sorts the rings by (image,
+    label) and builds the job table (:func:`_raster_plan`); the device only ever sees integers.  An
+    empty batch, no rings, no vertices and polygons that contain no centre launch nothing and
+    return zeros.  Nothing is read back from the device and nothing is waited for; the kernel runs
+    on the current stream.  A CPU ``device`` runs the oracle per image."""
+    B, H, W = int(B), int(H), int(W)
+    q, off, labs, img = _raster_inputs(polys, B, H, W)
+    dev = torch.device(device)
+    bound = int(labs.max()) + 1 if labs.size else 1
+    if dev.type != "cuda":
+        out = torch.from_numpy(_raster_oracle(q, off, labs, img, B, H, W))
+        out.label_bound = bound
+        return out
+    out = torch.zeros((B, H, W), dtype=torch.int32, device=dev)
+    out.label_bound = bound
+    plan = _raster_plan(q, off, labs, img, H, W) if B * H * W and q.shape[0] else None
+    if plan is None:
+        return out
+    edges, jobs = plan
+    E, J = edges.shape[0], jobs.shape[0]
+    with torch.cuda.device(dev):
+        # one upload: the edges (16 bytes each), then the jobs (32 bytes each, 16-byte aligned)
+        buf = torch.from_numpy(np.concatenate([edges.reshape(-1), jobs.reshape(-1)])).to(dev, non_blocking=True)
+        _native.call("be_cp_raster", _native.ptr(buf[:4 * E]), E, _native.ptr(buf[4 * E:]), J, _native.ptr(out), B, H, W,
+                     _native.stream(dev))
+    return out
 
 
 # ------------------------------------------------------------------ evaluation: average precision

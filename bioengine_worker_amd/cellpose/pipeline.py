@@ -1060,6 +1060,26 @@ class CellposeRunner:
             nlab = getattr(masks, "label_bound", None)
         return outline_rings(outline_launch(m, nlab=nlab, volume=volume))
 
+    # ---------------------------------------------------------------- polygon annotations
+    def labels_from_outlines(self, outlines, shape, device=None) -> torch.Tensor:
+        """Label images of polygon annotations (:func:`reference.rasterize_rings`): the way back from
+        :meth:`outlines`.
+
+        ``outlines``: a list with one document per image -- anything
+        :func:`reference.outlines_to_rings` accepts: a polygons dict, the app's ``"rings"`` list or
+        GeoJSON -- or a single document for a single image.  A list of the Z plane documents of a
+        stack (the app's ``{z, outlines}`` wrappers are unwrapped) gives the [Z, H, W] volume with the
+        volume's labels: it is the same call.  ``shape``: (H, W).  Returns int32 [B, H, W] on the
+        runner's device (or ``device``) with ``label_bound`` set, so that :meth:`measure`,
+        :meth:`outlines` and :meth:`score` skip their ``max()`` read.  On the GPU the polygons are
+        rasterised by the HIP kernel (:func:`gpu.rasterize_rings_gpu`: parsed, quantised and planned
+        on the host, nothing read back), everything else by the numpy oracle."""
+        from .gpu import rasterize_rings_gpu
+
+        parts = [ref.outlines_to_rings(ref.unwrap_outlines(d)) for d in outline_documents(outlines)]
+        H, W = int(shape[0]), int(shape[1])
+        return rasterize_rings_gpu(join_polygons(parts), len(parts), H, W, self.device if device is None else device)
+
     # ---------------------------------------------------------------- evaluation
     def score(self, masks_true, masks_pred, thresholds=(0.5, 0.75, 0.9), volume: bool = False) -> dict:
         """Average precision of predicted labels against ground truth (:func:`metrics.average_precision`).
@@ -1075,7 +1095,17 @@ class CellposeRunner:
         from .gpu import average_precision_gpu
 
         mp = masks_pred if torch.is_tensor(masks_pred) else torch.as_tensor(np.asarray(masks_pred))
-        mt = masks_true if torch.is_tensor(masks_true) else torch.as_tensor(np.asarray(masks_true))
+        nt = None
+        if is_outline_annotation(masks_true):
+            # polygon ground truth: rasterised at the prediction's (H, W) on the prediction's device
+            if mp.dim() < 2:
+                raise ValueError(f"score expects [B, H, W] masks or one [Z, H, W] volume, got shape {tuple(mp.shape)}")
+            mt = self.labels_from_outlines(masks_true, mp.shape[-2:], device=mp.device)
+            nt = mt.label_bound
+            if mp.dim() == 2 and mt.shape[0] == 1:
+                mt = mt[0]
+        else:
+            mt = masks_true if torch.is_tensor(masks_true) else torch.as_tensor(np.asarray(masks_true))
         if tuple(mt.shape) != tuple(mp.shape):
             raise ValueError(f"score: true masks {tuple(mt.shape)} do not fit predicted masks {tuple(mp.shape)}")
         if volume:
@@ -1088,7 +1118,7 @@ class CellposeRunner:
             raise ValueError(f"score expects [B, H, W] masks or one [Z, H, W] volume, got shape {tuple(mp.shape)}")
         ths = [thresholds] if np.isscalar(thresholds) else list(thresholds)
         bound = getattr(masks_pred, "label_bound", None)
-        ap, tp, fp, fn = average_precision_gpu(mt.to(mp.device), mp, ths, np_=bound)
+        ap, tp, fp, fn = average_precision_gpu(mt.to(mp.device), mp, ths, nt=nt, np_=bound)
         n_true, n_pred = (tp + fn)[:, 0], (tp + fp)[:, 0]
         return {"ap": ap, "tp": tp, "fp": fp, "fn": fn, "n_true": n_true, "n_pred": n_pred,
                 "summary": metrics.metrics_document(ap, ths, n_true.sum(), n_pred.sum())}
@@ -1102,6 +1132,45 @@ class CellposeRunner:
         res = self.score(masks_true, masks, thresholds)
         res["masks"] = masks
         return res
+
+
+def _outline_item(d) -> bool:
+    return isinstance(d, dict) and (d.get("type") == "Feature" or "rings" in d)
+
+
+def outline_documents(outlines) -> list:
+    """The per-image documents of a polygon annotation argument.  A dict is one document (a polygons
+    dict, a GeoJSON object or a ``{z, outlines}`` wrapper), and so is a non-empty list of GeoJSON
+    ``Feature`` s or of the app's ``{label, rings}`` items; any other list holds one document per
+    image (an image without cells is ``[]`` or an empty ``FeatureCollection``)."""
+    if isinstance(outlines, dict):
+        return [outlines]
+    if isinstance(outlines, (list, tuple)):
+        if outlines and all(_outline_item(d) for d in outlines):
+            return [outlines]
+        return list(outlines)
+    raise ValueError(f"expected a list of outline documents, got {type(outlines).__name__}")
+
+
+def is_outline_annotation(x) -> bool:
+    """Whether a ground-truth argument holds polygon documents and not label arrays."""
+    if isinstance(x, dict):
+        return True
+    return isinstance(x, (list, tuple)) and len(x) > 0 and all(isinstance(d, (dict, list, tuple)) and
+                                                              ref.is_outline_document(d) for d in x)
+
+
+def join_polygons(parts) -> dict:
+    """Per-image polygons dicts -> the arrays of the whole batch with ``ring_image``, the input of
+    :func:`gpu.rasterize_rings_gpu`.  Vertices become float64, which holds every integer and float
+    dtype below 2^53 exactly."""
+    vs = [np.asarray(p["verts"], np.float64).reshape(-1, 2) for p in parts]
+    offs = [np.asarray(p["ring_offsets"]).astype(np.int64) for p in parts]
+    nv = np.cumsum([0] + [v.shape[0] for v in vs])
+    return {"verts": np.concatenate(vs) if vs else np.zeros((0, 2)),
+            "ring_offsets": np.concatenate([o[:-1] + nv[b] for b, o in enumerate(offs)] + [nv[-1:]]).astype(np.int64),
+            "ring_label": np.concatenate([np.asarray(p["ring_label"]).astype(np.int64) for p in parts] + [np.zeros(0, np.int64)]),
+            "ring_image": np.concatenate([np.full(o.shape[0] - 1, b, np.int64) for b, o in enumerate(offs)] + [np.zeros(0, np.int64)])}
 
 
 def _planes_first(stack) -> torch.Tensor:

@@ -1074,3 +1074,234 @@ def rings_to_geojson(rings: dict, z: int | None = None) -> dict:
             {"type": "MultiPolygon", "coordinates": polys}
         feats.append({"type": "Feature", "properties": props, "geometry": geom})
     return {"type": "FeatureCollection", "features": feats}
+
+
+# ------------------------------------------------------------------ polygons -> labels
+
+#: sub-pixel steps per pixel of the rasteriser's integer lattice
+RASTER_SUBPIX = 256
+#: quantised coordinates must lie in [RASTER_QMIN, RASTER_QMAX] (-32,768 to 65,536 px): differences
+#: then stay below 2^25 and every product of the inside test below 2^50
+RASTER_QMIN, RASTER_QMAX = -(2 ** 23), 2 ** 24
+
+
+def quantize_verts(verts) -> np.ndarray:
+    """Vertices (any integer or float dtype, pixel-corner units) on the rasteriser's lattice:
+    ``floor(c * 256 + 0.5)`` in float64, as int64 of the same shape.  Raises ``ValueError`` on a
+    non-finite coordinate and on one outside ``[-2^23, 2^24]`` after quantisation."""
+    f = np.asarray(verts).astype(np.float64)
+    if not np.isfinite(f).all():
+        raise ValueError("quantize_verts: a coordinate is not finite")
+    q = np.floor(f * RASTER_SUBPIX + 0.5)
+    if q.size and (q.min() < RASTER_QMIN or q.max() > RASTER_QMAX):
+        raise ValueError(f"quantize_verts: a coordinate lies outside [{RASTER_QMIN // RASTER_SUBPIX}, "
+                         f"{RASTER_QMAX // RASTER_SUBPIX}] pixels")
+    return q.astype(np.int64)
+
+
+def polygon_arrays(polys: dict, what: str = "rasterize_rings"):
+    """The checked arrays of a polygons dict: quantised ``verts`` int64 [V, 2], ``ring_offsets``
+    int64 [R + 1] and ``ring_label`` int64 [R].  Raises ``ValueError`` when the offsets do not fit
+    (the check of the rings dicts, plus: they must not decrease), a label is not positive or a
+    coordinate cannot be quantised."""
+    off = np.asarray(polys["ring_offsets"]).astype(np.int64).reshape(-1)
+    v = np.asarray(polys["verts"])
+    if v.dtype.kind not in "iuf":
+        raise ValueError(f"{what}: verts must be integers or floats, got {v.dtype}")
+    v = v.reshape(-1, 2)
+    labs = np.asarray(polys["ring_label"]).astype(np.int64).reshape(-1)
+    if off.shape[0] != labs.shape[0] + 1 or off[0] != 0 or off[-1] != v.shape[0] or (np.diff(off) < 0).any():
+        raise ValueError(f"{what}: ring_offsets does not fit verts / ring_label")
+    if labs.size and (labs.min() <= 0 or labs.max() >= 2 ** 31 - 1):
+        raise ValueError(f"{what}: ring labels must be positive and below 2^31 - 1, got "
+                         f"{int(labs.min())} .. {int(labs.max())}")
+    return quantize_verts(v), off, labs
+
+
+def _first_centre(lo: np.ndarray) -> np.ndarray:
+    """The first pixel whose centre ``256 p + 128`` is at or beyond the lattice coordinate ``lo``."""
+    return -((RASTER_SUBPIX // 2 - lo) // RASTER_SUBPIX)
+
+
+def rasterize_rings(polys: dict, shape) -> np.ndarray:
+    """Label image int32 ``shape`` (H, W) of a polygons dict: the specification of
+    ``csrc/kernels/cellpose_raster.hip``, which the GPU tests compare with exactly.  (PIL's
+    ``ImageDraw.polygon`` truncates vertices to integers and is no yardstick; no other rasteriser is
+    installed.  The rule is this project's own.)
+
+    Polygons dict: the rings dict of :func:`mask_rings` with the vertex dtype freed -- ``verts``
+    [V, 2] (y, x) of any integer or float dtype in pixel-corner units (pixel ``(y, x)`` is the square
+    ``[y, y + 1) x [x, x + 1)``, its centre ``(y + 0.5, x + 0.5)``), ``ring_offsets`` int64 [R + 1],
+    ``ring_label`` int32 [R]; ``ring_area2`` is ignored.
+
+    The rule is in integers only.  Vertices are quantised by :func:`quantize_verts` to 1/256 pixel.
+    Pixel ``(y, x)`` has the centre ``C = (256 y + 128, 256 x + 128)``.  For a label, every directed
+    edge ``(Y0, X0) -> (Y1, X1)`` between consecutive vertices of each of its rings (the closing edge
+    included) *crosses* the pixel's row when ``(Y0 <= Cy) != (Y1 <= Cy)``, and a crossing edge
+    *counts* when its crossing lies at or left of the centre: ``(Cy - Y0)(X1 - X0) <= (Cx - X0)(Y1 -
+    Y0)`` if ``Y1 > Y0``, ``>=`` if ``Y1 < Y0``.  The pixel is inside the label when the number of
+    counting edges is odd: even-odd over all the rings of a label, so holes work whatever their
+    orientation, a self-intersecting ring follows even-odd, and two overlapping parts of one label
+    cancel where they overlap.  Horizontal and zero-length edges never cross and a ring of fewer
+    than three vertices cancels itself.  Ties are top-left: a centre on a left or top edge is
+    inside, one on a right or bottom edge outside, so polygons that share an edge never both claim a
+    pixel and never leave one out.  A pixel takes the largest label whose polygon contains its
+    centre.  Vertices may lie outside the image; the result is the part inside ``H x W``.
+
+    Raises ``ValueError`` when the offsets do not fit, a label is not positive or a coordinate is
+    not finite or out of range."""
+    H, W = int(shape[0]), int(shape[1])
+    q, off, labs = polygon_arrays(polys)
+    out = np.zeros((H, W), np.int32)
+    n = np.diff(off)
+    S = RASTER_SUBPIX
+    for lab in np.unique(labs).tolist():
+        rs = np.nonzero((labs == lab) & (n > 0))[0]
+        if rs.size == 0:
+            continue
+        a = np.concatenate([q[off[r]:off[r + 1]] for r in rs])
+        b = np.concatenate([np.roll(q[off[r]:off[r + 1]], -1, 0) for r in rs])
+        # rows and columns whose centre lies inside the vertex range: a row outside it is crossed by
+        # no edge, a column left of it has no crossing at or left of it, one right of it has all of
+        # them, an even number
+        y_lo, x_lo = np.maximum(_first_centre(a.min(0)), 0).tolist()
+        y_hi, x_hi = np.minimum(_first_centre(a.max(0)) - 1, (H - 1, W - 1)).tolist()
+        if y_lo > y_hi or x_lo > x_hi:
+            continue
+        cx = (np.arange(x_lo, x_hi + 1, dtype=np.int64) * S + S // 2)[None, :]
+        par = np.zeros((y_hi - y_lo + 1, x_hi - x_lo + 1), bool)
+        for (Y0, X0), (Y1, X1) in zip(a.tolist(), b.tolist()):
+            if Y0 == Y1:
+                continue
+            # rows with min(Y0, Y1) <= Cy < max(Y0, Y1): exactly those the edge crosses
+            r0 = max(int(_first_centre(np.int64(min(Y0, Y1)))), y_lo)
+            r1 = min(int(_first_centre(np.int64(max(Y0, Y1)))) - 1, y_hi)
+            if r0 > r1:
+                continue
+            cy = (np.arange(r0, r1 + 1, dtype=np.int64) * S + S // 2)[:, None]
+            lhs, rhs = (cy - Y0) * (X1 - X0), (cx - X0) * (Y1 - Y0)
+            par[r0 - y_lo:r1 - y_lo + 1] ^= (lhs <= rhs) if Y1 > Y0 else (lhs >= rhs)
+        sub = out[y_lo:y_hi + 1, x_lo:x_hi + 1]
+        sub[par] = np.maximum(sub[par], lab)
+    return out
+
+
+def _empty_polygons() -> dict:
+    return {"verts": np.zeros((0, 2), np.float64), "ring_offsets": np.zeros(1, np.int64),
+            "ring_label": np.zeros(0, np.int32)}
+
+
+def _geojson_ring(ring, where: str) -> np.ndarray:
+    try:
+        v = np.asarray([[float(p[1]), float(p[0])] for p in ring], np.float64).reshape(-1, 2)
+    except (TypeError, ValueError, IndexError, KeyError) as e:
+        raise ValueError(f"outlines_to_rings: {where}: positions must be [x, y] or [x, y, z] numbers") from e
+    if v.shape[0] > 1 and (v[0] == v[-1]).all():
+        v = v[:-1]
+    if v.shape[0] < 3:
+        raise ValueError(f"outlines_to_rings: {where}: a ring needs at least three vertices")
+    return v
+
+
+def _geojson_features(doc):
+    """The features of a GeoJSON document as (properties, geometry) pairs, or None when ``doc`` is
+    not GeoJSON."""
+    if isinstance(doc, dict):
+        t = doc.get("type")
+        if t == "FeatureCollection":
+            feats = doc.get("features")
+            if not isinstance(feats, (list, tuple)):
+                raise ValueError("outlines_to_rings: a FeatureCollection needs a list of features")
+            for i, f in enumerate(feats):
+                if not isinstance(f, dict) or f.get("type") != "Feature":
+                    raise ValueError(f"outlines_to_rings: feature {i} is not a GeoJSON Feature")
+            return [(f.get("properties") or {}, f.get("geometry")) for f in feats]
+        if t == "Feature":
+            return [(doc.get("properties") or {}, doc.get("geometry"))]
+        if isinstance(t, str):
+            return [({}, doc)]
+        return None
+    if isinstance(doc, (list, tuple)) and doc and all(isinstance(f, dict) and f.get("type") == "Feature" for f in doc):
+        return [(f.get("properties") or {}, f.get("geometry")) for f in doc]
+    return None
+
+
+def outlines_to_rings(doc) -> dict:
+    """One image's polygon annotation in any accepted form -> a polygons dict (see
+    :func:`rasterize_rings`).
+
+    * A polygons dict (``verts``, ``ring_offsets``, ``ring_label``): validated and returned.
+    * The app's ``"rings"`` form, a list of ``{label, rings: [[[x, y], ...], ...]}``: the inverse of
+      the app's ``outline_items``.
+    * GeoJSON: a ``FeatureCollection``, a list of ``Feature`` s, one ``Feature`` or a bare geometry.
+      ``Polygon`` and ``MultiPolygon`` only; any other geometry type, a ``null`` geometry and
+      ``GeometryCollection`` raise ``ValueError`` naming the feature's index.  Positions are
+      ``[x, y]`` or ``[x, y, z]`` (the third value is ignored); a ring's closing vertex, equal to its
+      first, is dropped, and a ring with fewer than three vertices after that is a ``ValueError``.
+      Labels are ``properties.label`` when every feature has it (a positive integer below 2^31 - 1;
+      the same label on several features means several parts of one label), the feature's position
+      + 1 when none has it; a mixture is a ``ValueError``.
+
+    ``verts`` comes back as float64 (y, x) for the two parsed forms."""
+    if isinstance(doc, dict) and "verts" in doc:
+        if "ring_offsets" not in doc or "ring_label" not in doc:
+            raise ValueError("outlines_to_rings: a polygons dict needs verts, ring_offsets and ring_label")
+        polygon_arrays(doc, "outlines_to_rings")
+        return doc
+    rings, labels = [], []
+    if isinstance(doc, (list, tuple)) and (not doc or all(isinstance(it, dict) and "rings" in it for it in doc)):
+        for i, it in enumerate(doc):
+            if "label" not in it:
+                raise ValueError(f"outlines_to_rings: item {i} has no label")
+            for ring in it["rings"]:
+                rings.append(_geojson_ring(ring, f"item {i}"))
+                labels.append(it["label"])
+    else:
+        feats = _geojson_features(doc)
+        if feats is None:
+            raise ValueError("outlines_to_rings expects a polygons dict, a list of {label, rings} or GeoJSON, got "
+                             f"{type(doc).__name__}")
+        has = [isinstance(p, dict) and p.get("label") is not None for p, _ in feats]
+        if any(has) and not all(has):
+            raise ValueError("outlines_to_rings: some features have properties.label and some do not")
+        for i, (props, geom) in enumerate(feats):
+            t = geom.get("type") if isinstance(geom, dict) else None
+            if t not in ("Polygon", "MultiPolygon"):
+                raise ValueError(f"outlines_to_rings: feature {i}: geometry {t!r} is not a Polygon or MultiPolygon")
+            coords = geom.get("coordinates")
+            if not isinstance(coords, (list, tuple)):
+                raise ValueError(f"outlines_to_rings: feature {i}: no coordinates")
+            for poly in ([coords] if t == "Polygon" else coords):
+                for ring in poly:
+                    rings.append(_geojson_ring(ring, f"feature {i}"))
+                    labels.append(props["label"] if has[i] else i + 1)
+    labs = []
+    for lab in labels:
+        if isinstance(lab, bool) or not isinstance(lab, (int, np.integer, float)) or lab != int(lab) \
+                or not 0 < int(lab) < 2 ** 31 - 1:
+            raise ValueError(f"outlines_to_rings: label {lab!r} is not a positive integer below 2^31 - 1")
+        labs.append(int(lab))
+    if not rings:
+        return _empty_polygons()
+    verts = np.concatenate(rings)
+    if not np.isfinite(verts).all():
+        raise ValueError("outlines_to_rings: a coordinate is not finite")
+    return {"verts": verts, "ring_offsets": np.concatenate([[0], np.cumsum([r.shape[0] for r in rings])]).astype(np.int64),
+            "ring_label": np.asarray(labs, np.int32)}
+
+
+def unwrap_outlines(doc):
+    """The annotation document of one image or plane: the app wraps a plane's ``"rings"`` outlines as
+    ``{z, outlines}``; everything else is returned as it is."""
+    if isinstance(doc, dict) and "outlines" in doc and "verts" not in doc and "type" not in doc:
+        return doc["outlines"]
+    return doc
+
+
+def is_outline_document(doc) -> bool:
+    """Whether ``doc`` looks like a polygon annotation of one image (any form
+    :func:`outlines_to_rings` accepts) and not like an array of labels."""
+    doc = unwrap_outlines(doc)
+    if isinstance(doc, dict):
+        return "verts" in doc or isinstance(doc.get("type"), str)
+    return isinstance(doc, (list, tuple)) and all(isinstance(it, dict) for it in doc)

@@ -96,7 +96,9 @@ def to_chw(img: np.ndarray, nchan: int) -> np.ndarray:
 
 
 def load_pairs(pairs: list[dict], nchan: int, enable_clahe: bool = False, device=None):
-    """Local (image, annotation) files -> lists of CHW float images and int32 label maps."""
+    """Local (image, annotation) files -> lists of CHW float images and int32 label maps.  A polygon
+    annotation (``.geojson`` / ``.json``) is rasterised at its image's shape, on ``device`` when that
+    is a GPU."""
     from ..cellpose.datasets import read_image, read_labels
 
     imgs, labs = [], []
@@ -110,7 +112,7 @@ def load_pairs(pairs: list[dict], nchan: int, enable_clahe: bool = False, device
                 g = g.to(device)
             im = clahe_u8(g, 3.0, (16, 16)).cpu().numpy()
         imgs.append(to_chw(im, nchan))
-        lab = read_labels(pr["annotation"])
+        lab = read_labels(pr["annotation"], shape=imgs[-1].shape[1:], device=device)
         if lab.shape != imgs[-1].shape[1:]:
             raise ValueError(f"annotation {pr['annotation']} shape {lab.shape} != image {imgs[-1].shape[1:]}")
         labs.append(lab)
