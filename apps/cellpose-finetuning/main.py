@@ -205,6 +205,25 @@ def outline_items(rings: dict, fmt: str, z: int | None = None):
     return out if z is None else {"z": int(z), "outlines": out}
 
 
+SURFACE_FORMATS = ("stats", "mesh", "obj")
+
+
+def surface_items(surf: dict, fmt: str, spacing, json_safe: bool):
+    """The ``surfaces`` entry of one z-stack of an ``infer`` result, from ``{"mesh", "stats"}`` of
+    :meth:`CellposeRunner.surfaces`.  ``"stats"``: the per-label table of
+    :func:`reference.surface_stats` (``area``, ``area_voxel``, ``volume``, ``mesh_volume``,
+    ``sphericity``, ...) as lists; ``"mesh"``: the arrays of :func:`reference.label_surface` (lists
+    when ``json_safe``); ``"obj"``: the Wavefront OBJ text of the surface-net mesh, one group per
+    label, scaled by ``spacing`` (sz, sy, sx)."""
+    from bioengine_worker_amd.cellpose import reference as ref
+
+    if fmt == "stats":
+        return {k: v.tolist() for k, v in surf["stats"].items()}
+    if fmt == "obj":
+        return ref.surface_to_obj(surf["mesh"], spacing=spacing)
+    return {k: (v.tolist() if json_safe else v) for k, v in surf["mesh"].items()}
+
+
 def _diameter_arg(diameter):
     """The ``diameter`` of a request: ``None``, a float, or the string ``"auto"``."""
     diameter = _opt(diameter)
@@ -583,6 +602,11 @@ class CellposeFinetune:
         outline_format: str = Field("rings", description="Form of the outlines: 'rings' (per label: rings of [x, y] "
                                                          "and their signed doubled areas) or 'geojson' (a "
                                                          "FeatureCollection of Polygon / MultiPolygon features)."),
+        return_surfaces: bool = Field(False, description="z-stacks: also return the surface of every 3-D label "
+                                                         "(surface area, sphericity, or the quad mesh itself)."),
+        surface_format: str = Field("stats", description="Form of the surfaces: 'stats' (per-label table: area, "
+                                                         "voxel-face area, volume, sphericity), 'mesh' (indexed "
+                                                         "quad mesh arrays) or 'obj' (Wavefront OBJ text)."),
     ) -> list:
         """Segment images; returns one {input_path, output(, flows)(, measurements, diameter_px)(, outlines)} per image.  With ``z_axis``,
         ``stitch_threshold > 0`` or ``do_3D`` every input array is one z-stack and ``output`` is
@@ -602,7 +626,11 @@ class CellposeFinetune:
         ``return_outlines``: ``outlines`` holds the cells' outlines in ``outline_format`` (see
         :func:`outline_items`), the same with and without ``json_safe``; for a z-stack a list with one
         entry per plane, ``z`` recorded.  Like ``return_measurements`` it is not in the batching key:
-        a batch traces if any of its requests asks and only those get the field."""
+        a batch traces if any of its requests asks and only those get the field.
+        ``return_surfaces`` (stack modes only: ``z_axis``, ``stitch_threshold > 0`` or ``do_3D``):
+        ``surfaces`` holds the surfaces of the stack's 3-D labels in ``surface_format`` (see
+        :func:`surface_items`), with voxel size ``(anisotropy or 1, 1, 1)``; faces on the border of the
+        volume count as surface.  It is not in the batching key either."""
         if isinstance(artifact, dict):
             w = artifact
             artifact = w.get("artifact", w.get("artifact_id", w.get("id")))
@@ -618,11 +646,17 @@ class CellposeFinetune:
             augment, normalize = w.get("augment", augment), w.get("normalize", normalize)
             return_outlines = w.get("return_outlines", return_outlines)
             outline_format = w.get("outline_format", outline_format)
+            return_surfaces = w.get("return_surfaces", return_surfaces)
+            surface_format = w.get("surface_format", surface_format)
         return_measurements = bool(_opt(return_measurements) or False)
         return_outlines = bool(_opt(return_outlines) or False)
         outline_format = _opt(outline_format) or "rings"
         if outline_format not in OUTLINE_FORMATS:
             raise ValueError(f"outline_format must be one of {OUTLINE_FORMATS}, got {outline_format!r}")
+        return_surfaces = bool(_opt(return_surfaces) or False)
+        surface_format = _opt(surface_format) or "stats"
+        if surface_format not in SURFACE_FORMATS:
+            raise ValueError(f"surface_format must be one of {SURFACE_FORMATS}, got {surface_format!r}")
         stitch_threshold = float(_opt(stitch_threshold) or 0.0)
         z_axis = _opt(z_axis)
         if not 0.0 <= stitch_threshold <= 1.0:
@@ -646,6 +680,9 @@ class CellposeFinetune:
         else:
             raise ValueError("Provide input_arrays or artifact + image_paths")
         stack_mode = z_axis is not None or stitch_threshold > 0 or do_3D
+        if return_surfaces and not stack_mode:
+            raise ValueError("return_surfaces needs a z-stack (z_axis / stitch_threshold / do_3D): a plane has "
+                             "outlines (return_outlines), not surfaces")
         diameter = _diameter_arg(diameter)
         if diameter == "auto" and stack_mode:
             raise ValueError("diameter='auto' is not supported for z-stacks (z_axis / stitch_threshold / do_3D): "
@@ -661,7 +698,8 @@ class CellposeFinetune:
         if stack_mode:
             out = await self._infer_stacks(runner, names, images, prm, stitch_threshold, int(z_axis or 0),
                                            bool(return_flows), bool(json_safe), do_3D, anisotropy, return_measurements,
-                                           outline_format if return_outlines else None)
+                                           outline_format if return_outlines else None,
+                                           surface_format if return_surfaces else None)
             if self._weights.get(model_id) == "random" and out:
                 out[0]["weights"] = "random"
             return out
@@ -694,12 +732,15 @@ class CellposeFinetune:
     async def _infer_stacks(self, runner, names: list, stacks: list, prm: dict, stitch_threshold: float, z_axis: int,
                             return_flows: bool, json_safe: bool, do_3D: bool = False,
                             anisotropy: float | None = None, return_measurements: bool = False,
-                            outline_format: str | None = None) -> list:
+                            outline_format: str | None = None, surface_format: str | None = None) -> list:
         """Stack mode of :meth:`infer`: every array is one z-stack ([Z,H,W], [Z,C,H,W] or [Z,H,W,C] once
         ``z_axis`` is moved to the front); its planes are one batch of ``runner.eval_stack`` (no
         continuous batching across requests), stitched on the device.  ``do_3D`` routes the stack to
-        ``runner.eval_3d`` instead (orthogonal views, 3-D dynamics; ``flow_threshold`` is unused)."""
+        ``runner.eval_3d`` instead (orthogonal views, 3-D dynamics; ``flow_threshold`` is unused).
+        ``surface_format`` (None: not asked for): the labels' surfaces, meshed on the device from the
+        final volume with voxel size ``(anisotropy or 1, 1, 1)``."""
         out = []
+        spacing = (float(anisotropy or 1.0), 1.0, 1.0)
         for name, a in zip(names, stacks):
             a = np.asarray(a)
             if a.ndim < 3:
@@ -721,17 +762,20 @@ class CellposeFinetune:
                     tab = runner.measure(m, a, volume=True) if return_measurements else None
                     # per plane, with the volume's labels (None: outlines were not asked for)
                     rings = runner.outlines(m, volume=True) if outline_format else None
+                    surf = runner.surfaces(m, spacing=spacing) if surface_format else None
                     m = m.cpu().numpy()
-                    return m, (f.cpu().numpy() if return_flows else None), tab, rings
+                    return m, (f.cpu().numpy() if return_flows else None), tab, rings, surf
 
             with trace.span("app.stack_eval", planes=int(a.shape[0])):
-                m, f, tab, rings = await offload(run)
+                m, f, tab, rings, surf = await offload(run)
             m = m.astype(np.uint16) if int(m.max(initial=0)) < 65536 else m.astype(np.int32)
             item = {"input_path": name, "output": [mask_png_payload(pl) for pl in m] if json_safe else m}
             if return_measurements:
                 item.update(measurement_items(tab, json_safe))
             if rings is not None:
                 item["outlines"] = [outline_items(r, outline_format, z) for z, r in enumerate(rings)]
+            if surf is not None:
+                item["surfaces"] = surface_items(surf, surface_format, spacing, json_safe)
             if return_flows:
                 if do_3D:  # f [4, Z', H, W] (dZ, dY, dX, cellprob)
                     fl = [np.stack([flow_rgb(f[1:3, z]) for z in range(f.shape[1])]), f[:3], f[3]]

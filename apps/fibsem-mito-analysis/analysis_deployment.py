@@ -232,9 +232,22 @@ class MitoAnalysisDeployment:
                              model_id_3d: str = Field("mito-unet3d", description="3-D model for inference='tiled3d'."),
                              tile_z: int = Field(32, description="3-D tile depth."),
                              overlap_z: int = Field(8, description="3-D tile z-overlap."),
+                             surface_stats: bool = Field(False, description="Also report every kept instance's "
+                                                                            "surface area (smoothed mesh and voxel "
+                                                                            "faces, nm^2) and sphericity (n_gpus = 1)."),
+                             z_size_nm: float | None = Field(None, description="Slice spacing in nm (default: "
+                                                                               "pixel_size_nm)."),
+                             return_mesh: bool = Field(False, description="Include the kept instances' surface mesh "
+                                                                          "as Wavefront OBJ text, in nm (n_gpus = 1)."),
                              ) -> dict:
         """3-D mitochondria instances with per-instance volume.  With ``n_gpus > 1`` the z-slabs run
-        as one rank per GPU (each reads only its slab) with globally consistent labels."""
+        as one rank per GPU (each reads only its slab) with globally consistent labels.
+        ``surface_stats`` adds ``surface_area_nm2`` (the surface-net mesh of the instance),
+        ``surface_area_voxel_nm2`` (its voxel faces) and ``sphericity`` to ``instances`` and
+        ``return_mesh`` adds ``mesh_obj``; the voxel size is (``z_size_nm``, ``pixel_size_nm``,
+        ``pixel_size_nm``).  Faces on the border of the volume count as surface: an instance cut by
+        the border is closed there.  Both need ``n_gpus = 1``: surfaces across slab seams are not
+        stitched."""
         import shutil
         import tempfile
 
@@ -244,6 +257,12 @@ class MitoAnalysisDeployment:
 
         if inference not in ("slice2d", "tiled3d"):
             raise ValueError("inference must be 'slice2d' or 'tiled3d'")
+        surface_stats, return_mesh = bool(surface_stats), bool(return_mesh)
+        if (surface_stats or return_mesh) and int(n_gpus or 1) > 1:
+            raise ValueError("surface_stats / return_mesh need n_gpus = 1: surfaces across GPU slab seams are not stitched")
+        spacing_nm = (float(pixel_size_nm if z_size_nm is None else z_size_nm), float(pixel_size_nm), float(pixel_size_nm))
+        if (surface_stats or return_mesh) and not all(np.isfinite(v) and v > 0 for v in spacing_nm):
+            raise ValueError(f"pixel_size_nm and z_size_nm must be positive and finite, got {spacing_nm[1]} and {spacing_nm[0]}")
         if self._pipe is None and not input_is_probability:
             raise RuntimeError("volume analysis needs the in-process pipeline (no model_runner_service)")
         work = Path(tempfile.mkdtemp(prefix="em-vol-", dir=os.environ.get("TMPDIR")))
@@ -289,7 +308,8 @@ class MitoAnalysisDeployment:
                                            min_voxels=int(min_voxels), norm_range=(float(p1), float(p99)),
                                            split_touching=bool(split_touching), closing_radius=int(closing_radius),
                                            min_distance=int(min_distance), predict3d=predict3d, tile_z=int(tile_z),
-                                           overlap_z=int(overlap_z))
+                                           overlap_z=int(overlap_z), surface_stats=surface_stats,
+                                           spacing_nm=spacing_nm, return_mesh=return_mesh)
                     labels = r.pop("labels_slab_t")
                     if return_labels:
                         b = io.BytesIO()

@@ -1,6 +1,6 @@
 """GPU (HIP) implementation of Cellpose pre/post-processing on batches of images.
 
-Every heavy step is a kernel in ``csrc/kernels/{tiles,cellpose_dynamics,cellpose_dynamics3d,cellpose_masks,cellpose_stitch,cellpose_measure,cellpose_ap,cellpose_rings,cellpose_raster}.hip``;
+Every heavy step is a kernel in ``csrc/kernels/{tiles,cellpose_dynamics,cellpose_dynamics3d,cellpose_masks,cellpose_stitch,cellpose_measure,cellpose_ap,cellpose_rings,cellpose_raster,label_surface}.hip``;
 torch is only used for tiny bookkeeping (sorting the seed keys, prefix sums over labels, building
 per-mask job lists).  The semantics are those of :mod:`bioengine_worker_amd.cellpose.reference`
 (the CPU oracle), which the GPU tests compare against.
@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import collections
 import ctypes
+import math
 import os
 
 import numpy as np
@@ -1518,6 +1519,145 @@ def mask_rings_gpu(M: torch.Tensor, nlab: int | None = None, volume: bool = Fals
         raise RuntimeError(f"be_cp_rings_trace: a walk left its counted bounds (error word {e}): the labels changed "
                            "while they were traced")
     return _rings_result(verts, off[:R + 1], o32[:R], area2[:R], o32[cap:cap + R], per_image)
+
+
+# ------------------------------------------------------------------ label surfaces: quad meshes of a volume
+
+SURF_TILE = 256  # corners per workgroup: TILE of label_surface.hip
+SURF_SLICES = 8  # workgroups per label of its statistics kernels: SL
+
+_SURF_KEYS = ("corner", "verts", "vert_label", "quads", "quad_label", "label_verts", "label_quads", "faces", "voxels")
+
+
+def _check_surface(Z: int, H: int, W: int) -> None:
+    """Corner coordinates stay inside 16 bits and the corner lattice is indexed in 32 bits."""
+    if max(Z, H, W) > 2 ** 15:
+        raise ValueError(f"label_surface_gpu: volume {Z} x {H} x {W} is too large (no axis may exceed 2^15)")
+    if (Z + 1) * (H + 1) * (W + 1) >= 2 ** 31:
+        raise ValueError(f"label_surface_gpu: volume {Z} x {H} x {W} is too large ((Z+1)(H+1)(W+1) must be below 2^31)")
+
+
+def _surface_empty(K: int, dev) -> dict:
+    return {k: torch.from_numpy(v).to(dev) for k, v in ref._empty_surface(K).items()}
+
+
+def label_surface_gpu(L: torch.Tensor, nlab: int | None = None) -> dict:
+    """The surface of every label of a volume as an indexed quad mesh, built on the device: HIP
+    implementation of :func:`reference.label_surface` (``csrc/kernels/label_surface.hip``), equal to it
+    in every array and bit-identical from run to run.
+
+    ``L`` [Z, H, W] integer labels (any integer dtype, any strides).  Returns the oracle's dict as
+    device tensors: ``corner`` int32 [V, 3], ``verts`` float32 [V, 3], ``vert_label`` int32 [V],
+    ``quads`` int32 [F, 4], ``quad_label`` int32 [F], ``label_verts`` / ``label_quads`` int64 [K + 1],
+    ``faces`` int64 [K, 3], ``voxels`` int64 [K].  ``nlab``: an upper bound on the labels + 1 (saves the
+    ``L.max()`` sync; labels above it are not meshed but still bound their neighbours).  The kernels
+    read int32: labels of a wider dtype are clamped to [-1, 2^31 - 1] first, which changes no result
+    (values outside ``1..K`` only bound their neighbours), and ``K`` must stay below 2^31 - 1
+    (``ValueError``).
+
+    A corner pass counts vertices and quads per tile of 256 corners, a prefix sum over the tiles gives
+    every tile its offset, a second pass writes the (corner, label) keys at offset + rank, a stable
+    sort of the label keys regroups them by label, and gather passes write the mesh, the label
+    offsets, the face counts and the voxel counts.  The host reads ``V`` and ``F`` after the count
+    (``V`` or ``F`` >= 2^31 raises ``RuntimeError`` before any allocation) and the error word at the
+    end: ``RuntimeError`` when the second pass did not find what the first counted (labels that
+    changed under the kernel).  An empty volume or ``K = 0`` returns empty arrays with no launch and
+    no read.  Runs on the current stream.  CPU tensors run the oracle."""
+    if L.dim() != 3:
+        raise ValueError(f"label_surface_gpu expects a [Z, H, W] label volume, got {tuple(L.shape)}")
+    if L.dtype.is_floating_point or L.dtype.is_complex:
+        raise ValueError(f"label_surface_gpu expects integer labels, got {L.dtype}")
+    Z, H, W = L.shape
+    _check_surface(Z, H, W)
+    if nlab is not None and int(nlab) - 1 >= 2 ** 31 - 1:
+        raise ValueError(f"label_surface_gpu: nlab {nlab} is too large (labels to mesh must stay below 2^31 - 1)")
+    dev = L.device
+    if L.numel() == 0 or (nlab is not None and int(nlab) <= 1):
+        return _surface_empty(max(int(nlab or 1) - 1, 0), dev)
+    if dev.type != "cuda":
+        return {k: torch.from_numpy(v) for k, v in ref.label_surface(L.numpy(), nlab).items()}
+    if L.dtype in (torch.int64, torch.uint32, torch.uint64):
+        # a plain conversion would wrap 2^32 + 1 into label 1; every value outside 1..K is equivalent
+        L = L.to(torch.int64).clamp_(-1, 2 ** 31 - 1)
+    Lc = L.to(torch.int32).contiguous()
+    if nlab is None:
+        nlab = int(Lc.max().item()) + 1
+        if nlab - 1 >= 2 ** 31 - 1:
+            raise ValueError("label_surface_gpu: labels to mesh must stay below 2^31 - 1")
+    K = max(int(nlab) - 1, 0)
+    if K == 0:
+        return _surface_empty(0, dev)
+    sp = _native.stream(dev)
+    ptr = _native.ptr
+    nt = -(-(Z + 1) * (H + 1) * (W + 1) // SURF_TILE)
+    tile_cnt = torch.empty(2, nt, dtype=torch.int32, device=dev)
+    _native.call("be_surf_count", ptr(Lc), Z, H, W, K, ptr(tile_cnt), sp)
+    tile_inc = torch.cumsum(tile_cnt, 1, dtype=torch.int64)  # along the contiguous axis
+    V, F = _host_ints(tile_inc[:, -1])
+    if V >= 2 ** 31 or F >= 2 ** 31:
+        raise RuntimeError(f"label_surface_gpu: {V} vertices and {F} quads do not fit 32-bit indices")
+    if V == 0 or F == 0:
+        return _surface_empty(K, dev)
+    k32 = torch.empty(2 * V + 2 * F, dtype=torch.int32, device=dev)
+    vcorner, vlabel, qcorner, qlabel = k32.split([V, V, F, F])
+    qside = torch.empty(F, dtype=torch.uint8, device=dev)
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    _native.call("be_surf_emit", ptr(Lc), Z, H, W, K, ptr(tile_inc), V, F, ptr(vcorner), ptr(vlabel), ptr(qcorner),
+                 ptr(qside), ptr(qlabel), ptr(err), sp)
+    vlab, vperm = torch.sort(vlabel, stable=True)
+    qlab, qperm = torch.sort(qlabel, stable=True)
+    o64 = torch.empty(2 * (K + 1), dtype=torch.int64, device=dev)
+    label_verts, label_quads = o64[:K + 1], o64[K + 1:]
+    corner = torch.empty(V, 3, dtype=torch.int32, device=dev)
+    verts = torch.empty(V, 3, dtype=torch.float32, device=dev)
+    vkey = torch.empty(V, dtype=torch.int32, device=dev)
+    quads = torch.empty(F, 4, dtype=torch.int32, device=dev)
+    _native.call("be_surf_gather", ptr(Lc), Z, H, W, K, V, F, ptr(vperm), ptr(vcorner), ptr(vlab), ptr(qlab),
+                 ptr(label_verts), ptr(label_quads), ptr(corner), ptr(verts), ptr(vkey), ptr(err), sp)
+    _native.call("be_surf_remap", Z, H, W, K, V, F, ptr(qperm), ptr(qcorner), ptr(qside), ptr(qlab), ptr(label_verts),
+                 ptr(vkey), ptr(quads), ptr(err), sp)
+    counts = torch.zeros(4 * K, dtype=torch.int64, device=dev)
+    faces, voxels = counts[:3 * K].view(K, 3), counts[3 * K:]
+    _native.call("be_surf_faces", Z, H, W, K, F, ptr(qperm), ptr(qcorner), ptr(qside), ptr(label_quads), ptr(faces),
+                 ptr(voxels), sp)
+    e, = _host_ints(err)
+    if e:
+        raise RuntimeError(f"label_surface_gpu: the second pass did not find what the first counted (error word {e}): "
+                           "the labels changed while they were meshed")
+    return {"corner": corner, "verts": verts, "vert_label": vlab, "quads": quads, "quad_label": qlab,
+            "label_verts": label_verts, "label_quads": label_quads, "faces": faces, "voxels": voxels}
+
+
+def surface_stats_gpu(surf: dict, spacing=(1.0, 1.0, 1.0)) -> dict:
+    """Per-label surface measurements of a :func:`label_surface_gpu` mesh: the table of
+    :func:`reference.surface_stats` (``label``, ``area_voxel``, ``area``, ``mesh_volume``, ``volume``,
+    ``sphericity``, ``n_verts``, ``n_quads``; float64 tensors [K]) on the mesh's device.  ``area`` and
+    ``mesh_volume`` are summed by ``be_surf_stats`` in fp64 over fixed chunks of every label's quads,
+    combined in chunk order (no float atomics: bit-identical from run to run).  Nothing is read back.
+    CPU tensors (or arrays) run the oracle."""
+    sz, sy, sx = ref._check_spacing(spacing, "surface_stats_gpu")
+    faces = surf["faces"]
+    if not torch.is_tensor(faces) or faces.device.type != "cuda":
+        host = {k: (v.numpy() if torch.is_tensor(v) else np.asarray(v)) for k, v in surf.items()}
+        return {k: torch.from_numpy(v) for k, v in ref.surface_stats(host, (sz, sy, sx)).items()}
+    dev = faces.device
+    K = faces.shape[0]
+    V, F = surf["verts"].shape[0], surf["quads"].shape[0]
+    out = torch.zeros(K, 2, dtype=torch.float64, device=dev)
+    if K and V and F:
+        part = torch.empty(K, SURF_SLICES, 2, dtype=torch.float64, device=dev)
+        _native.call("be_surf_stats", K, V, F, _native.ptr(surf["verts"].contiguous()),
+                     _native.ptr(surf["quads"].contiguous()), _native.ptr(surf["label_quads"].contiguous()), sz, sy, sx,
+                     _native.ptr(part), _native.ptr(out), _native.stream(dev))
+    f = faces.double()
+    area = out[:, 0]
+    volume = surf["voxels"].double() * (sz * sy * sx)
+    sph = torch.where(area > 0, math.pi ** (1.0 / 3.0) * (6.0 * volume) ** (2.0 / 3.0) / area,
+                      torch.full_like(area, float("nan")))
+    return {"label": torch.arange(1, K + 1, dtype=torch.float64, device=dev),
+            "area_voxel": f[:, 0] * sy * sx + f[:, 1] * sz * sx + f[:, 2] * sz * sy,
+            "area": area, "mesh_volume": out[:, 1], "volume": volume, "sphericity": sph,
+            "n_verts": surf["label_verts"].diff().double(), "n_quads": surf["label_quads"].diff().double()}
 
 
 # ------------------------------------------------------------------ polygons -> labels

@@ -1060,6 +1060,29 @@ class CellposeRunner:
             nlab = getattr(masks, "label_bound", None)
         return outline_rings(outline_launch(m, nlab=nlab, volume=volume))
 
+    # ---------------------------------------------------------------- surfaces
+    def surfaces(self, masks, spacing=(1.0, 1.0, 1.0), nlab: int | None = None) -> dict:
+        """The surface of every label of a volume (:func:`reference.label_surface`): an indexed quad
+        mesh with two vertex placements and per-label surface statistics.
+
+        ``masks``: one [Z, H, W] label volume, as :meth:`eval_stack` / :meth:`eval_3d` return it.
+        ``spacing``: the voxel size (sz, sy, sx), three positive finite numbers.  Returns ``{"mesh":
+        the mesh dict as numpy arrays (``corner``, ``verts``, ``vert_label``, ``quads``, ``quad_label``,
+        ``label_verts``, ``label_quads``, ``faces``, ``voxels``), "stats": the table of
+        :func:`reference.surface_stats` (``area``, ``area_voxel``, ``mesh_volume``, ``volume``,
+        ``sphericity``, ...; one float64 row per label)}``; :func:`reference.surface_to_obj` turns the
+        mesh into OBJ text.  Faces on the volume's border count as surface.  ``nlab``: an upper bound
+        on the labels + 1; by default the ``label_bound`` the mask stage left on ``masks``, else
+        ``masks.max() + 1``.  A volume on the GPU is meshed by the HIP kernels
+        (:func:`gpu.label_surface_gpu`, :func:`gpu.surface_stats_gpu`), everything else by the oracle."""
+        sp = ref._check_spacing(spacing, "surfaces")
+        m = masks if torch.is_tensor(masks) else torch.as_tensor(np.asarray(masks))
+        if m.dim() != 3:
+            raise ValueError(f"surfaces expects one [Z, H, W] label volume, got shape {tuple(m.shape)}")
+        if nlab is None:
+            nlab = getattr(masks, "label_bound", None)
+        return surface_tables(surface_launch(m, sp, nlab=nlab))
+
     # ---------------------------------------------------------------- polygon annotations
     def labels_from_outlines(self, outlines, shape, device=None) -> torch.Tensor:
         """Label images of polygon annotations (:func:`reference.rasterize_rings`): the way back from
@@ -1204,6 +1227,23 @@ def measure_tables(raws: dict, volume: bool = False):
         kb = int(present[-1]) + 1 if present.size else 0
         tables.append(ref.derive_measurements({k: (v[b] if k == "outlines" else v[b, :kb]) for k, v in host.items()}))
     return tables[0] if volume else tables
+
+
+def surface_launch(m: torch.Tensor, spacing=(1.0, 1.0, 1.0), nlab: int | None = None) -> dict:
+    """Surface mesh and statistics of one [Z, H, W] label volume on its device, as ``{"mesh",
+    "stats"}`` of tensors: the HIP kernels on the GPU (on the current stream, which is waited for
+    when the vertex and quad counts and, at the end, the error word are read), the numpy oracle
+    elsewhere."""
+    from .gpu import label_surface_gpu, surface_stats_gpu
+
+    mesh = label_surface_gpu(m, nlab=nlab)
+    return {"mesh": mesh, "stats": surface_stats_gpu(mesh, spacing)}
+
+
+def surface_tables(raws: dict) -> dict:
+    """Host side of :meth:`CellposeRunner.surfaces`: the tensors of :func:`surface_launch` as numpy."""
+    return {part: {k: (v.cpu().numpy() if torch.is_tensor(v) else np.asarray(v)) for k, v in d.items()}
+            for part, d in raws.items()}
 
 
 def outline_launch(m: torch.Tensor, nlab: int | None = None, volume: bool = False) -> dict:

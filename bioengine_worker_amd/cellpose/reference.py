@@ -1305,3 +1305,224 @@ def is_outline_document(doc) -> bool:
     if isinstance(doc, dict):
         return "verts" in doc or isinstance(doc.get("type"), str)
     return isinstance(doc, (list, tuple)) and all(isinstance(it, dict) for it in doc)
+
+
+# ------------------------------------------------------------------ label surfaces: quad meshes of a volume
+
+# corner offsets (in the next two axes b, c of the cycle z -> y -> x -> z) of a quad on the high
+# (s = 1) and the low (s = 0) side of its voxel: outward winding, see :func:`label_surface`
+_QUAD_BC = {1: ((0, 0), (1, 0), (1, 1), (0, 1)), 0: ((0, 0), (0, 1), (1, 1), (1, 0))}
+
+
+def _surface_result(corner, verts, vlab, quads, qlab, lverts, lquads, faces, voxels) -> dict:
+    return {"corner": corner, "verts": verts, "vert_label": vlab, "quads": quads, "quad_label": qlab,
+            "label_verts": lverts, "label_quads": lquads, "faces": faces, "voxels": voxels}
+
+
+def _empty_surface(K: int) -> dict:
+    return _surface_result(np.zeros((0, 3), np.int32), np.zeros((0, 3), np.float32), np.zeros(0, np.int32),
+                           np.zeros((0, 4), np.int32), np.zeros(0, np.int32), np.zeros(K + 1, np.int64),
+                           np.zeros(K + 1, np.int64), np.zeros((K, 3), np.int64), np.zeros(K, np.int64))
+
+
+def surface_net_offsets(inside: np.ndarray):
+    """Naive surface nets at lattice corners.  ``inside`` bool [V, 8]: whether each of the 8 voxels
+    around the corner (index ``4 dz + 2 dy + dx``, ``d = 0`` the voxel below the corner along that
+    axis) carries the vertex's label.  Returns ``nsum`` int32 [V, 3], the per-axis sum over the
+    crossing edges of the 2 x 2 x 2 block of voxel centres of the edge midpoint's offset from the
+    corner in half-voxel units, and ``ncross`` int32 [V], the number of crossing edges."""
+    ins = np.asarray(inside, bool).reshape(-1, 2, 2, 2)
+    nsum = np.zeros((ins.shape[0], 3), np.int32)
+    ncross = np.zeros(ins.shape[0], np.int32)
+    for a in range(3):
+        lo, hi = np.take(ins, 0, axis=1 + a), np.take(ins, 1, axis=1 + a)  # [V, 2, 2] over the other two axes
+        cross = lo != hi
+        ncross += cross.reshape(-1, 4).sum(1).astype(np.int32)
+        others = [ax for ax in range(3) if ax != a]
+        for j, ax in enumerate(others):
+            sign = np.array([-1, 1], np.int32).reshape((1, 2, 1) if j == 0 else (1, 1, 2))
+            nsum[:, ax] += (cross * sign).reshape(-1, 4).sum(1).astype(np.int32)
+    return nsum, ncross
+
+
+def label_surface(L, nlab: int | None = None) -> dict:
+    """The surface of every label of a volume as an indexed quad mesh (numpy only; the oracle of
+    :func:`gpu.label_surface_gpu`, which is compared with it exactly).
+
+    ``L`` [Z, H, W] integer labels; everything outside the array counts as 0.  ``K = nlab - 1``
+    (default ``L.max()``): labels outside ``1..K`` are never meshed but still bound their neighbours.
+    Coordinates are ``(z, y, x)`` on the corner lattice ``[0..Z] x [0..H] x [0..W]``; voxel
+    ``(z, y, x)`` spans the corners ``(z, y, x)..(z + 1, y + 1, x + 1)``.
+
+    Quads.  A voxel of label ``l`` owns one quad per side whose 6-neighbour is outside the array or
+    carries another value (two touching labels each get a quad on the shared face, with opposite
+    winding).  A side is (axis ``a``: 0 = z, 1 = y, 2 = x; ``s``: 0 = low, 1 = high); with ``(b, c)``
+    the next two axes in the cycle z -> y -> x -> z the quad lies in the plane ``a = v_a + s`` with
+    corners at the ``(b, c)`` offsets (0,0),(1,0),(1,1),(0,1) for ``s = 1`` and (0,0),(0,1),(1,1),(1,0)
+    for ``s = 0``.  With this winding the sum of ``det(p0,p1,p2) + det(p0,p2,p3)`` over a label's quads
+    is ``+6 x`` its voxel count and the directed edges of a label cancel in pairs.  Quads are ordered
+    by (label, voxel raster index, ``2a + s``).
+
+    Vertices.  One per (label ``l``, corner) where ``l`` holds between 1 and 7 of the 8 voxels around
+    the corner, ordered by (label, corner raster index over ``(Z+1, H+1, W+1)``).  Two voxels of one
+    label that meet only at an edge or corner share the vertex there (non-manifold by design).
+
+    Returns ``corner`` int32 [V, 3] (the lattice corner: this mesh is the voxel set exactly),
+    ``verts`` float32 [V, 3] (naive surface nets: ``float32(float64(corner) + float64(nsum) /
+    float64(2 ncross))``, see :func:`surface_net_offsets`), ``vert_label`` int32 [V], ``quads`` int32
+    [F, 4], ``quad_label`` int32 [F], ``label_verts`` / ``label_quads`` int64 [K + 1] (label ``l`` owns
+    ``[l - 1]:[l]``), ``faces`` int64 [K, 3] (quads per axis z, y, x) and ``voxels`` int64 [K], computed
+    from the mesh as the sum over the x-axis quads of +-(x of the quad's plane), + for ``s = 1``."""
+    L = np.asarray(L)
+    if L.ndim != 3:
+        raise ValueError(f"label_surface expects a [Z, H, W] label volume, got shape {L.shape}")
+    if L.dtype.kind not in "iub":
+        raise ValueError(f"label_surface expects integer labels, got dtype {L.dtype}")
+    Z, H, W = L.shape
+    if nlab is None:
+        nlab = int(L.max(initial=0)) + 1
+    K = max(int(nlab) - 1, 0)
+    if L.size == 0 or K == 0:
+        return _empty_surface(K)
+    dt = np.int64 if L.dtype.itemsize > 4 or L.dtype == np.uint32 else np.int32
+    P = np.zeros((Z + 2, H + 2, W + 2), dt)
+    P[1:-1, 1:-1, 1:-1] = L
+    C = P[1:-1, 1:-1, 1:-1]
+    valid = (C >= 1) & (C <= K)
+    shape = (Z, H, W)
+    NC = (Z + 1) * (H + 1) * (W + 1)
+
+    # quads: (label, voxel, side)
+    parts = []
+    for a in range(3):
+        for s in range(2):
+            sl = [slice(1, -1)] * 3
+            sl[a] = slice(2, None) if s else slice(0, -2)
+            vox = np.flatnonzero(valid & (P[tuple(sl)] != C))
+            parts.append((vox, np.full(vox.shape[0], 2 * a + s, np.int64)))
+    qvox = np.concatenate([p[0] for p in parts])
+    qside = np.concatenate([p[1] for p in parts])
+    qlab = C.reshape(-1)[qvox].astype(np.int64)
+    order = np.lexsort((qside, qvox, qlab))
+    qvox, qside, qlab = qvox[order], qside[order], qlab[order]
+
+    # vertices: (label, corner) at the corners whose 8 voxels are not all equal
+    views = [P[dz:dz + Z + 1, dy:dy + H + 1, dx:dx + W + 1] for dz in range(2) for dy in range(2) for dx in range(2)]
+    mixed = np.zeros((Z + 1, H + 1, W + 1), bool)
+    for v in views[1:]:
+        mixed |= v != views[0]
+    cidx = np.flatnonzero(mixed)
+    around = np.stack([v[mixed] for v in views], 1).astype(np.int64)  # [n, 8]
+    ok = (around >= 1) & (around <= K)
+    keys = np.unique((around * NC + cidx[:, None])[ok])
+    vlab, vcorner = keys // NC, keys % NC
+    row = np.searchsorted(cidx, vcorner)
+    inside = around[row] == vlab[:, None]
+    nsum, ncross = surface_net_offsets(inside)
+    corner = np.stack(np.unravel_index(vcorner, (Z + 1, H + 1, W + 1)), 1).astype(np.int32)
+    verts = (corner.astype(np.float64) + nsum.astype(np.float64) / (2 * ncross).astype(np.float64)[:, None]).astype(np.float32)
+
+    # quad corners -> vertex indices
+    vz, vy, vx = np.unravel_index(qvox, shape)
+    base = np.stack([vz, vy, vx], 1).astype(np.int64)
+    qa, qs = qside // 2, qside % 2
+    quads = np.zeros((qvox.shape[0], 4), np.int64)
+    strides = np.array([(H + 1) * (W + 1), W + 1, 1], np.int64)
+    for a in range(3):
+        b, c = (a + 1) % 3, (a + 2) % 3
+        for s in range(2):
+            sel = np.flatnonzero((qa == a) & (qs == s))
+            for k, (ob, oc) in enumerate(_QUAD_BC[s]):
+                p = base[sel].copy()
+                p[:, a] += s
+                p[:, b] += ob
+                p[:, c] += oc
+                key = qlab[sel] * NC + p @ strides
+                idx = np.searchsorted(keys, key)
+                if not np.array_equal(keys[np.minimum(idx, keys.shape[0] - 1)], key):
+                    raise AssertionError("label_surface: a quad corner has no vertex")
+                quads[sel, k] = idx
+    lbl = np.arange(1, K + 2)
+    lverts = np.concatenate([[0], np.searchsorted(vlab, lbl[:-1], side="right")]).astype(np.int64)
+    lquads = np.concatenate([[0], np.searchsorted(qlab, lbl[:-1], side="right")]).astype(np.int64)
+    faces = np.bincount((qlab - 1) * 3 + qa, minlength=3 * K).reshape(K, 3).astype(np.int64)
+    xs = qa == 2
+    plane = base[xs, 2] + qs[xs]
+    voxels = np.zeros(K, np.int64)
+    np.add.at(voxels, qlab[xs] - 1, np.where(qs[xs] == 1, plane, -plane))
+    return _surface_result(corner, verts, vlab.astype(np.int32), quads.astype(np.int32), qlab.astype(np.int32), lverts,
+                           lquads, faces, voxels)
+
+
+def _check_spacing(spacing, what: str):
+    try:
+        sp = tuple(float(v) for v in spacing)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: spacing must be three positive finite numbers, got {spacing!r}") from None
+    if len(sp) != 3 or not all(np.isfinite(v) and v > 0 for v in sp):
+        raise ValueError(f"{what}: spacing must be three positive finite numbers, got {spacing!r}")
+    return sp
+
+
+def _quad_triangles(pts: np.ndarray, quads: np.ndarray):
+    p = pts[quads]  # [F, 4, 3]
+    return p[:, 0], p[:, 1], p[:, 2], p[:, 3]
+
+
+def _segment_sums(values: np.ndarray, offsets: np.ndarray) -> np.ndarray:
+    return np.array([values[a:b].sum(dtype=np.float64) for a, b in zip(offsets[:-1], offsets[1:])], np.float64)
+
+
+def surface_stats(surf: dict, spacing=(1.0, 1.0, 1.0)) -> dict:
+    """Per-label surface measurements of a :func:`label_surface` mesh, float64, one row per label.
+
+    ``area_voxel = fz sy sx + fy sz sx + fx sz sy`` from ``faces`` (the voxel-face area, about 1.5 x a
+    smooth surface's); ``area``: the ``verts`` mesh scaled by ``spacing`` (sz, sy, sx), every quad as
+    the triangles (p0, p1, p2) and (p0, p2, p3); ``mesh_volume``: the sum of ``det / 6`` over the same
+    triangles; ``volume = voxels sz sy sx``; ``sphericity = pi^(1/3) (6 volume)^(2/3) / area`` (NaN
+    where ``area == 0``); ``n_verts``; ``n_quads``."""
+    sz, sy, sx = sp = _check_spacing(spacing, "surface_stats")
+    faces = np.asarray(surf["faces"], np.float64).reshape(-1, 3)
+    K = faces.shape[0]
+    lq, lv = np.asarray(surf["label_quads"], np.int64), np.asarray(surf["label_verts"], np.int64)
+    pts = np.asarray(surf["verts"], np.float64).reshape(-1, 3) * np.asarray(sp, np.float64)
+    p0, p1, p2, p3 = _quad_triangles(pts, np.asarray(surf["quads"], np.int64).reshape(-1, 4))
+    n1, n2 = np.cross(p1 - p0, p2 - p0), np.cross(p2 - p0, p3 - p0)
+    qarea = 0.5 * np.sqrt((n1 * n1).sum(1)) + 0.5 * np.sqrt((n2 * n2).sum(1))
+    qvol = ((p0 * n1).sum(1) + (p0 * n2).sum(1)) / 6.0  # det(p0, p1, p2) = p0 . ((p1 - p0) x (p2 - p0))
+    area, mesh_volume = _segment_sums(qarea, lq), _segment_sums(qvol, lq)
+    volume = np.asarray(surf["voxels"], np.float64).reshape(-1) * (sz * sy * sx)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        sph = np.where(area > 0, np.pi ** (1.0 / 3.0) * (6.0 * volume) ** (2.0 / 3.0) / area, np.nan)
+    return {"label": np.arange(1, K + 1, dtype=np.float64),
+            "area_voxel": faces[:, 0] * sy * sx + faces[:, 1] * sz * sx + faces[:, 2] * sz * sy,
+            "area": area, "mesh_volume": mesh_volume, "volume": volume, "sphericity": sph,
+            "n_verts": np.diff(lv).astype(np.float64), "n_quads": np.diff(lq).astype(np.float64)}
+
+
+def surface_to_obj(surf: dict, spacing=(1.0, 1.0, 1.0), labels=None, smooth: bool = True) -> str:
+    """Wavefront OBJ text of a :func:`label_surface` mesh: one ``o label_<l>`` group per label (all
+    with quads, or the given ``labels``), ``v x y z`` lines (the reverse of the stored order, scaled by
+    ``spacing`` (sz, sy, sx), written with ``repr`` of the Python float; ``smooth=False`` writes the
+    lattice corners instead of the surface-net vertices) and 1-based ``f`` lines with every quad's
+    vertex order reversed, so that normals point outward in the ``(x, y, z)`` frame."""
+    sz, sy, sx = _check_spacing(spacing, "surface_to_obj")
+    lv, lq = np.asarray(surf["label_verts"], np.int64), np.asarray(surf["label_quads"], np.int64)
+    K = lv.shape[0] - 1
+    if labels is None:
+        labels = [l for l in range(1, K + 1) if lq[l] > lq[l - 1]]
+    labels = [int(l) for l in labels]
+    if any(l < 1 or l > K for l in labels):
+        raise ValueError(f"surface_to_obj: labels must lie in 1..{K}, got {labels}")
+    pts = np.asarray(surf["verts" if smooth else "corner"]).astype(np.float64).reshape(-1, 3)
+    quads = np.asarray(surf["quads"], np.int64).reshape(-1, 4)
+    lines, base = [], 1
+    for l in labels:
+        v0, v1 = int(lv[l - 1]), int(lv[l])
+        lines.append(f"o label_{l}")
+        for z, y, x in pts[v0:v1].tolist():
+            lines.append(f"v {x * sx!r} {y * sy!r} {z * sz!r}")
+        for q in (quads[int(lq[l - 1]):int(lq[l])] - v0 + base).tolist():
+            lines.append(f"f {q[3]} {q[2]} {q[1]} {q[0]}")
+        base += v1 - v0
+    return "\n".join(lines) + ("\n" if lines else "")

@@ -286,6 +286,27 @@ def instance_stats(labels: torch.Tensor, n: int, z_offset: int = 0, group=None) 
             "centroid_z": acc[1, 1:] / c, "centroid_y": acc[2, 1:] / c, "centroid_x": acc[3, 1:] / c}
 
 
+def instance_surfaces(labels: torch.Tensor, n: int, keep: np.ndarray, spacing_nm, stats: bool, mesh: bool,
+                      instances: dict) -> dict:
+    """Surfaces of the instances ``1..n`` of a label volume, for :func:`analyze_volume`: the three
+    surface columns of the kept instances are added to ``instances`` (``stats``) and the OBJ text of
+    their meshes is returned as ``mesh_obj`` (``mesh``)."""
+    from ..cellpose import reference as cref
+    from ..cellpose.gpu import label_surface_gpu, surface_stats_gpu
+
+    sp = cref._check_spacing(spacing_nm, "analyze_volume")
+    surf = label_surface_gpu(labels, nlab=n + 1)
+    out = {}
+    if stats:
+        tab = {k: v.cpu().numpy() for k, v in surface_stats_gpu(surf, sp).items()}
+        for key, col in (("surface_area_nm2", "area"), ("surface_area_voxel_nm2", "area_voxel"), ("sphericity", "sphericity")):
+            instances[key] = tab[col][keep].tolist()
+    if mesh:
+        host = {k: v.cpu().numpy() for k, v in surf.items()}
+        out["mesh_obj"] = cref.surface_to_obj(host, spacing=sp, labels=(np.flatnonzero(keep) + 1).tolist())
+    return out
+
+
 def split_instances_sharded(mask: torch.Tensor, group=None, min_size: int = 300, closing_radius: int = 4,
                             min_distance: int = 8) -> tuple[torch.Tensor, int]:
     """Touching objects split by the 3-D marker watershed (:func:`mito.prob_to_instances_3d`) for a
@@ -454,7 +475,8 @@ def analyze_volume(vol: torch.Tensor, predict, tile: int = 512, overlap: int = 6
                    z_offset: int = 0, gather: str | None = None, timings: bool = False,
                    norm_range: tuple[float, float] | None = None, split_touching: bool = False,
                    closing_radius: int = 4, min_distance: int = 8, predict3d=None, tile_z: int = 32,
-                   overlap_z: int = 8, core: tuple[int, int] | None = None, split_halo: int | None = None) -> dict:
+                   overlap_z: int = 8, core: tuple[int, int] | None = None, split_halo: int | None = None,
+                   surface_stats: bool = False, spacing_nm=(1.0, 1.0, 1.0), return_mesh: bool = False) -> dict:
     """Single-process (or per-rank) 3-D analysis.  With a process group, ``vol`` is this rank's
     z-slab and results are globally consistent.  ``gather="mask"`` / ``"labels"`` all-gathers the
     stitched foreground mask (uint8) / global instance labels of the whole volume onto every rank
@@ -465,8 +487,17 @@ def analyze_volume(vol: torch.Tensor, predict, tile: int = 512, overlap: int = 6
     ``predict3d`` ([B, 1, tz, t, t] -> [B, C, tz, t, t], a 3-D U-Net) switches inference from
     slice-wise 2-D tiles to 3-D tiles with z-overlap blending (:func:`infer_tiled_3d`); ``core``
     = (lo, hi) crops this rank's slab out of a ``vol`` read with extra z-margin for that context
-    (overlap recompute instead of an input halo exchange)."""
+    (overlap recompute instead of an input halo exchange).  ``surface_stats`` (single process only)
+    meshes the labels' surfaces (:func:`cellpose.gpu.label_surface_gpu`, the HIP kernels on the GPU)
+    with voxel size ``spacing_nm`` (sz, sy, sx) and adds ``surface_area_nm2`` (the surface-net mesh),
+    ``surface_area_voxel_nm2`` (the voxel faces, about 1.5 x a smooth surface's) and ``sphericity`` to
+    ``instances``; ``return_mesh`` adds ``mesh_obj``, the OBJ text of the kept instances in nm.  Faces
+    on the volume's border count as surface: an instance cut by the border is closed there."""
     import time
+
+    if (surface_stats or return_mesh) and dist.is_initialized() and dist.get_world_size(group) > 1:
+        raise ValueError("surface_stats / return_mesh are not supported across GPU slabs (n_gpus > 1): an instance's "
+                         "surface would be cut at every slab seam")
 
     from ..search.preprocess import percentiles
 
@@ -511,6 +542,8 @@ def analyze_volume(vol: torch.Tensor, predict, tile: int = 512, overlap: int = 6
     keep = stats["voxels"] >= min_voxels
     out = {"n_instances": int(keep.sum()), "n_components": n, "volume_shape": list(mask.shape),
            "instances": {k: vv[keep].tolist() for k, vv in stats.items()}}
+    if surface_stats or return_mesh:
+        out.update(instance_surfaces(labels, n, keep, spacing_nm, surface_stats, return_mesh, out["instances"]))
     mark("stats")
     out["labels_slab_t"] = labels  # this rank's globally consistent slab labels (device tensor)
     if gather_labels:
