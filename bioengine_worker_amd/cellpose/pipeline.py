@@ -174,9 +174,34 @@ def resolve_norm(p: EvalParams) -> EvalParams:
     return p
 
 
+def _intake(p: "EvalParams | None", kw: dict, copy: bool) -> EvalParams:
+    """The ``(p, **kw)`` of an entry point -> its parameters: the keyword overrides set on ``p`` (a
+    fresh :class:`EvalParams` for None) and ``normalize`` canonicalised (:func:`resolve_norm`).  With
+    ``copy`` both happen on a copy and the caller's object stays as it was (:meth:`~CellposeRunner.
+    eval_stack`, :meth:`~CellposeRunner.eval_3d`); without, they are written into the caller's object
+    (:meth:`~CellposeRunner.eval`, :meth:`~CellposeRunner.eval_locked`, :meth:`~CellposeRunner.stream`)."""
+    if p is None:
+        p = EvalParams()
+    elif copy:
+        p = dataclasses.replace(p)
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return resolve_norm(p)
+
+
 def norm_on(p: EvalParams) -> bool:
     """Whether ``p`` asks for normalisation, whichever form ``p.normalize`` has."""
     return norm_params(p.normalize).normalize
+
+
+def _rescale_factor(diameter, diam_mean: float) -> float:
+    """``diam_mean / diameter``, the factor an image with cells of this diameter is resized by before
+    the network sees it; 1.0 (not rescaled) without a positive diameter (``None``, 0, nan, negative)
+    and within the band ``|diam_mean / diameter - 1| <= 1e-3``."""
+    if diameter is None or not diameter > 0:
+        return 1.0
+    r = diam_mean / float(diameter)
+    return r if abs(r - 1.0) > 1e-3 else 1.0
 
 
 def diameter_form(diameter) -> str:
@@ -206,10 +231,7 @@ def per_image_diameters(diameter, B: int, diam_mean: float) -> list:
             d = None if d is None else float(d)
         except (TypeError, ValueError):
             raise ValueError(f"diameter: every entry must be a number or None, got {d!r}") from None
-        if d is None or not d > 0 or abs(diam_mean / d - 1.0) <= 1e-3:
-            out.append(None)
-        else:
-            out.append(d)
+        out.append(None if _rescale_factor(d, diam_mean) == 1.0 else d)
     return out
 
 
@@ -288,6 +310,7 @@ class CellposeRunner:
         self._plans: dict = {}
         self._scaled_plans: dict = {}
         self._net_graphs: dict = {}
+        self._mask_stream = None  # made on first use (:meth:`_masks_on_side_stream`)
 
     # ---------------------------------------------------------------- network
     def _plan(self, H, W, p: EvalParams):
@@ -470,10 +493,7 @@ class CellposeRunner:
         With a per-image or ``"auto"`` ``diameter`` the masks carry ``masks.diameters``: a float32
         CPU tensor [B] of the diameter used for each image (0: not rescaled; under ``"auto"`` the
         estimate, whether it led to a second pass or not)."""
-        p = p or EvalParams()
-        for k, v in kw.items():
-            setattr(p, k, v)
-        resolve_norm(p)
+        p = _intake(p, kw, copy=False)
         form = diameter_form(p.diameter)
         if form == "auto" and not p.compute_masks:
             raise ValueError("diameter='auto' estimates the diameters from the masks: it needs compute_masks=True")
@@ -522,7 +542,7 @@ class CellposeRunner:
         B = x.shape[0]
         masks, y, style = self._eval_batch(x, dataclasses.replace(p, diameter=None), raw)
         d = self.estimate_diameters(masks)
-        redo = [b for b in range(B) if d[b] > 0 and abs(self.diam_mean / d[b] - 1.0) > 1e-3]
+        redo = [b for b in range(B) if _rescale_factor(d[b], self.diam_mean) != 1.0]
         if redo:
             idx = torch.tensor(redo, device=x.device)
             xs = x if len(redo) == B else x[idx].contiguous()
@@ -546,31 +566,18 @@ class CellposeRunner:
         p.norm3d`` the percentiles are taken per channel over the whole stack; the planes then run
         through :meth:`eval` in chunks of ``p.stack_batch``.  ``p.stitch_threshold == 0`` returns the
         per-plane masks unstitched."""
-        p = dataclasses.replace(p) if p is not None else EvalParams()
-        for k, v in kw.items():
-            setattr(p, k, v)
+        p = _intake(p, kw, copy=True)
         _scalar_diameter_only(p, "eval_stack")
-        resolve_norm(p)
         if norm_on(p) and p.norm3d and p.normalize.tile_blocksize > 0:
             raise ValueError("tile_norm_blocksize over a whole stack (norm3D) is not supported: give norm3D=False "
                              "to normalise every plane against its own block grid")
-        x = torch.as_tensor(np.asarray(stack) if not torch.is_tensor(stack) else stack)
-        if x.dim() == 3:
-            x = x[:, None]
-        elif x.dim() == 4:
-            if x.shape[-1] <= 4 and x.shape[1] > 4:  # channel-last, as as_batch decides for one image
-                x = x.permute(0, 3, 1, 2)
-        else:
-            raise ValueError(f"eval_stack expects [Z,H,W], [Z,C,H,W] or [Z,H,W,C], got shape {tuple(x.shape)}")
-        x = as_batch(x, self.nchan, self.device)
-        Z, C, H, W = x.shape
+        x = as_batch(_planes_first(stack, "eval_stack expects"), self.nchan, self.device)
+        Z = x.shape[0]
         if Z == 0:
             raise ValueError("eval_stack: empty stack")
         pp = dataclasses.replace(p)
         if norm_on(p) and p.norm3d:
-            with trace.span("cellpose.normalize99", cuda=self.device.type == "cuda", images=Z):
-                xs = x.permute(1, 0, 2, 3).reshape(1, C, Z * H, W)
-                x = self._normalize(xs, p.normalize).reshape(C, Z, H, W).permute(1, 0, 2, 3).contiguous()
+            x = self._normalize_volume(x, p.normalize)
             pp.normalize = False
         masks, flows, styles = [], [], []
         step = max(1, int(p.stack_batch))
@@ -584,13 +591,10 @@ class CellposeRunner:
             return None, flows, styles
         M = torch.cat(masks)
         if p.stitch_threshold > 0:
-            with trace.span("cellpose.stitch3d", cuda=M.is_cuda, planes=Z):
-                if M.is_cuda:
-                    from .gpu import stitch3d_gpu
+            from .gpu import stitch3d_gpu  # the oracle for CPU tensors
 
-                    M = stitch3d_gpu(M.to(torch.int32), p.stitch_threshold, min_size=p.min_size)
-                else:
-                    M = torch.from_numpy(ref.stitch3d(M.numpy(), p.stitch_threshold, min_size=p.min_size))
+            with trace.span("cellpose.stitch3d", cuda=M.is_cuda, planes=Z):
+                M = stitch3d_gpu(M.to(torch.int32), p.stitch_threshold, min_size=p.min_size)
         return M, flows, styles
 
     #: fewest planes along any axis of an :meth:`eval_3d` volume.  The ZX and ZY views are Z planes
@@ -619,22 +623,13 @@ class CellposeRunner:
         resampled along z to ``Z' = round(Z * anisotropy)`` planes (trilinear, ``align_corners=False``),
         masks are computed there and brought back with the nearest-plane rule ``z_src = min(floor((z +
         0.5) * Z' / Z), Z' - 1)`` and numbered ``1..K`` again.  ``flows`` stay at the resampled depth ``Z'`` (``Z' = Z`` otherwise)."""
-        p = dataclasses.replace(p) if p is not None else EvalParams()
-        for k, v in kw.items():
-            setattr(p, k, v)
+        from . import gpu
+
+        p = _intake(p, kw, copy=True)
         _scalar_diameter_only(p, "eval_3d")
-        resolve_norm(p)
         if norm_on(p) and p.normalize.tile_blocksize > 0:
             raise ValueError("tile_norm_blocksize is not supported by eval_3d: the volume is normalised once over all voxels")
-        x = torch.as_tensor(np.asarray(volume) if not torch.is_tensor(volume) else volume)
-        if x.dim() == 3:
-            x = x[:, None]
-        elif x.dim() == 4:
-            if x.shape[-1] <= 4 and x.shape[1] > 4:  # channel-last, as as_batch decides for one image
-                x = x.permute(0, 3, 1, 2)
-        else:
-            raise ValueError(f"eval_3d expects [Z,H,W], [Z,C,H,W] or [Z,H,W,C], got shape {tuple(x.shape)}")
-        x = as_batch(x, self.nchan, self.device)
+        x = as_batch(_planes_first(volume, "eval_3d expects"), self.nchan, self.device)
         Z, C, H, W = x.shape
         aniso = p.anisotropy
         if aniso is not None and not aniso > 0:
@@ -646,13 +641,9 @@ class CellposeRunner:
                              f"{Z} x {H} x {W} volume" + (f" resampled to {Zr} planes" if Zr != Z else ""))
         on_gpu = self.device.type == "cuda"
         if on_gpu:
-            from . import gpu
-
             gpu._check_volume(Zr, H, W)
         if norm_on(p):
-            with trace.span("cellpose.normalize99", cuda=on_gpu, images=Z):
-                xs = x.permute(1, 0, 2, 3).reshape(1, C, Z * H, W)
-                x = self._normalize(xs, p.normalize).reshape(C, Z, H, W).permute(1, 0, 2, 3).contiguous()
+            x = self._normalize_volume(x, p.normalize)
         if Zr != Z:
             x = F.interpolate(x.permute(1, 0, 2, 3)[None], size=(Zr, H, W), mode="trilinear",
                               align_corners=False)[0].permute(1, 0, 2, 3).contiguous()
@@ -683,13 +674,8 @@ class CellposeRunner:
             return None, acc, style
         niter = p.niter if p.niter else int(200 / max(rescale, 1e-3))
         with trace.span("cellpose.masks3d", cuda=on_gpu, planes=Zr):
-            if on_gpu:
-                M = gpu.compute_masks3d_gpu(acc, None, niter=niter, cellprob_threshold=p.cellprob_threshold,
-                                            min_size=p.min_size, max_size_fraction=p.max_size_fraction)
-            else:
-                a = acc.numpy()
-                M = torch.from_numpy(ref.compute_masks3d(a[:3], a[3], niter=niter, cellprob_threshold=p.cellprob_threshold,
-                                                         min_size=p.min_size, max_size_fraction=p.max_size_fraction))
+            M = gpu.compute_masks3d_gpu(acc, None, niter=niter, cellprob_threshold=p.cellprob_threshold,  # CPU: the oracle
+                                        min_size=p.min_size, max_size_fraction=p.max_size_fraction)
             if Zr != Z:
                 zs = ((torch.arange(Z, device=M.device) * 2 + 1) * Zr // (2 * Z)).clamp_(max=Zr - 1)
                 # an instance that lives only on planes the rule skips is gone: number the rest 1..K again
@@ -777,7 +763,7 @@ class CellposeRunner:
             return x, False
         from .gpu import takes_fused_front
 
-        rescaled = p.diameter is not None and p.diameter > 0 and abs(self.diam_mean / float(p.diameter) - 1.0) > 1e-3
+        rescaled = _rescale_factor(p.diameter, self.diam_mean) != 1.0
         if (self.device.type == "cuda" and norm_on(p) and p.tile and not rescaled and x.shape[0] > self.GRAPH_NET_MAX_B
                 and takes_fused_front(x)):
             return x, True
@@ -813,59 +799,32 @@ class CellposeRunner:
         return y, style, rescale
 
     def _eval_one(self, x, p: EvalParams, raw: bool = False):
-        if diameter_form(p.diameter) == "list":
-            y, style, rescale = self._net_stage_list(x, p, raw)
-            if not p.compute_masks:
-                return None, y, style
-            with trace.span("cellpose.masks", cuda=self.device.type == "cuda", images=x.shape[0]):
-                masks = self.compute_masks(y, p, rescale)
-            return masks, y, style
-        x, raw = self._front(x, p, raw)
-        B, C, H, W = x.shape
-        if not (p.diameter is not None and p.diameter > 0 and abs(self.diam_mean / float(p.diameter) - 1.0) > 1e-3):
-            r = self._net_graphed(x, p)
-            if r is not None:
-                y, style = r
-                if not p.compute_masks:
-                    return None, y, style
-                with trace.span("cellpose.masks", cuda=True, images=B):
-                    masks = self.compute_masks(y, p, 1.0)
-                return masks, y, style
-        if norm_on(p) and not raw:
-            with trace.span("cellpose.normalize99", cuda=True, images=B):
-                x = self._normalize(x, p.normalize)
-        rescale = 1.0
-        if p.diameter is not None and p.diameter > 0:
-            rescale = self.diam_mean / float(p.diameter)
-        if abs(rescale - 1.0) > 1e-3:
-            Hs, Ws = max(8, int(round(H * rescale))), max(8, int(round(W * rescale)))
-            xs = resize_bilinear(x, (Hs, Ws))
-            y, style = self.run_net(xs, p)
-            y = resize_bilinear(y, (H, W))
-        else:
-            y, style = self.run_net(x, p, raw=True) if raw else self.run_net(x, p)
+        y, style, rescale = self._net_stage(x, p, raw)
         if not p.compute_masks:
             return None, y, style
-        with trace.span("cellpose.masks", cuda=True, images=B):
+        with trace.span("cellpose.masks", cuda=self.device.type == "cuda", images=x.shape[0]):
             masks = self.compute_masks(y, p, rescale)
         return masks, y, style
 
     def _net_stage(self, x, p: EvalParams, raw: bool = False):
+        """Everything before mask recovery, for a batch as :func:`as_batch` returns it (``raw`` as it
+        says): front end, normalisation, the ``diameter`` rescale around the network, blend.
+        Returns ``(y [B, 3, H, W], style [B, S], rescale)``, ``rescale`` being what
+        :meth:`compute_masks` takes: :func:`_rescale_factor` of a scalar diameter, a
+        :class:`PerImageRescale` for the sequence form."""
         if diameter_form(p.diameter) == "list":
             return self._net_stage_list(x, p, raw)
         x, raw = self._front(x, p, raw)
         B, C, H, W = x.shape
-        if not (p.diameter is not None and p.diameter > 0 and abs(self.diam_mean / float(p.diameter) - 1.0) > 1e-3):
+        rescale = _rescale_factor(p.diameter, self.diam_mean)
+        if rescale == 1.0:
             r = self._net_graphed(x, p)
             if r is not None:
-                return r[0], r[1], 1.0
+                return r[0], r[1], rescale
         if norm_on(p) and not raw:
             with trace.span("cellpose.normalize99", cuda=True, images=B):
                 x = self._normalize(x, p.normalize)
-        rescale = 1.0
-        if p.diameter is not None and p.diameter > 0:
-            rescale = self.diam_mean / float(p.diameter)
-        if abs(rescale - 1.0) > 1e-3:
+        if rescale != 1.0:
             Hs, Ws = max(8, int(round(H * rescale))), max(8, int(round(W * rescale)))
             xs = resize_bilinear(x, (Hs, Ws))
             y, style = self.run_net(xs, p)
@@ -874,28 +833,29 @@ class CellposeRunner:
             y, style = self.run_net(x, p, raw=True) if raw else self.run_net(x, p)
         return y, style, rescale
 
+    def _masks_on_side_stream(self, y, p: EvalParams, rescale, ev) -> torch.Tensor:
+        """:meth:`compute_masks` of ``y`` on the runner's second stream (:func:`mask_stream`, made on
+        first use), queued there behind ``ev``, the event recorded after ``y``'s network stage.  The
+        masks belong to that stream (``self._mask_stream``); who waits for them, and how, is left
+        to the caller: :meth:`_eval_pipelined`, :meth:`eval_locked` and :meth:`stream` each differ."""
+        if self._mask_stream is None:
+            self._mask_stream = mask_stream(self.device)
+        side = self._mask_stream
+        with torch.cuda.stream(side):
+            side.wait_event(ev)
+            y.record_stream(side)
+            with trace.span("cellpose.masks", cuda=True, images=y.shape[0]):
+                return self.compute_masks(y, p, rescale)
+
     def _eval_pipelined(self, x, p: EvalParams, nch: int, raw: bool = False):
         """Two-stream software pipeline over micro-batches: net(i+1) on the current stream is queued
         before mask recovery of micro-batch i (which syncs the host on its own stream) starts."""
         main = torch.cuda.current_stream(self.device)
-        if getattr(self, "_mask_stream", None) is None:
-            self._mask_stream = mask_stream(self.device)
-        side = self._mask_stream
         parts = x.tensor_split(nch)
         ys, styles, masks = [], [], []
         pending = None
         per_image = diameter_form(p.diameter) == "list"
         starts = np.cumsum([0] + [part.shape[0] for part in parts])  # the diameters split with the images
-
-        def finish(item):
-            y, rescale, ev = item
-            with torch.cuda.stream(side):
-                side.wait_event(ev)
-                y.record_stream(side)
-                with trace.span("cellpose.masks", cuda=True, images=y.shape[0]):
-                    m = self.compute_masks(y, p, rescale)
-            masks.append(m)
-
         for i, part in enumerate(parts):
             pp = dataclasses.replace(p, diameter=list(p.diameter[starts[i]: starts[i + 1]])) if per_image else p
             y, style, rescale = self._net_stage(part, pp, raw)
@@ -904,10 +864,10 @@ class CellposeRunner:
             ev = torch.cuda.Event()
             ev.record(main)
             if pending is not None:
-                finish(pending)
-            pending = (y, rescale, ev)
-        finish(pending)
-        main.wait_stream(side)
+                masks.append(self._masks_on_side_stream(*pending))
+            pending = (y, p, rescale, ev)
+        masks.append(self._masks_on_side_stream(*pending))
+        main.wait_stream(self._mask_stream)
         for m in masks:
             m.record_stream(main)
         out = torch.cat(masks)
@@ -924,10 +884,7 @@ class CellposeRunner:
         ``(masks, flows, styles, ready)``: ``ready`` is a HIP event recorded after the masks (None
         off the GPU path) -- wait on it on a copy stream rather than on the caller's stream, which may
         already hold the next batch's network."""
-        p = p or EvalParams()
-        for k, v in kw.items():
-            setattr(p, k, v)
-        resolve_norm(p)
+        p = _intake(p, kw, copy=False)
         if self.device.type != "cuda" or not p.compute_masks or diameter_form(p.diameter) == "auto":
             with net_lock:  # "auto" is two dependent passes: it runs whole, as eval() runs it
                 m, y, st = self.eval(images, p)
@@ -944,16 +901,9 @@ class CellposeRunner:
             ev = torch.cuda.Event()
             ev.record(main)
         with mask_lock:
-            if getattr(self, "_mask_stream", None) is None:
-                self._mask_stream = mask_stream(self.device)
-            side = self._mask_stream
-            with torch.cuda.stream(side):
-                side.wait_event(ev)
-                y.record_stream(side)
-                with trace.span("cellpose.masks", cuda=True, images=y.shape[0]):
-                    m = self.compute_masks(y, p, rescale)
+            m = self._masks_on_side_stream(y, p, rescale, ev)
             done = torch.cuda.Event()
-            done.record(side)
+            done.record(self._mask_stream)
         return m, y, style, done
 
     def stream(self, p: EvalParams | None = None) -> "_EvalStream":
@@ -962,7 +912,15 @@ class CellposeRunner:
         batch i-1 on a second HIP stream (so its latency-bound kernels and host syncs overlap batch
         i's convs) and returns batch i-1's ``(masks, flows, styles)`` (None for the first batch);
         ``flush()`` returns the last batch's.  Same per-batch results as :meth:`eval`."""
-        return _EvalStream(self, p or EvalParams())
+        return _EvalStream(self, _intake(p, {}, copy=False))
+
+    def _normalize_volume(self, x, norm):
+        """``x`` [Z, C, H, W] normalised per channel over the whole stack, which :meth:`_normalize`
+        sees as one image of ``Z * H`` rows."""
+        Z, C, H, W = x.shape
+        with trace.span("cellpose.normalize99", cuda=self.device.type == "cuda", images=Z):
+            xs = x.permute(1, 0, 2, 3).reshape(1, C, Z * H, W)
+            return self._normalize(xs, norm).reshape(C, Z, H, W).permute(1, 0, 2, 3).contiguous()
 
     def _normalize(self, x, norm=True):
         """``x`` [B, C, H, W] normalised per image by ``norm`` (anything :func:`norm_params` takes)."""
@@ -1025,14 +983,10 @@ class CellposeRunner:
         the caller's units.  Returns a list with one table (a dict of numpy arrays plus ``n_cells`` and
         ``diameter_px``) per image, or the one table of a volume.  Masks on the GPU are measured by
         the HIP kernel (:func:`gpu.measure_masks_gpu`), everything else by the numpy oracle."""
-        m = masks if torch.is_tensor(masks) else torch.as_tensor(np.asarray(masks))
-        if m.dim() == 2 and not volume:
-            m = m[None]
-        if m.dim() != 3:
-            raise ValueError(f"measure expects [B, H, W] masks or one [Z, H, W] volume, got shape {tuple(m.shape)}")
+        m, _ = _label_masks(masks, "measure", volume)
         img = None
         if images is not None:
-            img = as_batch(_planes_first(images) if volume else images, self.nchan, m.device)
+            img = as_batch(_planes_first(images, "a z-stack is") if volume else images, self.nchan, m.device)
             if img.shape[0] != m.shape[0] or img.shape[2:] != m.shape[1:]:
                 raise ValueError(f"measure: images {tuple(img.shape)} do not fit masks {tuple(m.shape)}")
         raws = measure_launch(m, img, volume=volume)
@@ -1051,13 +1005,7 @@ class CellposeRunner:
         planes' dicts for a volume.  ``nlab``: an upper bound on the labels + 1; by default the
         ``label_bound`` the mask stage left on ``masks``, else ``masks.max() + 1``.  Masks on the GPU
         are traced by the HIP kernels (:func:`gpu.mask_rings_gpu`), everything else by the oracle."""
-        m = masks if torch.is_tensor(masks) else torch.as_tensor(np.asarray(masks))
-        if m.dim() == 2 and not volume:
-            m = m[None]
-        if m.dim() != 3:
-            raise ValueError(f"outlines expects [B, H, W] masks or one [Z, H, W] volume, got shape {tuple(m.shape)}")
-        if nlab is None:
-            nlab = getattr(masks, "label_bound", None)
+        m, nlab = _label_masks(masks, "outlines", volume, nlab)
         return outline_rings(outline_launch(m, nlab=nlab, volume=volume))
 
     # ---------------------------------------------------------------- surfaces
@@ -1076,11 +1024,7 @@ class CellposeRunner:
         ``masks.max() + 1``.  A volume on the GPU is meshed by the HIP kernels
         (:func:`gpu.label_surface_gpu`, :func:`gpu.surface_stats_gpu`), everything else by the oracle."""
         sp = ref._check_spacing(spacing, "surfaces")
-        m = masks if torch.is_tensor(masks) else torch.as_tensor(np.asarray(masks))
-        if m.dim() != 3:
-            raise ValueError(f"surfaces expects one [Z, H, W] label volume, got shape {tuple(m.shape)}")
-        if nlab is None:
-            nlab = getattr(masks, "label_bound", None)
+        m, nlab = _label_masks(masks, "surfaces", True, nlab, "one [Z, H, W] label volume")
         return surface_tables(surface_launch(m, sp, nlab=nlab))
 
     # ---------------------------------------------------------------- polygon annotations
@@ -1196,14 +1140,28 @@ def join_polygons(parts) -> dict:
             "ring_image": np.concatenate([np.full(o.shape[0] - 1, b, np.int64) for b, o in enumerate(offs)] + [np.zeros(0, np.int64)])}
 
 
-def _planes_first(stack) -> torch.Tensor:
-    """[Z, H, W], [Z, C, H, W] or [Z, H, W, C] -> [Z, C, H, W], as eval_stack reads a z-stack."""
+def _planes_first(stack, what: str) -> torch.Tensor:
+    """[Z, H, W], [Z, C, H, W] or [Z, H, W, C] -> [Z, C, H, W]: how every entry point reads a z-stack
+    (channel-last as :func:`as_batch` decides it for one image).  ``what`` opens the error text."""
     x = torch.as_tensor(np.asarray(stack) if not torch.is_tensor(stack) else stack)
     if x.dim() == 3:
         return x[:, None]
     if x.dim() == 4:
         return x.permute(0, 3, 1, 2) if x.shape[-1] <= 4 and x.shape[1] > 4 else x
-    raise ValueError(f"a z-stack is [Z,H,W], [Z,C,H,W] or [Z,H,W,C], got shape {tuple(x.shape)}")
+    raise ValueError(f"{what} [Z,H,W], [Z,C,H,W] or [Z,H,W,C], got shape {tuple(x.shape)}")
+
+
+def _label_masks(masks, method: str, volume: bool, nlab: int | None = None,
+                 forms: str = "[B, H, W] masks or one [Z, H, W] volume"):
+    """The ``masks`` argument of ``method`` (measure, outlines, surfaces) -> ``(m, nlab)``: a [B or Z,
+    H, W] tensor (one [H, W] image is a batch of one, unless a volume is asked for) and the bound on
+    the labels + 1, by default the ``label_bound`` the mask stage left on ``masks`` (else None)."""
+    m = masks if torch.is_tensor(masks) else torch.as_tensor(np.asarray(masks))
+    if m.dim() == 2 and not volume:
+        m = m[None]
+    if m.dim() != 3:
+        raise ValueError(f"{method} expects {forms}, got shape {tuple(m.shape)}")
+    return m, (getattr(masks, "label_bound", None) if nlab is None else nlab)
 
 
 def measure_launch(m: torch.Tensor, img: torch.Tensor | None, volume: bool = False, nlab: int | None = None) -> dict:
@@ -1343,14 +1301,10 @@ class _EvalStream:
     """See :meth:`CellposeRunner.stream` (GPU only; a CPU runner evaluates each batch directly)."""
 
     def __init__(self, runner: CellposeRunner, p: EvalParams):
-        self.r, self.p = runner, resolve_norm(p)
+        self.r, self.p = runner, p
         self.pending = None
         # "auto" is two dependent passes per batch: such a stream evaluates every batch directly
         self.cuda = runner.device.type == "cuda" and p.compute_masks and diameter_form(p.diameter) != "auto"
-        if self.cuda:
-            if getattr(runner, "_mask_stream", None) is None:
-                runner._mask_stream = mask_stream(runner.device)
-            self.side = runner._mask_stream
 
     @torch.no_grad()
     def submit(self, images):
@@ -1366,13 +1320,9 @@ class _EvalStream:
     def _finish(self, item):
         y, style, rescale, ev = item
         main = torch.cuda.current_stream(self.r.device)
-        with torch.cuda.stream(self.side):
-            self.side.wait_event(ev)
-            y.record_stream(self.side)
-            with trace.span("cellpose.masks", cuda=True, images=y.shape[0]):
-                m = self.r.compute_masks(y, self.p, rescale)
+        m = self.r._masks_on_side_stream(y, self.p, rescale, ev)
         done = torch.cuda.Event()
-        done.record(self.side)
+        done.record(self.r._mask_stream)
         main.wait_event(done)  # consumers on the main stream see finished masks
         m.record_stream(main)
         return m, y, style
