@@ -567,8 +567,9 @@ class CellImageSearch:
 
     @schema_method
     async def get_umap_preview(self, n_samples: int = Field(10_000, ge=100, le=100_000), color_by: str = Field("compound"),
-                               force_recompute: bool = Field(False)) -> dict:
-        """2-D projection of a sample of indexed cells (UMAP if installed, else GPU PCA)."""
+                               force_recompute: bool = Field(False), method: str = Field("auto")) -> dict:
+        """2-D projection of a sample of indexed cells.  ``method``: "auto" (umap-learn if installed, else the
+        in-house GPU UMAP on a GPU worker, else PCA), "umap" (the in-house UMAP) or "pca"."""
         from bioengine_worker_amd.search.ingestion import index_dir
         from bioengine_worker_amd.search.projection import compute_projection
 
@@ -576,7 +577,8 @@ class CellImageSearch:
         if self._metadata_df is not None and color_by in self._metadata_df.columns:
             labels = self._metadata_df[color_by].astype(str).tolist()
         cache = index_dir(self._workspace_dir) / f"umap_cache_{color_by}.npz"
-        return await asyncio.to_thread(compute_projection, self._index, labels, cache, n_samples, 42, force_recompute)
+        return await asyncio.to_thread(compute_projection, self._index, labels, cache, n_samples, 42, force_recompute,
+                                       "", method)
 
     @schema_method
     async def project_query_onto_umap(self, image_b64: str = Field(..., description="Base64 query image.")) -> dict:

@@ -1,5 +1,25 @@
 """CPU oracle of the cell-image-search pre-processing (numpy + PIL), mirroring the reference's
-normalizer.py:32-153 and ingestion.py:317-387 semantics.  Used by tests and as the CPU path."""
+normalizer.py:32-153 and ingestion.py:317-387 semantics.  Used by tests and as the CPU path.
+
+UMAP for the landscape view (second half of the file; the oracle of ``search/umap.py`` and
+``csrc/kernels/umap.hip``).  The rules are written from memory of umap-learn 0.5 (``UMAP(n_neighbors=15, min_dist=0.1,
+metric="cosine")``, two components).  umap-learn is not installed where this project is built and
+tested, so NOTHING here has been compared with it; the oracle is the definition the GPU path is
+tested against, stage by stage.
+
+Deliberate departures from umap-learn:
+
+1. The layout step is SYNCHRONOUS (every position read in an epoch is of the epoch's input) and its
+   negative samples come from a stateless counter hash of (edge, seed, epoch, sample).  umap-learn
+   updates positions in place, edge by edge, with a per-vertex ``tau_rand`` state.  The synchronous
+   form is what makes a GPU run bitwise reproducible and comparable with an oracle at all.
+2. The initialisation is PCA (umap-learn's ``init="pca"``), not the spectral layout.
+3. No noise is added to the initial coordinates.
+
+Precision: the neighbour table, the bisection and the memberships take a ``dtype`` (float64 is the
+rule, float32 the yardstick the GPU tests measure rounding with); the symmetric weights and the whole
+schedule state are float32 with every operation rounded on its own.
+"""
 from __future__ import annotations
 
 import numpy as np
@@ -129,3 +149,290 @@ def extract_cell_crops(image: np.ndarray, crop_size: int = 224, n_crops: int = 1
     if len(cents) < 10:
         cents = grid_centroids(H, W, crop_size, n_crops)
     return crops_at(img, cents[:n_crops], crop_size)
+
+
+# ---------------------------------------------------------------------------------------------------
+# UMAP for the landscape view: the numpy oracle of search/umap.py and csrc/kernels/umap.hip
+# ---------------------------------------------------------------------------------------------------
+UMAP_METRICS = ("cosine", "euclidean")
+SMOOTH_K_TOLERANCE = 1e-5
+MIN_K_DIST_SCALE = 1e-3
+_F32 = np.float32
+
+
+def umap_ab(spread: float = 1.0, min_dist: float = 0.1) -> tuple[float, float]:
+    """Least-squares fit of ``1 / (1 + a x^(2b))`` to ``1 if x < min_dist else exp(-(x - min_dist) / spread)``
+    sampled on ``linspace(0, 3 spread, 300)`` (umap's ``find_ab_params``)."""
+    from scipy.optimize import curve_fit
+
+    xv = np.linspace(0, spread * 3, 300)
+    yv = np.where(xv < min_dist, 1.0, np.exp(-(xv - min_dist) / spread))
+    (a, b), _ = curve_fit(lambda x, a, b: 1.0 / (1.0 + a * x ** (2 * b)), xv, yv)
+    return float(a), float(b)
+
+
+def knn_table(x: np.ndarray, k: int, metric: str = "cosine", dtype=np.float64):
+    """-> ``idx [n, k]`` int32, ``dist [n, k]`` float32.  ``k`` counts the point itself: column 0 is
+    forced to ``(i, 0.0)``, the others are the ``k - 1`` nearest OTHER points, ascending (ties by index)."""
+    if metric not in UMAP_METRICS:
+        raise ValueError(f"metric must be one of {UMAP_METRICS}")
+    x = np.asarray(x, dtype)
+    n = x.shape[0]
+    if not n > k:
+        raise ValueError(f"need more points ({n}) than n_neighbors ({k})")
+    if metric == "cosine":
+        nrm = np.sqrt((x * x).sum(1))
+        if (nrm == 0).any():
+            raise ValueError("cosine metric: zero-norm row")
+        xn = x / nrm[:, None]
+        d = np.maximum(0, 1 - xn @ xn.T)
+    else:
+        sq = (x * x).sum(1)
+        d = np.sqrt(np.maximum(0, sq[:, None] + sq[None, :] - 2 * (x @ x.T)))
+    np.fill_diagonal(d, np.inf)
+    order = np.argsort(d, axis=1, kind="stable")[:, : k - 1]
+    idx = np.concatenate([np.arange(n)[:, None], order], 1).astype(np.int32)
+    dist = np.concatenate([np.zeros((n, 1), d.dtype), np.take_along_axis(d, order, 1)], 1).astype(_F32)
+    return idx, dist
+
+
+def smooth_knn(dist: np.ndarray, dtype=np.float64, n_iter: int = 64):
+    """umap's ``smooth_knn_dist`` with ``local_connectivity = 1``, ``bandwidth = 1`` -> ``rho [n]``,
+    ``sigma [n]`` in ``dtype``.  ``rho_i`` is the smallest strictly positive entry of row i (0 without
+    one); ``sigma_i`` the bisection of ``sum_{j>=1} (exp(-(d_ij - rho_i) / sigma) if d_ij > rho_i else 1)``
+    to ``log2(k)``, floored at 1e-3 of the row's mean (of the global mean when ``rho_i == 0``)."""
+    d = np.asarray(dist, _F32).astype(dtype)
+    n, k = d.shape
+    one = dtype(1)
+    target = dtype(np.log2(dtype(k)))
+    gmean = d.mean(dtype=dtype)
+    rho = np.zeros(n, dtype)
+    sigma = np.zeros(n, dtype)
+    for i in range(n):
+        row = d[i]
+        pos = row[row > 0]
+        r = pos.min() if pos.size else dtype(0)
+        gap = row[1:] - r
+        lo, hi, mid = dtype(0), dtype(np.inf), one
+        for _ in range(n_iter):
+            psum = np.where(gap > 0, np.exp(-(np.maximum(gap, 0) / mid)), one).sum(dtype=dtype)
+            if abs(psum - target) < SMOOTH_K_TOLERANCE:
+                break
+            if psum > target:
+                hi = mid
+                mid = (lo + hi) / dtype(2)
+            else:
+                lo = mid
+                mid = mid * dtype(2) if np.isinf(hi) else (lo + hi) / dtype(2)
+        floor = dtype(MIN_K_DIST_SCALE) * (row.mean(dtype=dtype) if r > 0 else gmean)
+        rho[i] = r
+        sigma[i] = max(mid, floor)
+    return rho, sigma
+
+
+def memberships(idx: np.ndarray, dist: np.ndarray, rho: np.ndarray, sigma: np.ndarray) -> np.ndarray:
+    """Directed memberships ``a [n, k-1]`` (float32) of columns 1..k-1, computed in ``rho.dtype``:
+    1 when ``d - rho <= 0`` or ``sigma == 0``, else ``exp(-(d - rho) / sigma)``; 0 for a listed self."""
+    dt = rho.dtype.type
+    gap = np.asarray(dist, _F32).astype(dt)[:, 1:] - rho[:, None]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        a = np.where((gap <= 0) | (sigma[:, None] == 0), dt(1), np.exp(-(np.maximum(gap, 0) / sigma[:, None])))
+    a = np.where(idx[:, 1:] == np.arange(idx.shape[0])[:, None], dt(0), a)
+    return a.astype(_F32)
+
+
+def default_n_epochs(n: int) -> int:
+    return 500 if n <= 10000 else 200
+
+
+def fuzzy_union(a: np.ndarray, b: np.ndarray) -> np.ndarray:
+    """``fmaf(-a, b, a + b)`` in float32: the sum is rounded to float32, the product of two float32 is
+    exact in float64, the difference is rounded once to float64 and once to float32.  Symmetric in its
+    arguments bit for bit, so ``w_ij == w_ji`` exactly; the layout schedule relies on that."""
+    a = np.asarray(a, _F32)
+    b = np.asarray(b, _F32)
+    return ((a + b).astype(np.float64) - a.astype(np.float64) * b.astype(np.float64)).astype(_F32)
+
+
+def fuzzy_graph(idx: np.ndarray, dist: np.ndarray, n_epochs: int | None = None, dtype=np.float64):
+    """Neighbour table -> symmetric CSR ``(row_ptr int64 [n+1], col int32, w float32)``: the fuzzy union of
+    the directed memberships over every pair present in either direction, pairs with
+    ``w < max(w) / n_epochs`` dropped, columns ascending within a row.  A row of ``idx`` must not list
+    a vertex twice (a neighbour table never does)."""
+    idx = np.asarray(idx)
+    n, k = idx.shape
+    if n_epochs is None:
+        n_epochs = default_n_epochs(n)
+    rho, sigma = smooth_knn(dist, dtype)
+    a = memberships(idx, dist, rho, sigma)
+    rows = np.repeat(np.arange(n, dtype=np.int64), k - 1)
+    cols = idx[:, 1:].astype(np.int64).ravel()
+    av = a.ravel()
+    keep = rows != cols
+    rows, cols, av = rows[keep], cols[keep], av[keep]
+    key = rows * n + cols
+    if np.unique(key).size != key.size:
+        raise ValueError("a row of idx lists a vertex twice")
+    order = np.argsort(key)
+    skey, sa = key[order], av[order]
+    rkey = cols * n + rows  # the reciprocal direction; an absent one counts as 0
+    p = np.minimum(np.searchsorted(skey, rkey), skey.size - 1)
+    rec = np.where(skey[p] == rkey, sa[p], _F32(0)).astype(_F32)
+    w = fuzzy_union(av, rec)
+    ukey, first = np.unique(np.concatenate([key, rkey]), return_index=True)
+    uw = np.concatenate([w, w])[first]
+    thr = _F32(uw.max()) / _F32(n_epochs)
+    live = uw >= thr
+    ukey, uw = ukey[live], uw[live]
+    row_ptr = np.concatenate([[0], np.cumsum(np.bincount(ukey // n, minlength=n))]).astype(np.int64)
+    return row_ptr, (ukey % n).astype(np.int32), uw.astype(_F32)
+
+
+def prune_threshold(w: np.ndarray, n_epochs: int) -> np.float32:
+    return _F32(np.max(w)) / _F32(n_epochs)
+
+
+def layout_state(w: np.ndarray, negative_sample_rate: int = 5) -> dict:
+    """Per directed edge, float32: ``eps = max(w) / w``, ``epn = eps / negative_sample_rate``,
+    ``next = eps``, ``nneg = epn``."""
+    w = np.asarray(w, _F32)
+    eps = (_F32(w.max()) / w).astype(_F32)
+    epn = (eps / _F32(negative_sample_rate)).astype(_F32)
+    return {"eps": eps, "epn": epn, "next": eps.copy(), "nneg": epn.copy()}
+
+
+def mix(x):
+    """The 32-bit mixer of the negative sampler (uint32 in, uint32 out; arrays or scalars)."""
+    x = np.asarray(x, np.uint32).copy()
+    x ^= x >> np.uint32(16)
+    x *= np.uint32(0x7FEB352D)
+    x ^= x >> np.uint32(15)
+    x *= np.uint32(0x846CA68B)
+    x ^= x >> np.uint32(16)
+    return x
+
+
+def negative_vertex(e, seed: int, ep: int, p: int, n: int):
+    """``mix(mix(mix(e ^ seed) + ep) + p) % n`` on uint32."""
+    with np.errstate(over="ignore"):
+        r = mix(mix(mix(np.asarray(e, np.uint32) ^ np.uint32(seed & 0xFFFFFFFF)) + np.uint32(ep)) + np.uint32(p))
+    return (r % np.uint32(n)).astype(np.int64)
+
+
+def epoch_alpha(ep: int, n_epochs: int, lr: float = 1.0) -> np.float32:
+    """``lr`` rounded to float32, the product in float64, rounded to float32."""
+    return _F32(float(_F32(lr)) * (1.0 - ep / n_epochs))
+
+
+def layout_epoch(Y: np.ndarray, graph, state: dict, ep: int, n_epochs: int, a: float, b: float, seed: int,
+                 gamma: float = 1.0, lr: float = 1.0, dtype=np.float32, return_counts: bool = False):
+    """ONE synchronous epoch: ``Y [n, 2]`` -> new ``Y`` (in ``dtype``) and the new state.  ``a``, ``b``,
+    ``gamma`` and ``alpha`` enter rounded to float32; forces are evaluated in ``dtype`` (``d2^(b-1)`` as
+    ``d2^b / d2``); the schedule is float32 whatever ``dtype`` is."""
+    row_ptr, col, _ = graph
+    n = Y.shape[0]
+    dt = np.dtype(dtype).type
+    Yd = np.asarray(Y).astype(dt)
+    a, b, gamma = dt(_F32(a)), dt(_F32(b)), dt(_F32(gamma))
+    alpha = dt(epoch_alpha(ep, n_epochs, lr))
+    head = np.repeat(np.arange(n, dtype=np.int64), np.diff(row_ptr))
+    epf = _F32(ep)
+    eps, epn, nxt, nneg = (np.asarray(state[s], _F32) for s in ("eps", "epn", "next", "nneg"))
+    act = np.nonzero(nxt <= epf)[0]
+    delta = np.zeros((n, 2), dt)
+    four = dt(4)
+
+    def clip(v):
+        return np.clip(v, -four, four)
+
+    j = head[act]
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        d = Yd[j] - Yd[col[act]]
+        d2 = d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]
+        pw = np.power(d2, b)
+        c = np.where(d2 > 0, dt(-2) * a * b * (pw / d2) / (a * pw + dt(1)), dt(0))
+        np.add.at(delta, j, dt(2) * clip(c[:, None] * d) * alpha)
+        m = np.maximum(((epf - nneg[act]).astype(_F32) / epn[act]).astype(_F32).astype(np.int64), 0)
+        for p in range(int(m.max()) if m.size else 0):
+            sel = m > p
+            e, js = act[sel], j[sel]
+            v = negative_vertex(e, seed, ep, p, n)
+            d = Yd[js] - Yd[v]
+            d2 = d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]
+            pw = np.power(d2, b)
+            c = dt(2) * gamma * b / ((dt(0.001) + d2) * (a * pw + dt(1)))
+            ok = (v != js) & (d2 > 0)
+            np.add.at(delta, js[ok], clip(c[ok, None] * d[ok]) * alpha)
+    new = {"eps": eps, "epn": epn, "next": nxt.copy(), "nneg": nneg.copy()}
+    new["next"][act] = (nxt[act] + eps[act]).astype(_F32)
+    new["nneg"][act] = (nneg[act] + (m.astype(_F32) * epn[act]).astype(_F32)).astype(_F32)
+    out = (Yd + delta).astype(dt)
+    if return_counts:
+        full = np.zeros(nxt.size, np.int64)
+        full[act] = m
+        return out, new, full
+    return out, new
+
+
+def umap_layout(Y0: np.ndarray, graph, n_epochs: int, a: float, b: float, seed: int = 42, gamma: float = 1.0,
+                lr: float = 1.0, negative_sample_rate: int = 5, dtype=np.float32, stop: int | None = None,
+                return_state: bool = False):
+    """The loop over ``ep = 0 .. n_epochs - 1`` (``stop``: return what epoch ``stop`` would read)."""
+    Y = np.asarray(Y0).astype(dtype)
+    st = layout_state(graph[2], negative_sample_rate)
+    for ep in range(n_epochs if stop is None else stop):
+        Y, st = layout_epoch(Y, graph, st, ep, n_epochs, a, b, seed, gamma, lr, dtype)
+    return (Y, st) if return_state else Y
+
+
+def pca_init(x: np.ndarray) -> np.ndarray:
+    """The first two principal axes, each column of V signed so that its largest-magnitude entry is
+    positive, each axis mapped affinely to [0, 10] -> float32 [n, 2]."""
+    x = np.asarray(x, np.float64)
+    xc = x - x.mean(0, keepdims=True)
+    evals, evecs = np.linalg.eigh(xc.T @ xc)
+    V = evecs[:, ::-1][:, :2]
+    V = V * np.sign(V[np.abs(V).argmax(0), np.arange(2)])[None, :]
+    p = xc @ V
+    lo, hi = p.min(0), p.max(0)
+    return (10.0 * (p - lo) / np.where(hi > lo, hi - lo, 1.0)).astype(_F32)
+
+
+def umap_fit(x: np.ndarray, params=None, dtype=np.float32) -> np.ndarray:
+    """Everything chained: table, graph, PCA initialisation (or ``params.init`` as an ``[n, 2]`` array),
+    layout.  ``params`` is a ``search.umap.UMAPParams`` (defaults when None) -> float32 ``[n, 2]``."""
+    if params is None:
+        from .umap import UMAPParams
+
+        params = UMAPParams()
+    x = np.asarray(x)
+    check_umap_limits(x.shape[0], params.n_neighbors, params.metric)
+    if not np.isfinite(x).all():
+        raise ValueError("non-finite input")
+    n = x.shape[0]
+    n_epochs = params.n_epochs or default_n_epochs(n)
+    a, b = umap_ab(params.spread, params.min_dist)
+    idx, dist = knn_table(x, params.n_neighbors, params.metric)
+    graph = fuzzy_graph(idx, dist, n_epochs)
+    if isinstance(params.init, str):
+        if params.init != "pca":
+            raise ValueError('init must be "pca" or an [n, 2] array')
+        Y0 = pca_init(x)
+    else:
+        Y0 = np.asarray(params.init, _F32)
+        if Y0.shape != (n, 2):
+            raise ValueError("init array must be [n, 2]")
+    Y = umap_layout(Y0, graph, n_epochs, a, b, params.seed, params.repulsion_strength, params.learning_rate,
+                    params.negative_sample_rate, dtype)
+    return np.asarray(Y, _F32)
+
+
+def check_umap_limits(n: int, n_neighbors: int, metric: str = "cosine") -> None:
+    if metric not in UMAP_METRICS:
+        raise ValueError(f"metric must be one of {UMAP_METRICS}")
+    if not 2 <= n_neighbors <= 64:
+        raise ValueError("n_neighbors must be in 2..64")
+    if n <= n_neighbors:
+        raise ValueError(f"need more points ({n}) than n_neighbors ({n_neighbors})")
+    if n >= 2 ** 31 // n_neighbors:
+        raise ValueError("too many points: n * n_neighbors must stay below 2^31")

@@ -62,7 +62,10 @@ HIP_FLAGS = [
 # (profiles/r05/conv/pp_noslp_ab: stem -18 %, 32->32 -7.5 %, 64->32 up -9 %, headline +1.5 %)
 PER_SOURCE_FLAGS = {"clahe": ["-ffp-contract=off"], "attention": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
                     "gemm_mt": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"], "conv_pair": ["-fno-slp-vectorize"],
-                    "conv_pp128": ["-fno-slp-vectorize"]}  # conv_pp128: the same phase scheme as conv_pair
+                    "conv_pp128": ["-fno-slp-vectorize"],  # conv_pp128: the same phase scheme as conv_pair
+                    # umap: the layout schedule (nneg + m * epn) must round the product on its own, as the float32
+                    # oracle does; __fmul_rn / __fadd_rn are plain operators to hipcc and were fused into v_fmac_f32
+                    "umap": ["-ffp-contract=off"]}
 CXX_FLAGS = ["-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-pthread", "-I", str(CSRC / "runtime")]
 
 
