@@ -4,8 +4,8 @@ API parity with the reference app ``apps/cell-image-search/main.py`` (``CellImag
 ``:1033-1519``): ping, get_index_stats, list_datasets, add_dataset, add_jump_cp_dataset,
 remove_dataset, start_ingestion, get_ingestion_status, stop_ingestion, get_active_sessions, search,
 get_umap_preview, project_query_onto_umap, enrich_metadata_with_compounds — plus
-``add_synthetic_dataset`` / ``add_local_dataset`` for offline deployments and ``search`` by raw
-array or precomputed embedding.
+``add_synthetic_dataset`` / ``add_local_dataset`` for offline deployments, ``search`` by raw
+array or precomputed embedding and ``project_embeddings_onto_umap`` (the UMAP transform of a batch).
 
 Everything heavy runs through ``bioengine_worker_amd.search``: GPU nucleus detection (Otsu +
 union-find CCL kernels), batched percentile-stretch / PIL-bicubic / ImageNet normalisation kernels,
@@ -567,9 +567,12 @@ class CellImageSearch:
 
     @schema_method
     async def get_umap_preview(self, n_samples: int = Field(10_000, ge=100, le=100_000), color_by: str = Field("compound"),
-                               force_recompute: bool = Field(False), method: str = Field("auto")) -> dict:
+                               force_recompute: bool = Field(False), method: str = Field("auto"),
+                               extend_to: int = Field(0, ge=0, le=1_000_000)) -> dict:
         """2-D projection of a sample of indexed cells.  ``method``: "auto" (umap-learn if installed, else the
-        in-house GPU UMAP on a GPU worker, else PCA), "umap" (the in-house UMAP) or "pca"."""
+        in-house GPU UMAP on a GPU worker, else PCA), "umap" (the in-house UMAP) or "pca".  ``extend_to`` above
+        ``n_samples`` places further indexed cells on the fitted landscape (the UMAP transform) up to that many
+        points; the result then carries ``n_fitted`` and ``placement``."""
         from bioengine_worker_amd.search.ingestion import index_dir
         from bioengine_worker_amd.search.projection import compute_projection
 
@@ -578,11 +581,19 @@ class CellImageSearch:
             labels = self._metadata_df[color_by].astype(str).tolist()
         cache = index_dir(self._workspace_dir) / f"umap_cache_{color_by}.npz"
         return await asyncio.to_thread(compute_projection, self._index, labels, cache, n_samples, 42, force_recompute,
-                                       "", method)
+                                       "", method, extend_to)
+
+    def _umap_cache(self):
+        from bioengine_worker_amd.search.ingestion import index_dir
+
+        return index_dir(self._workspace_dir) / "umap_cache_compound.npz"
 
     @schema_method
-    async def project_query_onto_umap(self, image_b64: str = Field(..., description="Base64 query image.")) -> dict:
-        """Place a query on the projection at its nearest indexed neighbour."""
+    async def project_query_onto_umap(self, image_b64: str = Field(..., description="Base64 query image."),
+                                      placement: str = Field("nearest")) -> dict:
+        """Place a query on the projection.  ``placement``: "nearest" (on a sampled cell near its nearest indexed
+        neighbour), "auto" (the UMAP transform of the query where the landscape has one, else "nearest") or
+        "transform" (an error where "auto" would fall back); the latter two add a ``placement`` key saying how."""
         if self._index is None:
             return {"error": "No index loaded."}
         q, _ = await self._embed_query(_decode_image_b64(image_b64), 1.0, 99.0)
@@ -590,13 +601,39 @@ class CellImageSearch:
         proj = await self.get_umap_preview()
         nn = int(I[0, 0])
         x = y = 0.0
-        if nn >= 0 and proj["sample_idx"]:
+        how = None
+        if placement != "nearest" and proj["sample_idx"]:
+            from bioengine_worker_amd.search.projection import place_points
+
+            xy, how = await asyncio.to_thread(place_points, self._index, self._umap_cache(), np.asarray(q)[None], placement)
+            x, y = xy[0]
+        elif nn >= 0 and proj["sample_idx"]:
             sidx = np.asarray(proj["sample_idx"])
             j = int(np.argmin(np.abs(sidx - nn)))
             x, y = proj["x"][j], proj["y"][j]
         meta = self._metadata_df.iloc[nn].to_dict() if self._metadata_df is not None and nn >= 0 else {}
-        return {"umap_x": float(x), "umap_y": float(y), "nearest_score": float(S[0, 0]),
-                "nearest_compound": meta.get("compound", "unknown"), "nearest_moa": meta.get("moa_class", "unknown")}
+        out = {"umap_x": float(x), "umap_y": float(y), "nearest_score": float(S[0, 0]),
+               "nearest_compound": meta.get("compound", "unknown"), "nearest_moa": meta.get("moa_class", "unknown")}
+        if placement != "nearest":
+            out["placement"] = how or "nearest"
+        return out
+
+    @schema_method
+    async def project_embeddings_onto_umap(self, embeddings: list = Field(..., description="Up to 10,000 768-d vectors."),
+                                           placement: str = Field("auto")) -> dict:
+        """Place precomputed embeddings on the projection in one call -> ``x``, ``y``, ``placement``."""
+        if self._index is None:
+            return {"error": "No index loaded."}
+        vecs = np.asarray(embeddings, np.float32)
+        if vecs.ndim != 2 or not 1 <= len(vecs) <= 10_000 or vecs.shape[1] != self._index.dim:
+            return {"error": f"embeddings must be [1..10000, {self._index.dim}]"}
+        proj = await self.get_umap_preview()
+        if not proj["sample_idx"]:
+            return {"error": "The index is empty."}
+        from bioengine_worker_amd.search.projection import place_points
+
+        xy, how = await asyncio.to_thread(place_points, self._index, self._umap_cache(), vecs, placement)
+        return {"x": xy[:, 0].tolist(), "y": xy[:, 1].tolist(), "placement": how}
 
     @schema_method
     async def enrich_metadata_with_compounds(self, lookup_csv: str = Field("", description=(

@@ -19,6 +19,22 @@ Deliberate departures from umap-learn:
 Precision: the neighbour table, the bisection and the memberships take a ``dtype`` (float64 is the
 rule, float32 the yardstick the GPU tests measure rounding with); the symmetric weights and the whole
 schedule state are float32 with every operation rounded on its own.
+
+UMAP ``transform`` of new points onto a fitted layout (third part of the file; ``umap_transform``), again
+from memory of umap-learn 0.5 and never compared with it.  Every rule is PER QUERY, so a query's result
+depends on nothing else in its batch.  Deliberate departures, beside the synchronous epoch above:
+
+4. ``rho`` is the row's minimum distance, zero included (umap-learn: ``rho = 0``), all ``k`` columns are
+   summed in the bisection (umap-learn skips column 0), and the floor of ``sigma`` is 1e-3 of the row's
+   own mean (umap-learn: of the mean over the whole query batch, which ties a result to its batch).
+   ``rho = min`` instead of "smallest positive" keeps the rule continuous when a query duplicates an
+   indexed point and a float32 GEMM returns ``1e-8`` instead of ``0``.  The nearest training point always
+   has membership exactly 1.
+5. A slot is pruned when ``w < 1 / E``: umap-learn's ``max / n_epochs`` with the row maximum (always 1)
+   in place of the batch-wide maximum.
+6. ``E`` is 100 whatever the number of queries (umap-learn: 100 or 30 by batch size).
+7. The negative samples of a query are keyed by its nearest training point and the slot, not by the
+   query's place in the batch.
 """
 from __future__ import annotations
 
@@ -436,3 +452,218 @@ def check_umap_limits(n: int, n_neighbors: int, metric: str = "cosine") -> None:
         raise ValueError(f"need more points ({n}) than n_neighbors ({n_neighbors})")
     if n >= 2 ** 31 // n_neighbors:
         raise ValueError("too many points: n * n_neighbors must stay below 2^31")
+
+
+# ---------------------------------------------------------------------------------------------------
+# UMAP transform: new points onto a fitted layout (oracle of search/umap.py's umap_transform_gpu)
+# ---------------------------------------------------------------------------------------------------
+TRANSFORM_EPOCHS = 100
+TRANSFORM_MAX_DRAWS = 4096  # negative samples of one slot in one epoch; unreachable from a schedule run from its start
+
+
+def transform_n_epochs(params=None) -> int:
+    """``params.transform_epochs``, 100 when None: never a function of the number of queries."""
+    e = getattr(params, "transform_epochs", None)
+    e = TRANSFORM_EPOCHS if e is None else int(e)
+    if e < 1:
+        raise ValueError("transform_epochs must be at least 1")
+    return e
+
+
+def check_transform_limits(m: int, n: int, k: int, metric: str = "cosine") -> None:
+    if metric not in UMAP_METRICS:
+        raise ValueError(f"metric must be one of {UMAP_METRICS}")
+    if not 1 <= k <= 64:
+        raise ValueError("n_neighbors must be in 1..64")
+    if k > n:
+        raise ValueError(f"need at least n_neighbors ({k}) training points, not {n}")
+    if n >= 2 ** 31 // 64 or m >= 2 ** 31 // k:
+        raise ValueError("too many points: n * 64 and m * n_neighbors must stay below 2^31")
+
+
+def knn_query_table(q: np.ndarray, x: np.ndarray, k: int, metric: str = "cosine", dtype=np.float64):
+    """``q [m, d]`` against the training rows ``x [n, d]`` -> ``idx [m, k]`` int32, ``dist [m, k]`` float32: the
+    ``k`` nearest training rows, ascending (ties by index).  No self column: a query is not a training row.
+    The distance formulas are ``knn_table``'s."""
+    q, x = np.asarray(q, dtype), np.asarray(x, dtype)
+    if q.ndim != 2 or x.ndim != 2 or q.shape[1] != x.shape[1]:
+        raise ValueError(f"q {q.shape} and x {x.shape} must be [m, d] and [n, d]")
+    check_transform_limits(q.shape[0], x.shape[0], k, metric)
+    if not (np.isfinite(q).all() and np.isfinite(x).all()):
+        raise ValueError("non-finite input")
+    if metric == "cosine":
+        qn, xn = np.sqrt((q * q).sum(1)), np.sqrt((x * x).sum(1))
+        if (qn == 0).any() or (xn == 0).any():
+            raise ValueError("cosine metric: zero-norm row")
+        d = np.maximum(0, 1 - (q / qn[:, None]) @ (x / xn[:, None]).T)
+    else:
+        d = np.sqrt(np.maximum(0, (q * q).sum(1)[:, None] + (x * x).sum(1)[None, :] - 2 * (q @ x.T)))
+    order = np.argsort(d, axis=1, kind="stable")[:, :k]
+    return order.astype(np.int32), np.take_along_axis(d, order, 1).astype(_F32).reshape(q.shape[0], k)
+
+
+def smooth_knn_query(dist: np.ndarray, dtype=np.float64, n_iter: int = 64):
+    """``dist [m, k]`` (no self column) -> ``rho [m]``, ``sigma [m]`` in ``dtype``.  ``rho_i`` is the row's minimum,
+    zero included; ``sigma_i`` the bisection of ``smooth_knn`` over ALL k columns towards ``log2(k)``, floored at
+    1e-3 of the row's own mean."""
+    d = np.asarray(dist, _F32).astype(dtype)
+    m, k = d.shape
+    one = dtype(1)
+    target = dtype(np.log2(dtype(k)))
+    rho = np.zeros(m, dtype)
+    sigma = np.zeros(m, dtype)
+    for i in range(m):
+        row = d[i]
+        r = row.min()
+        gap = row - r
+        lo, hi, mid = dtype(0), dtype(np.inf), one
+        for _ in range(n_iter):
+            psum = np.where(gap > 0, np.exp(-(np.maximum(gap, 0) / mid)), one).sum(dtype=dtype)
+            if abs(psum - target) < SMOOTH_K_TOLERANCE:
+                break
+            if psum > target:
+                hi = mid
+                mid = (lo + hi) / dtype(2)
+            else:
+                lo = mid
+                mid = mid * dtype(2) if np.isinf(hi) else (lo + hi) / dtype(2)
+        rho[i] = r
+        sigma[i] = max(mid, dtype(MIN_K_DIST_SCALE) * row.mean(dtype=dtype))
+    return rho, sigma
+
+
+def memberships_query(dist: np.ndarray, rho: np.ndarray, sigma: np.ndarray) -> np.ndarray:
+    """``w [m, k]`` (float32), computed in ``rho.dtype``: 1 where ``d - rho <= 0`` or ``sigma == 0``, else
+    ``exp(-(d - rho) / sigma)``.  Not symmetrised: these are the edge weights of the transform."""
+    dt = rho.dtype.type
+    gap = np.asarray(dist, _F32).astype(dt) - rho[:, None]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        w = np.where((gap <= 0) | (sigma[:, None] == 0), dt(1), np.exp(-(np.maximum(gap, 0) / sigma[:, None])))
+    return w.astype(_F32)
+
+
+def transform_state(w: np.ndarray, n_epochs: int, negative_sample_rate: int = 5) -> dict:
+    """Per slot, float32, as ``layout_state`` with the row maximum 1: ``eps = 1 / w``, ``epn = eps /
+    negative_sample_rate``, ``next = eps``, ``nneg = epn``; ``live`` is False where ``w < 1 / n_epochs`` (such a
+    slot never fires)."""
+    w = np.asarray(w, _F32)
+    with np.errstate(divide="ignore"):
+        eps = (_F32(1) / w).astype(_F32)
+        epn = (eps / _F32(negative_sample_rate)).astype(_F32)
+    return {"eps": eps, "epn": epn, "next": eps.copy(), "nneg": epn.copy(), "live": w >= _F32(1) / _F32(n_epochs)}
+
+
+def transform_init(idx: np.ndarray, w: np.ndarray, Y_train: np.ndarray) -> np.ndarray:
+    """The start of a query: the mean of its neighbours' training positions weighted by ``w`` over all k slots
+    (the later pruned ones included), summed in float64 -> float32 ``[m, 2]``."""
+    w64 = np.asarray(w, _F32).astype(np.float64)
+    Yn = np.asarray(Y_train, _F32).astype(np.float64)[np.asarray(idx, np.int64)]
+    return ((w64[:, :, None] * Yn).sum(1) / w64.sum(1)[:, None]).astype(_F32)
+
+
+def transform_key(idx: np.ndarray) -> np.ndarray:
+    """The sampler key of every slot, ``uint32(idx[i, 0]) * 64 + slot``: intrinsic to the query."""
+    idx = np.asarray(idx)
+    return (idx[:, :1].astype(np.uint32) * np.uint32(64) + np.arange(idx.shape[1], dtype=np.uint32)[None, :]).astype(np.uint32)
+
+
+def transform_epoch(Y: np.ndarray, Y_train: np.ndarray, idx: np.ndarray, state: dict, ep: int, n_epochs: int, a: float,
+                    b: float, seed: int, gamma: float = 1.0, lr: float = 1.0, dtype=np.float32,
+                    return_counts: bool = False):
+    """ONE synchronous epoch of the transform: ``layout_epoch`` where only the queries ``Y [m, 2]`` move and the
+    training positions are fixed.  The attractive term carries factor 1 (the edge exists in one direction),
+    ``alpha = epoch_alpha(ep, n_epochs, float32(lr) / 4)``, a negative sample is the TRAINING vertex
+    ``negative_vertex(transform_key, seed, ep, p, n_train)``, skipped at ``d2 == 0``; there is no self to exclude."""
+    dt = np.dtype(dtype).type
+    Yd = np.asarray(Y).astype(dt)
+    Yt = np.asarray(Y_train, _F32).astype(dt)
+    n = Yt.shape[0]
+    idx = np.asarray(idx, np.int64)
+    m, k = idx.shape
+    a, b, gamma = dt(_F32(a)), dt(_F32(b)), dt(_F32(gamma))
+    alpha = dt(epoch_alpha(ep, n_epochs, _F32(lr) / _F32(4)))
+    epf = _F32(ep)
+    eps, epn, nxt, nneg = (np.asarray(state[s], _F32).reshape(-1) for s in ("eps", "epn", "next", "nneg"))
+    head = np.repeat(np.arange(m, dtype=np.int64), k)
+    col = idx.reshape(-1)
+    key = transform_key(idx).reshape(-1)
+    act = np.nonzero(np.asarray(state["live"], bool).reshape(-1) & (nxt <= epf))[0]
+    delta = np.zeros((m, 2), dt)
+    four = dt(4)
+
+    def clip(v):
+        return np.clip(v, -four, four)
+
+    j = head[act]
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        d = Yd[j] - Yt[col[act]]
+        d2 = d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]
+        pw = np.power(d2, b)
+        c = np.where(d2 > 0, dt(-2) * a * b * (pw / d2) / (a * pw + dt(1)), dt(0))
+        np.add.at(delta, j, clip(c[:, None] * d) * alpha)
+        cnt = np.maximum(((epf - nneg[act]).astype(_F32) / epn[act]).astype(_F32).astype(np.int64), 0)
+        cnt = np.minimum(cnt, TRANSFORM_MAX_DRAWS)
+        for p in range(int(cnt.max()) if cnt.size else 0):
+            sel = cnt > p
+            js = j[sel]
+            v = negative_vertex(key[act[sel]], seed, ep, p, n)
+            d = Yd[js] - Yt[v]
+            d2 = d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]
+            pw = np.power(d2, b)
+            c = dt(2) * gamma * b / ((dt(0.001) + d2) * (a * pw + dt(1)))
+            ok = d2 > 0
+            np.add.at(delta, js[ok], clip(c[ok, None] * d[ok]) * alpha)
+    new_next, new_nneg = nxt.copy(), nneg.copy()
+    new_next[act] = (nxt[act] + eps[act]).astype(_F32)
+    new_nneg[act] = (nneg[act] + (cnt.astype(_F32) * epn[act]).astype(_F32)).astype(_F32)
+    new = {"eps": state["eps"], "epn": state["epn"], "live": state["live"], "next": new_next.reshape(m, k),
+           "nneg": new_nneg.reshape(m, k)}
+    out = (Yd + delta).astype(dt)
+    if return_counts:
+        full = np.zeros(m * k, np.int64)
+        full[act] = cnt
+        return out, new, full.reshape(m, k)
+    return out, new
+
+
+def umap_transform_layout(Y0: np.ndarray, Y_train: np.ndarray, idx: np.ndarray, w: np.ndarray, n_epochs: int, a: float,
+                          b: float, seed: int = 42, gamma: float = 1.0, lr: float = 1.0, negative_sample_rate: int = 5,
+                          dtype=np.float32, stop: int | None = None, return_state: bool = False):
+    """The loop over ``ep = 0 .. n_epochs - 1`` (``stop``: return what epoch ``stop`` would read)."""
+    Y = np.asarray(Y0).astype(dtype)
+    st = transform_state(w, n_epochs, negative_sample_rate)
+    for ep in range(n_epochs if stop is None else stop):
+        Y, st = transform_epoch(Y, Y_train, idx, st, ep, n_epochs, a, b, seed, gamma, lr, dtype)
+    return (Y, st) if return_state else Y
+
+
+def umap_transform(q: np.ndarray, x_train: np.ndarray, Y_train: np.ndarray, params=None, dtype=np.float32) -> np.ndarray:
+    """New points ``q [m, d]`` onto the layout ``Y_train [n, 2]`` of ``x_train [n, d]``: query table, smooth-kNN,
+    memberships, weighted-mean start, layout.  ``params`` is a ``search.umap.UMAPParams`` (defaults when None);
+    ``dtype`` is the precision of the forces (table and memberships follow the float64 rule) -> float32 ``[m, 2]``."""
+    if params is None:
+        from .umap import UMAPParams
+
+        params = UMAPParams()
+    q, x_train = np.asarray(q), np.asarray(x_train)
+    Y_train = np.asarray(Y_train, _F32)
+    if q.ndim != 2 or x_train.ndim != 2 or q.shape[1] != x_train.shape[1]:
+        raise ValueError(f"q {q.shape} and x_train {x_train.shape} must be [m, d] and [n, d]")
+    if Y_train.shape != (x_train.shape[0], 2):
+        raise ValueError("Y_train must be [n, 2]")
+    n_epochs = transform_n_epochs(params)
+    check_transform_limits(q.shape[0], x_train.shape[0], params.n_neighbors, params.metric)
+    if not np.isfinite(Y_train).all():
+        raise ValueError("non-finite training positions")
+    if q.shape[0] == 0:
+        if not np.isfinite(x_train).all():
+            raise ValueError("non-finite input")
+        return np.zeros((0, 2), _F32)
+    a, b = umap_ab(params.spread, params.min_dist)
+    idx, dist = knn_query_table(q, x_train, params.n_neighbors, params.metric)
+    rho, sigma = smooth_knn_query(dist)
+    w = memberships_query(dist, rho, sigma)
+    Y0 = transform_init(idx, w, Y_train)
+    Y = umap_transform_layout(Y0, Y_train, idx, w, n_epochs, a, b, params.seed, params.repulsion_strength,
+                              params.learning_rate, params.negative_sample_rate, dtype)
+    return np.asarray(Y, _F32)

@@ -11,6 +11,16 @@ compared with it; its departures are listed there).  Stages:
   arrays.  One host read (the edge count).
 * :func:`layout_gpu` — ``be_umap_layout``: all epochs queued back to back, one launch per epoch, positions
   ping-ponging between two buffers; no host read, no allocation and no synchronisation in between.
+
+New points onto a fitted layout (:func:`umap_transform_gpu`; the rules are ``reference.umap_transform``'s, every
+one of them per query):
+
+* :func:`knn_query_table_gpu` — torch: score blocks of query rows against the training set, ``topk``.
+* :func:`smooth_knn_query_gpu` — ``be_umap_smooth_knn_query``: rho (the row minimum), sigma and the ``k``
+  memberships, which are the edge weights.
+* :func:`transform_init_gpu` — torch: the weighted mean of the neighbours' training positions.
+* :func:`transform_layout_gpu` — ``be_umap_transform``: all epochs in ONE launch; a query's position and
+  schedule stay in the registers of its 16 lanes.
 """
 from __future__ import annotations
 
@@ -37,6 +47,7 @@ class UMAPParams:
     repulsion_strength: float = 1.0
     seed: int = 42
     init: Any = "pca"
+    transform_epochs: int | None = None  # of umap_transform_gpu; None: 100, whatever the number of queries
 
 
 def _seed32(seed: int) -> int:
@@ -257,3 +268,162 @@ def _mark(dev):
     ev = torch.cuda.Event(enable_timing=True)
     ev.record(torch.cuda.current_stream(dev))
     return ev
+
+
+# ------------------------------------------------------------------------------------------- transform
+TRANSFORM_CHUNK = 1 << 17  # queries per pass of umap_transform_gpu; no rule looks beyond its own row
+
+
+def knn_query_table_gpu(q: torch.Tensor, x: torch.Tensor, k: int, metric: str = "cosine", budget: int = 1 << 30):
+    """``q [m, d]`` against the training rows ``x [n, d]`` -> ``idx [m, k]`` int32, ``dist [m, k]`` float32 as
+    ``reference.knn_query_table``: the ``k`` nearest training rows, ascending, no self column.  Score blocks of
+    ``budget // n`` query rows; an ``m x n`` matrix is never materialised."""
+    if q.dim() != 2 or x.dim() != 2 or q.shape[1] != x.shape[1]:
+        raise ValueError(f"q {tuple(q.shape)} and x {tuple(x.shape)} must be [m, d] and [n, d]")
+    m, n = q.shape[0], x.shape[0]
+    ref.check_transform_limits(m, n, k, metric)
+    q, x = q.float(), x.float()
+    if metric == "cosine":
+        q = q / q.norm(dim=1, keepdim=True)
+        x = x / x.norm(dim=1, keepdim=True)
+    else:
+        sq, sx = (q * q).sum(1), (x * x).sum(1)
+    rows = max(1, min(max(m, 1), budget // n))
+    idx = torch.empty(m, k, dtype=torch.int32, device=q.device)
+    dist = torch.empty(m, k, dtype=torch.float32, device=q.device)
+    xt = x.T
+    for i in range(0, m, rows):
+        s = torch.mm(q[i:i + rows], xt)
+        if metric == "cosine":
+            d = (1.0 - s).clamp_(min=0.0)
+        else:
+            d = (sq[i:i + rows, None] + sx[None, :] - 2.0 * s).clamp_(min=0.0).sqrt_()
+        td, ti = torch.topk(d, k, dim=1, largest=False, sorted=True)
+        idx[i:i + rows] = ti.int()
+        dist[i:i + rows] = td
+    return idx, dist
+
+
+def smooth_knn_query_gpu(dist: torch.Tensor):
+    """``dist [m, k]`` (no self column) -> ``rho [m]``, ``sigma [m]``, memberships ``[m, k]`` (float32) as
+    ``reference.smooth_knn_query`` / ``memberships_query``: ``be_umap_smooth_knn_query``."""
+    m, k = dist.shape
+    if not 1 <= k <= 64:
+        raise ValueError("n_neighbors must be in 1..64")
+    if not dist.is_cuda:
+        raise _native.NativeUnavailable("be_umap_smooth_knn_query needs a GPU tensor")
+    dist = dist.float().contiguous()
+    rho = torch.empty(m, dtype=torch.float32, device=dist.device)
+    sigma = torch.empty_like(rho)
+    memb = torch.empty(m, k, dtype=torch.float32, device=dist.device)
+    _native.call("be_umap_smooth_knn_query", _native.ptr(dist), m, k, _native.ptr(rho), _native.ptr(sigma),
+                 _native.ptr(memb), _native.stream(dist.device))
+    return rho, sigma, memb
+
+
+def transform_init_gpu(idx: torch.Tensor, w: torch.Tensor, Y_train: torch.Tensor) -> torch.Tensor:
+    """``reference.transform_init``: the ``w``-weighted mean of the neighbours' training positions, in fp64."""
+    w64 = w.double()
+    Yn = Y_train.double()[idx.long()]
+    return ((w64[:, :, None] * Yn).sum(1) / w64.sum(1, keepdim=True)).float().contiguous()
+
+
+def transform_layout_gpu(Y: torch.Tensor, Y_train: torch.Tensor, idx: torch.Tensor, w: torch.Tensor, n_epochs: int,
+                         a: float, b: float, seed: int = 42, gamma: float = 1.0, lr: float = 1.0,
+                         negative_sample_rate: int = 5, ep0: int = 0, ep1: int | None = None,
+                         state: dict | None = None) -> torch.Tensor:
+    """``be_umap_transform``: epochs ``ep0 .. ep1 - 1`` of ``n_epochs`` in ONE launch.  ``Y [m, 2]`` holds the start
+    and is updated in place (and returned); ``state`` (``next`` / ``nneg`` ``[m, k]``) is read and written when
+    given, else the run starts from the initial schedule, which needs ``ep0 == 0``."""
+    m, k = idx.shape
+    n = Y_train.shape[0]
+    ep1 = n_epochs if ep1 is None else ep1
+    if not 1 <= k <= 64:
+        raise ValueError("n_neighbors must be in 1..64")
+    if state is None and ep0 != 0:
+        raise ValueError("a run that does not start at epoch 0 needs its schedule state")
+    if not 0 <= ep0 <= ep1 <= n_epochs:
+        raise ValueError("need 0 <= ep0 <= ep1 <= n_epochs")
+    if negative_sample_rate < 1 or n < 1:
+        raise ValueError("negative_sample_rate and the training set must be at least 1")
+    if not (Y.is_cuda and Y_train.is_cuda and idx.is_cuda and w.is_cuda):
+        raise _native.NativeUnavailable("the UMAP transform kernel needs GPU tensors")
+    assert Y.dtype == torch.float32 and Y.shape == (m, 2) and Y.is_contiguous()
+    assert Y_train.dtype == torch.float32 and Y_train.shape == (n, 2) and Y_train.is_contiguous()
+    assert idx.dtype == torch.int32 and idx.is_contiguous()
+    assert w.dtype == torch.float32 and w.shape == (m, k) and w.is_contiguous()
+    nxt = nng = None
+    if state is not None:
+        nxt, nng = state["next"], state["nneg"]
+        for t in (nxt, nng):
+            assert t.is_cuda and t.dtype == torch.float32 and t.shape == (m, k) and t.is_contiguous()
+    _native.call("be_umap_transform", _native.ptr(Y_train), n, _native.ptr(idx), _native.ptr(w), m, k, _native.ptr(Y),
+                 _native.ptr(nxt), _native.ptr(nng), ep0, ep1, n_epochs, lr, a, b, gamma, int(negative_sample_rate),
+                 _seed32(seed), _native.stream(Y.device))
+    return Y
+
+
+def umap_transform_gpu(q, x_train, Y_train, params: UMAPParams | None = None, device=None):
+    """New points ``q [m, d]`` onto the layout ``Y_train [n, 2]`` of ``x_train [n, d]`` (``reference.umap_transform``)
+    -> ``(coords float32 [m, 2] on the device, info)``.  ``info``: ``n_epochs`` and ``spans_ms`` (device time of
+    ``knn``, ``smooth_knn``, ``init``, ``layout``, summed over the chunks).  Queries go through in chunks of
+    ``TRANSFORM_CHUNK`` rows (a host array is uploaded chunk by chunk); every rule is per row, so from the
+    neighbour table onward the chunking cannot change a result."""
+    p = params or UMAPParams()
+    if not _native.hip_available():
+        raise _native.NativeUnavailable("umap_transform_gpu needs a GPU and the native kernel library")
+    dev = torch.device(device) if device is not None else next(
+        (t.device for t in (q, x_train, Y_train) if torch.is_tensor(t) and t.is_cuda), torch.device("cuda"))
+
+    def host_or_dev(t):
+        return t if torch.is_tensor(t) else torch.from_numpy(np.ascontiguousarray(np.asarray(t, np.float32)))
+
+    q = host_or_dev(q)
+    x = host_or_dev(x_train).to(dev, torch.float32)
+    Yt = host_or_dev(Y_train).to(dev, torch.float32).contiguous()
+    if q.dim() != 2 or x.dim() != 2 or q.shape[1] != x.shape[1]:
+        raise ValueError(f"q {tuple(q.shape)} and x_train {tuple(x.shape)} must be [m, d] and [n, d]")
+    m, n = q.shape[0], x.shape[0]
+    if Yt.shape != (n, 2):
+        raise ValueError("Y_train must be [n, 2]")
+    n_epochs = ref.transform_n_epochs(p)
+    k = p.n_neighbors
+    ref.check_transform_limits(m, n, k, p.metric)
+
+    def bad(t):
+        ok = torch.isfinite(t).all()
+        if p.metric == "cosine":
+            ok = ok & (t.float().norm(dim=1) > 0).all()
+        return not bool(ok)
+
+    if bad(x) or not bool(torch.isfinite(Yt).all()) or (m and bad(q)):
+        raise ValueError("non-finite input or, under the cosine metric, a zero-norm row")
+    a, b = ref.umap_ab(p.spread, p.min_dist)
+    out = torch.empty(m, 2, dtype=torch.float32, device=dev)
+    spans = {"knn": 0.0, "smooth_knn": 0.0, "init": 0.0, "layout": 0.0}
+    marks = []
+    with torch.cuda.device(dev):
+        for i in range(0, m, TRANSFORM_CHUNK):
+            qc = q[i:i + TRANSFORM_CHUNK].to(dev, torch.float32)
+            ev = [_mark(dev)]
+            with trace.span("umap.transform.knn", cuda=True, m=qc.shape[0], n=n):
+                idx, dist = knn_query_table_gpu(qc, x, k, p.metric)
+            ev.append(_mark(dev))
+            with trace.span("umap.transform.smooth_knn", cuda=True):
+                _, _, w = smooth_knn_query_gpu(dist)
+            ev.append(_mark(dev))
+            with trace.span("umap.transform.init", cuda=True):
+                Y = transform_init_gpu(idx, w, Yt)
+            ev.append(_mark(dev))
+            with trace.span("umap.transform.layout", cuda=True, n_epochs=n_epochs):
+                transform_layout_gpu(Y, Yt, idx, w, n_epochs, a, b, p.seed, p.repulsion_strength, p.learning_rate,
+                                     p.negative_sample_rate)
+                out[i:i + TRANSFORM_CHUNK] = Y
+            ev.append(_mark(dev))
+            marks.append(ev)
+        if marks:
+            marks[-1][-1].synchronize()
+    for ev in marks:
+        for j, name in enumerate(spans):
+            spans[name] += ev[j].elapsed_time(ev[j + 1])
+    return out, {"n_epochs": n_epochs, "spans_ms": {s: round(v, 4) for s, v in spans.items()}}
