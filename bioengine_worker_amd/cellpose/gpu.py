@@ -9,6 +9,8 @@ from __future__ import annotations
 
 import collections
 import ctypes
+import dataclasses
+import enum
 import math
 import os
 
@@ -19,13 +21,8 @@ from ..ops import _native
 from . import reference as ref
 
 RPAD = 20
-_JOB_BYTES = 32
 LDS_DIFFUSE_BYTES = 156 * 1024  # one mask per CU up to ~95 x 95 boxes; larger ones run tiled
 LDS_FILL_BYTES = 32 * 1024
-
-
-def _launch_cfg(n: int):
-    return n
 
 
 # ------------------------------------------------------------------ percentiles / tiles
@@ -560,65 +557,103 @@ def _plan_jobs(bbox_valid, labs_b, labs_l, lds_fn, caps, scratch_fn, valid=None)
     return out, int(host[nb])
 
 
-def _plan_masks(bbox: torch.Tensor, valid: torch.Tensor | None, kind: int, caps):
-    """Device-side :func:`_plan_jobs` (one ``be_cp_plan_masks`` launch + one host sync): returns
-    ``(jobs_by_bucket, scratch_total, niter_img)``; ``kind`` 0 = diffusion (LDS need / scratch of
-    :func:`_diffuse_lds_bytes` / :func:`_diffuse_scratch_doubles`, and cellpose's per-image
-    ``niter_img``), 1 = hole filling (``R`` bytes).  Job order inside a bucket is arbitrary."""
-    return _plan_finish([_plan_launch(bbox, valid, kind, caps)])[0]
+class PlanKind(enum.IntEnum):
+    """``kind`` of ``be_cp_plan_masks``: what a mask needs for the flow-QC diffusion or the hole filling."""
+    DIFFUSE = 0
+    FILL = 1
+    DIFFUSE_QUEUE = 2  # DIFFUSE with the compact work-queue buckets in front (needs pixel counts)
+    FILL_WAVE = 3      # FILL with the one-wave buckets in front
+
+
+#: (kind, pixel counts given) -> the kernel's bucket order, as the fields of :class:`MaskPlan`
+#: (``lds`` = one bucket per LDS cap of the kind); what is not listed cannot be planned
+PLAN_LAYOUT = {
+    (PlanKind.DIFFUSE, False): ("lds", "big"),
+    (PlanKind.DIFFUSE, True): ("lds", "sparse_big", "big"),
+    (PlanKind.DIFFUSE_QUEUE, True): ("queue_wave", "queue_group", "lds", "sparse_big", "big"),
+    (PlanKind.FILL, False): ("lds", "big"),
+    (PlanKind.FILL_WAVE, False): ("wave_small", "wave_big", "lds", "big"),
+}
+
+
+@dataclasses.dataclass
+class MaskPlan:
+    """Jobs of one ``be_cp_plan_masks`` launch by bucket, each [n, 4] int64 (MaskJob rows, order
+    inside a bucket arbitrary); a bucket the kind does not have is empty ([0, 4])."""
+    kind: PlanKind
+    scratch_total: int
+    niter_img: torch.Tensor   # [B] int32, diffusion kinds
+    lds: list                 # one workgroup per mask in LDS: one bucket per cap, smallest first
+    big: torch.Tensor         # beyond LDS, with scratch offsets: tiled diffusion / global-scratch fill
+    sparse_big: torch.Tensor  # diffusion with counts: beyond LDS but sparse, heat field in scratch
+    queue_wave: torch.Tensor  # diffusion queue: wave jobs (<= 256 pixels)
+    queue_group: torch.Tensor  # diffusion queue: workgroup jobs
+    wave_small: torch.Tensor  # one-wave fill: box + ring <= 64 x 64
+    wave_big: torch.Tensor    # one-wave fill: box + ring <= 256 x 128
 
 
 def _plan_finish(launched: list) -> list:
-    """Read back the bucket sizes of several :func:`_plan_launch` plans with ONE host sync."""
-    host = torch.cat([torch.cat([counts.long(), tot]) for _, counts, tot, _ in launched]).cpu().tolist()
+    """Read back the bucket sizes of several :func:`_plan_launch` plans (each one ``be_cp_plan_masks``
+    launch, the device-side :func:`_plan_jobs`) with ONE host sync: a :class:`MaskPlan` for each."""
+    host = torch.cat([torch.cat([nk.long(), tot]) for _, nk, tot, _, _ in launched]).cpu().tolist()
     out, o = [], 0
-    for jobs, counts, _, niter_img in launched:
-        nb = counts.shape[0]
-        out.append(([jobs[k, :host[o + k]] for k in range(nb)], int(host[o + nb]), niter_img))
+    for jobs, nk, _, niter_img, (kind, split) in launched:
+        layout, nb = PLAN_LAYOUT[kind, split], nk.shape[0]
+        e = jobs[0, :0]  # every bucket without jobs: a slice is ~4 us of host time, and most buckets are empty
+        plan = MaskPlan(kind, int(host[o + nb]), niter_img, lds=[], big=e, sparse_big=e, queue_wave=e, queue_group=e,
+                        wave_small=e, wave_big=e)
+        names = [name for name in layout for _ in range(nb - len(layout) + 1 if name == "lds" else 1)]
+        for k, name in enumerate(names):
+            rows = jobs[k, :host[o + k]] if host[o + k] else e
+            if name == "lds":
+                plan.lds.append(rows)
+            else:
+                setattr(plan, name, rows)
+        out.append(plan)
         o += nb + 1
     return out
 
 
-def _plan_launch(bbox: torch.Tensor, valid: torch.Tensor | None, kind: int, caps, counts: torch.Tensor | None = None):
-    """``counts`` (kind 0): per-label pixel counts; the too-big-for-LDS masks then split into a
-    big-sparse bucket (``len(caps)``) and the tiled one (last)."""
+def _plan_launch(bbox: torch.Tensor, valid: torch.Tensor | None, kind: PlanKind, counts: torch.Tensor | None = None):
+    """``counts`` (diffusion kinds): per-label pixel counts [B, nlab] int32, which split the too-big-for-LDS masks
+    into big-sparse and tiled.  Returns ``(jobs, bucket_n, scratch_total, niter_img, (kind, counts given))``."""
     B, nlab = bbox.shape[:2]
     dev = bbox.device
-    n = B * nlab
-    split = kind in (0, 2) and counts is not None
-    if split:
-        assert counts.shape == (B, nlab) and counts.dtype == torch.int32
-        px_counts = counts.contiguous()
-    # kind 2 (needs counts): the compact work-queue buckets (wave jobs, workgroup jobs) in front of
-    # kind 0's buckets, which keep the masks the queue kernel cannot take
-    nb = len(caps) + 1 + int(split) + (2 if kind == 2 and split else 0) + (2 if kind == 3 else 0)
-    jobs = torch.empty(nb, max(n, 1), 4, dtype=torch.int64, device=dev)
+    kind, split = PlanKind(kind), counts is not None
+    # the kernel would write queue buckets that are not there (no counts), or put fill jobs
+    # through the diffusion queue's test (FILL_WAVE with counts)
+    if (kind, split) not in PLAN_LAYOUT:
+        raise ValueError(f"no {kind.name} plan {'with' if split else 'without'} pixel counts")
+    assert not split or (counts.shape == (B, nlab) and counts.dtype == torch.int32)
+    caps = [LDS_FILL_BYTES] if kind in (PlanKind.FILL, PlanKind.FILL_WAVE) else DIFFUSE_CAPS
+    nb = len(PLAN_LAYOUT[kind, split]) - 1 + len(caps)
+    jobs = torch.empty(nb, max(B * nlab, 1), 4, dtype=torch.int64, device=dev)
     bucket_n = torch.zeros(nb, dtype=torch.int32, device=dev)
     tot = torch.zeros(1, dtype=torch.int64, device=dev)
     niter_img = torch.zeros(B, dtype=torch.int32, device=dev)
-    carr = (ctypes.c_int * max(1, len(caps)))(*[int(c) for c in caps])
+    carr = (ctypes.c_int * len(caps))(*[int(c) for c in caps])
     vptr = _native.ptr(valid.contiguous().view(torch.uint8)) if valid is not None else None
-    cptr = _native.ptr(px_counts) if split else None
-    _native.call("be_cp_plan_masks", _native.ptr(bbox.contiguous()), vptr, cptr, B, nlab, kind, ctypes.addressof(carr),
+    cptr = _native.ptr(counts.contiguous()) if split else None
+    _native.call("be_cp_plan_masks", _native.ptr(bbox.contiguous()), vptr, cptr, B, nlab, int(kind), ctypes.addressof(carr),
                  len(caps), _native.ptr(jobs), _native.ptr(bucket_n), _native.ptr(tot), _native.ptr(niter_img),
                  _native.stream(dev))
-    return jobs, bucket_n, tot, niter_img
+    return jobs, bucket_n, tot, niter_img, (kind, split)
 
 
 #: compact work-queue diffusion (be_cp_diffuse_q) for the masks it can take; 0 = the LDS-box buckets
 DIFFUSE_QUEUE = os.environ.get("BE_DIFFUSE_QUEUE", "1") != "0"
 
 
-def _diffuse_plan_kind() -> int:
-    return 2 if DIFFUSE_QUEUE else 0
+def _diffuse_plan_kind() -> PlanKind:
+    return PlanKind.DIFFUSE_QUEUE if DIFFUSE_QUEUE else PlanKind.DIFFUSE
 
 
 #: one-wave hole filling (be_cp_fill_holes_wave) for boxes up to 64 x 64 with the ring; 0 = LDS kernel only
 FILL_WAVE = os.environ.get("BE_FILL_WAVE", "1") != "0"
 
 
-def _fill_plan_kind() -> int:
-    return 3 if FILL_WAVE else 1
+def _fill_plan_kind() -> PlanKind:
+    return PlanKind.FILL_WAVE if FILL_WAVE else PlanKind.FILL
 
 
 def _diffuse_lds_bytes(ly, lx):
@@ -641,14 +676,6 @@ DIFFUSE_CAPS = [c for c, _ in DIFFUSE_BUCKETS]
 DIFFUSE_DV = 4
 
 
-def _diffuse_dv() -> int:
-    return int(os.environ.get("BE_DIFFUSE_DV", DIFFUSE_DV))
-
-
-def _diffuse_buckets(dv: int):
-    return tuple((cap, min(1024, t * (8 // dv))) for cap, t in DIFFUSE_BUCKETS)
-
-
 _DEBUG_STATS = os.environ.get("BIOENGINE_MASK_STATS", "0") == "1"
 
 
@@ -669,21 +696,23 @@ def _side_streams(dev):
     return _SIDE_STREAMS[key]
 
 
-def _bucket_small(slices):
-    """(bucket index, LDS cap, threads, jobs) of the non-empty one-workgroup buckets, largest first
-    (they set the critical path)."""
-    out = []
-    for i, (cap, threads) in enumerate(_diffuse_buckets(_diffuse_dv())):
-        if slices[i].shape[0]:
-            out.append((i, cap, threads, slices[i]))
+def _bucket_small(plan: MaskPlan, L, scratch, dv: int) -> list:
+    """``(entry, jobs, arguments after niter_img)`` of the non-empty one-workgroup-per-mask launches in
+    queue order: the big sparse masks (global-scratch heat field; ``niter`` sweeps of the largest boxes,
+    the longest-running launches), then the LDS buckets, largest first (they set the critical path)."""
+    out = [("be_cp_diffuse_nt", jobs, (_native.ptr(L), cap, min(1024, threads * (8 // dv)), dv))
+           for jobs, (cap, threads) in zip(plan.lds, DIFFUSE_BUCKETS) if jobs.shape[0]]
+    if plan.sparse_big.shape[0]:
+        out.append(("be_cp_diffuse_sparse_big", plan.sparse_big, (_native.ptr(scratch), _native.ptr(L))))
     if _DEBUG_STATS:
-        print(f"[diffuse_small] buckets={[int(x.shape[0]) for x in slices[:-1]]} big={int(slices[-1].shape[0])}", flush=True)
+        print(f"[diffuse_small] buckets={[x.shape[0] for x in plan.lds]} sparse_big={plan.sparse_big.shape[0]} "
+              f"big={plan.big.shape[0]}", flush=True)
     return out[::-1]
 
 
-def _diffuse_small(Mc, buckets, niter_img, L, st, ready=None, scratch=None) -> None:
-    """``ready``: event recorded on the current stream once the inputs exist; the buckets start
-    from it instead of from the stream's tail, so they run alongside the big-mask kernel.
+def _diffuse_small(Mc, launches, niter_img, L, scratch, st, ready=None) -> None:
+    """Queues :func:`_bucket_small`'s ``launches``.  ``ready``: event recorded on the current stream once the inputs
+    exist; the buckets start from it instead of from the stream's tail, so they run alongside the big-mask kernel.
 
     Every bucket kernel runs ``niter`` dependent sweeps, so its time grows with its mask size and a
     stream's tail is the sum of its buckets: the buckets (largest first) go to the queues in snake
@@ -701,24 +730,16 @@ def _diffuse_small(Mc, buckets, niter_img, L, st, ready=None, scratch=None) -> N
                 sd.wait_stream(main)
         queues = sides if ready is not None else [None] + sides  # None = the main stream itself
         nq = len(queues)
-    for k, (i, cap, threads, jobs) in enumerate(buckets):
+    for k, (entry, jobs, tail) in enumerate(launches):
+        sptr = st
         if concurrent:
             r = k % (2 * nq)
             sd = queues[r if r < nq else 2 * nq - 1 - r]
-            if sd is None:
-                sptr = st
-            else:
-                for t in (jobs, Mc, niter_img, L) + ((scratch,) if scratch is not None else ()):
+            if sd is not None:
+                for t in (jobs, Mc, niter_img, L, scratch):
                     t.record_stream(sd)
                 sptr = ctypes.c_void_p(sd.cuda_stream)
-        else:
-            sptr = st
-        if i < 0:  # big-sparse bucket: global-scratch heat field, one workgroup per mask
-            _native.call("be_cp_diffuse_sparse_big", _native.ptr(Mc), _native.ptr(jobs), jobs.shape[0], H, W,
-                         _native.ptr(niter_img), _native.ptr(scratch), _native.ptr(L), sptr)
-            continue
-        _native.call("be_cp_diffuse_nt", _native.ptr(Mc), _native.ptr(jobs), jobs.shape[0], H, W,
-                     _native.ptr(niter_img), _native.ptr(L), cap, threads, _diffuse_dv(), sptr)
+        _native.call(entry, _native.ptr(Mc), _native.ptr(jobs), jobs.shape[0], H, W, _native.ptr(niter_img), *tail, sptr)
     if concurrent:
         for sd in sides:
             main.wait_stream(sd)
@@ -730,7 +751,7 @@ _TILE_PARAMS: tuple | None = None
 BIG_MASK_MODE = "tiled"
 
 
-def _diffuse_big(Mc, bj, niter_img, scratch, L, st, between=None) -> None:
+def _diffuse_big(Mc, bj, niter_img, scratch, L, st, between=None) -> torch.Tensor | None:
     """Diffusion of masks too large for one workgroup's LDS (see diffuse_tiled_kernel).
     ``between()`` runs after the short per-mask centre kernel is queued and before the long
     cooperative sweep (the caller releases its other streams there)."""
@@ -743,8 +764,6 @@ def _diffuse_big(Mc, bj, niter_img, scratch, L, st, between=None) -> None:
                      _native.ptr(scratch), _native.ptr(L), 0, st)
         return None
     if _TILE_PARAMS is None:
-        import ctypes
-
         buf = (ctypes.c_int * 3)()
         _native.call("be_cp_diffuse_tile_params", ctypes.addressof(buf))
         _TILE_PARAMS = (buf[0], buf[1], buf[2])
@@ -805,51 +824,40 @@ def masks_to_flows_gpu(M: torch.Tensor, dp: torch.Tensor | None = None, niter: i
 
     Returns (mu [B, 2, H, W] fp32, err_sum [B, nlab] fp32 or None, counts [B, nlab]).  When ``dp``
     ([B, >=2, H, W] network output) is given, err_sum[b, l] = sum over mask l of |mu - dp/5|^2.
-    ``counts`` / ``plan`` (label_counts and a kind-0 plan of the same labels) skip recomputing them;
+    ``counts`` / ``plan`` (label_counts and a diffusion plan of the same labels) skip recomputing them;
     ``want_mu=False`` (flow QC: only the errors are used) returns ``mu=None`` and skips its writes.
     """
     B, H, W = M.shape
     dev = M.device
     if nlab is None:  # an upper bound on the labels + 1 is enough (absent labels have no pixels)
-        nlab = int(M.max().item()) + 1 if M.numel() else 1
+        nlab = _label_bound(M)
     mu = torch.zeros(B, 2, H, W, dtype=torch.float32, device=dev) if (want_mu or dp is None) else None
     if counts is None:
         counts = label_counts(M, nlab)
     if nlab <= 1:
         return mu, (torch.zeros(B, nlab, device=dev) if dp is not None else None), counts
     if plan is None:
-        plan = _plan_finish([_plan_launch(mask_bboxes(M, nlab), None, _diffuse_plan_kind(), DIFFUSE_CAPS, counts)])[0]
-    slices, ssize, niter_img = plan
-    qjobs = None
-    if len(slices) == len(DIFFUSE_BUCKETS) + 4:  # kind 2: queue buckets first
-        qjobs, slices = slices[:2], slices[2:]
-    if niter is not None:
-        niter_img = torch.full((B,), niter, dtype=torch.int32, device=dev)
-    bj = slices[-1]
+        plan = _plan_finish([_plan_launch(mask_bboxes(M, nlab), None, _diffuse_plan_kind(), counts)])[0]
+    niter_img = plan.niter_img if niter is None else torch.full((B,), niter, dtype=torch.int32, device=dev)
+    bj, qw, qg = plan.big, plan.queue_wave, plan.queue_group
     L = torch.zeros(B, H, W, dtype=torch.float64, device=dev)
-    scratch = torch.empty(max(ssize, 1), dtype=torch.float64, device=dev)
+    scratch = torch.empty(max(plan.scratch_total, 1), dtype=torch.float64, device=dev)
     st = _native.stream(dev)
     Mc = M.contiguous()
-    buckets = _bucket_small(slices)
-    if len(slices) == len(DIFFUSE_BUCKETS) + 2 and slices[len(DIFFUSE_BUCKETS)].shape[0]:
-        # big sparse masks: the longest-running launches (niter sweeps of the largest boxes), so
-        # they head the queue order
-        buckets.insert(0, (-1, 0, 1024, slices[len(DIFFUSE_BUCKETS)]))
-    ws = None
-    ready = None
+    dv = int(os.environ.get("BE_DIFFUSE_DV", DIFFUSE_DV))  # read per call: benchmarks switch it between variants
+    buckets = _bucket_small(plan, L, scratch, dv)
+    ws = ready = release = None
     if bj.shape[0] and Mc.is_cuda and buckets:
         ready = torch.cuda.Event()
 
         def release():  # the buckets start once the big masks' centre kernel is done
             ready.record(torch.cuda.current_stream(dev))
-    else:
-        release = None
-    if qjobs is not None and (qjobs[0].shape[0] or qjobs[1].shape[0]):
+    if qw.shape[0] or qg.shape[0]:
         # one persistent launch over every mask the compact kernel takes (nearly all of them),
         # queued first: the box-bucket kernels below then only see the rare leftovers
         qws = torch.empty(2, dtype=torch.int32, device=dev)
-        _native.call("be_cp_diffuse_q", _native.ptr(Mc), _native.ptr(qjobs[0]), qjobs[0].shape[0], _native.ptr(qjobs[1]),
-                     qjobs[1].shape[0], H, W, _native.ptr(niter_img), _native.ptr(L), _native.ptr(qws), st)
+        _native.call("be_cp_diffuse_q", _native.ptr(Mc), _native.ptr(qw), qw.shape[0], _native.ptr(qg), qg.shape[0], H, W,
+                     _native.ptr(niter_img), _native.ptr(L), _native.ptr(qws), st)
     if bj.shape[0]:
         # first, on an idle device: the centre kernel runs alone (~0.07 ms instead of ~0.36 ms
         # among the bucket kernels), then the cooperative tiled sweep -- the critical path -- is
@@ -857,10 +865,8 @@ def masks_to_flows_gpu(M: torch.Tensor, dp: torch.Tensor | None = None, niter: i
         # (which never wait on it) fill the remaining CUs, so its grid barrier cannot starve
         ws = _diffuse_big(Mc, bj, niter_img, scratch, L, st, between=release)
     if buckets:
-        _diffuse_small(Mc, buckets, niter_img, L, st, ready=ready, scratch=scratch)
-    err = None
-    dpp = None
-    bstride = 0
+        _diffuse_small(Mc, buckets, niter_img, L, scratch, st, ready=ready)
+    err, dpp, bstride = None, None, 0
     if dp is not None:
         dpp = dp.float().contiguous()
         bstride = dpp.shape[1] * H * W
@@ -872,28 +878,33 @@ def masks_to_flows_gpu(M: torch.Tensor, dp: torch.Tensor | None = None, niter: i
 
 
 def _renumber(M: torch.Tensor, keep: torch.Tensor) -> torch.Tensor:
-    """keep [B, nlab] bool (index 0 ignored) -> M relabelled 1..k per image, dropped labels -> 0."""
-    keep = keep.clone()
-    keep[:, 0] = False
-    lut = torch.cumsum(keep.int(), dim=1) * keep.int()
-    B = M.shape[0]
-    return torch.gather(lut, 1, M.reshape(B, -1).long()).reshape(M.shape).to(torch.int32)
+    """keep [B, nlab] bool (index 0 ignored) -> M (B images; B = 1: any shape) relabelled 1..k per
+    image, dropped labels -> 0."""
+    return torch.gather(_rank_lut(keep), 1, M.reshape(keep.shape[0], -1).long()).reshape(M.shape)
 
 
-def fill_holes_gpu(M: torch.Tensor, min_size: int = 15, nlab: int | None = None) -> torch.Tensor:
-    """``nlab``: optional upper bound on the labels + 1 (saves the host sync on ``M.max()``)."""
-    B, H, W = M.shape
-    dev = M.device
-    if nlab is None:
-        nlab = int(M.max().item()) + 1 if M.numel() else 1
-    if nlab <= 1:
-        return M.clone()
-    counts = label_counts(M, nlab)
+def _label_bound(M: torch.Tensor) -> int:
+    """The labels + 1 of ``M``, by a host read of ``M.max()``."""
+    return int(M.max().item()) + 1 if M.numel() else 1
+
+
+def _present_keep(counts: torch.Tensor, min_size: int) -> torch.Tensor:
+    """counts [B, nlab] -> bool: the labels (never 0) that occur, with at least ``min_size`` pixels."""
     keep = counts > 0
     if min_size > 0:
         keep &= counts >= min_size
     keep[:, 0] = False
-    plan = _plan_masks(mask_bboxes(M, nlab), keep, _fill_plan_kind(), [LDS_FILL_BYTES])
+    return keep
+
+
+def fill_holes_gpu(M: torch.Tensor, min_size: int = 15, nlab: int | None = None) -> torch.Tensor:
+    """``nlab``: optional upper bound on the labels + 1 (saves the host sync on ``M.max()``)."""
+    if nlab is None:
+        nlab = _label_bound(M)
+    if nlab <= 1:
+        return M.clone()
+    keep = _present_keep(label_counts(M, nlab), min_size)
+    plan = _plan_finish([_plan_launch(mask_bboxes(M, nlab), keep, _fill_plan_kind())])[0]
     return _fill_run(M, _rank_lut(keep), nlab, plan)
 
 
@@ -904,31 +915,25 @@ def _rank_lut(keep: torch.Tensor) -> torch.Tensor:
     return (torch.cumsum(keep.int(), dim=1) * keep.int()).to(torch.int32).contiguous()
 
 
-def _fill_run(M: torch.Tensor, lut: torch.Tensor, nlab: int, plan) -> torch.Tensor:
-    """Hole filling of the planned jobs (a kind-1 plan); jobs whose lut entry is 0 write nothing."""
+def _fill_run(M: torch.Tensor, lut: torch.Tensor, nlab: int, plan: MaskPlan) -> torch.Tensor:
+    """Hole filling of the planned jobs (a fill plan); jobs whose lut entry is 0 write nothing."""
     B, H, W = M.shape
-    dev = M.device
     out = torch.zeros_like(M)
-    slices, ssize, _ = plan
-    wjs = []
-    if len(slices) == 4:  # kind 3: the one-wave buckets (<= 64 x 64, <= 256 x 128 boxes) first
-        wjs, slices = slices[:2], slices[2:]
-    sj, bj = slices
+    wjs = (plan.wave_small, plan.wave_big)
+    (sj,), bj = plan.lds, plan.big
     if sj.shape[0] + bj.shape[0] + sum(w.shape[0] for w in wjs) == 0:
         return out
-    scratch = torch.empty(max(ssize, 1), dtype=torch.uint8, device=dev)
-    st = _native.stream(dev)
+    scratch = torch.empty(max(plan.scratch_total, 1), dtype=torch.uint8, device=M.device)
+    st = _native.stream(M.device)
     Mc = M.contiguous()
     for big, wj in enumerate(wjs):
         if wj.shape[0]:
             _native.call("be_cp_fill_holes_wave", _native.ptr(Mc), _native.ptr(wj), wj.shape[0], H, W, _native.ptr(lut), nlab,
                          _native.ptr(out), big, st)
-    if sj.shape[0]:
-        _native.call("be_cp_fill_holes", _native.ptr(Mc), _native.ptr(sj), sj.shape[0], H, W, _native.ptr(lut), nlab,
-                     _native.ptr(scratch), _native.ptr(out), LDS_FILL_BYTES, st)
-    if bj.shape[0]:
-        _native.call("be_cp_fill_holes", _native.ptr(Mc), _native.ptr(bj), bj.shape[0], H, W, _native.ptr(lut), nlab,
-                     _native.ptr(scratch), _native.ptr(out), 0, st)
+    for jobs, lds_bytes in ((sj, LDS_FILL_BYTES), (bj, 0)):  # 0: the flood fill runs in global scratch
+        if jobs.shape[0]:
+            _native.call("be_cp_fill_holes", _native.ptr(Mc), _native.ptr(jobs), jobs.shape[0], H, W, _native.ptr(lut), nlab,
+                         _native.ptr(scratch), _native.ptr(out), lds_bytes, st)
     return out
 
 
@@ -962,6 +967,17 @@ def follow_flows_gpu(y: torch.Tensor, niter: int = 200, cellprob_threshold: floa
     _native.call(FOLLOW_FLOWS_ENTRY if entry is None else entry, _native.ptr(flow2), _native.ptr(fg), _native.ptr(hist),
                  _native.ptr(pos), B, H, W, int(niter), st)
     return (hist, pos, flow2, fg) if with_flow else (hist, pos)
+
+
+def _lookup_labels(pos, M1, M0, B: int, nlab: int, max_size_fraction: float, st) -> torch.Tensor:
+    """Tail of :func:`get_masks_gpu` / :func:`get_masks3d_gpu`: per-pixel lookup in the expanded seeds ``M1``
+    into the zeroed ``M0`` (``B`` images or one volume), big-mask removal and renumber."""
+    N, Np = M0.numel() // B, M1.numel() // B
+    counts = torch.zeros(B, nlab, dtype=torch.int32, device=M0.device)
+    _native.call("be_cp_label_lookup", _native.ptr(pos), _native.ptr(M1), B, N, Np, _native.ptr(M0), _native.ptr(counts),
+                 nlab, st)
+    keep = (counts > 0) & (counts <= N * max_size_fraction)
+    return _renumber(M0, keep)
 
 
 def get_masks_gpu(hist: torch.Tensor, pos: torch.Tensor, shape=None, max_size_fraction: float = 0.4,
@@ -1000,12 +1016,7 @@ def get_masks_gpu(hist: torch.Tensor, pos: torch.Tensor, shape=None, max_size_fr
     _native.call("be_cp_expand", _native.ptr(hist), _native.ptr(keys_sorted), _native.ptr(nseeds), B, Hp, Wp, kmax, kmax,
                  _native.ptr(M1), st)
     nlab = kmax + 1
-    counts = torch.zeros(B, nlab, dtype=torch.int32, device=dev)
-    _native.call("be_cp_label_lookup", _native.ptr(pos), _native.ptr(M1), B, H * W, Hp * Wp, _native.ptr(M0),
-                 _native.ptr(counts), nlab, st)
-    big = H * W * max_size_fraction
-    keep = (counts > 0) & (counts <= big)
-    M = _renumber(M0, keep)
+    M = _lookup_labels(pos, M1, M0, B, nlab, max_size_fraction, st)
     return (M, nlab) if with_bound else M
 
 
@@ -1030,23 +1041,20 @@ def compute_masks_gpu(y: torch.Tensor, niter: int = 200, cellprob_threshold: flo
     # labels kept by QC and min_size in id order (= QC renumber followed by the fill's renumber).
     counts = label_counts(M, nlab)
     bbox = mask_bboxes(M, nlab)
-    fill_keep = counts > 0
-    if min_size > 0:
-        fill_keep &= counts >= min_size
-    fill_keep[:, 0] = False
+    fill_keep = _present_keep(counts, min_size)
     qc = flow_threshold is not None and flow_threshold > 0
     # masks below min_size are dropped whatever their flow error: the QC diffusion skips them (the
     # plan still takes cellpose's per-image niter over ALL masks, so the kept masks' flows are
     # unchanged)
-    plans = _plan_finish(([_plan_launch(bbox, fill_keep, _diffuse_plan_kind(), DIFFUSE_CAPS, counts)] if qc else [])
-                         + [_plan_launch(bbox, fill_keep, _fill_plan_kind(), [LDS_FILL_BYTES])])
+    *qc_plan, fill_plan = _plan_finish(([_plan_launch(bbox, fill_keep, _diffuse_plan_kind(), counts)] if qc else [])
+                                       + [_plan_launch(bbox, fill_keep, _fill_plan_kind())])
     if qc:
-        _, err, _ = masks_to_flows_gpu(M, dp=y, nlab=nlab, counts=counts, plan=plans[0], want_mu=False)
+        _, err, _ = masks_to_flows_gpu(M, dp=y, nlab=nlab, counts=counts, plan=qc_plan[0], want_mu=False)
         qc_keep = (counts > 0) & ~(err / counts.clamp(min=1).float() > flow_threshold)
         qc_keep[:, 0] = False
         M = torch.gather(qc_keep.to(torch.int32), 1, M.reshape(M.shape[0], -1).long()).reshape(M.shape) * M
         fill_keep &= qc_keep
-    out = _fill_run(M.contiguous(), _rank_lut(fill_keep), nlab, plans[-1])
+    out = _fill_run(M.contiguous(), _rank_lut(fill_keep), nlab, fill_plan)
     out.label_bound = nlab  # labels + 1 never exceed it: measure_masks_gpu(nlab=...) then plans without a sync
     return out
 
@@ -1216,7 +1224,7 @@ def get_masks3d_gpu(hist: torch.Tensor, pos: torch.Tensor, shape=None, max_size_
     if tuple(hist.shape) != (Zp, Hp, Wp) or tuple(pos.shape) != (Z, H, W):
         raise ValueError(f"get_masks3d_gpu: hist {tuple(hist.shape)} / pos {tuple(pos.shape)} do not fit a "
                          f"{Z} x {H} x {W} volume padded by {RPAD}")
-    N, Np = Z * H * W, Zp * Hp * Wp
+    N = Z * H * W
     if pos.device.type != "cuda":
         pn = pos.numpy()
         inds = np.nonzero(pn >= 0)
@@ -1241,11 +1249,7 @@ def get_masks3d_gpu(hist: torch.Tensor, pos: torch.Tensor, shape=None, max_size_
     M1 = torch.zeros(Zp, Hp, Wp, dtype=torch.int32, device=dev)
     _native.call("be_cp_expand3d", _native.ptr(hist), _native.ptr(keys_sorted), k, Zp, Hp, Wp, _native.ptr(M1), st)
     nlab = k + 1
-    counts = torch.zeros(1, nlab, dtype=torch.int32, device=dev)
-    _native.call("be_cp_label_lookup", _native.ptr(pos), _native.ptr(M1), 1, N, Np, _native.ptr(M0), _native.ptr(counts),
-                 nlab, st)
-    keep = (counts > 0) & (counts <= N * max_size_fraction)
-    M = _renumber(M0.view(1, N), keep).view(Z, H, W)
+    M = _lookup_labels(pos, M1, M0, 1, nlab, max_size_fraction, st)
     return (M, nlab) if with_bound else M
 
 
@@ -1275,20 +1279,16 @@ def fill_holes3d_gpu(M: torch.Tensor, min_size: int = 15, nlab: int | None = Non
     if M.device.type != "cuda":
         return torch.from_numpy(ref.fill_holes_and_remove_small_masks3d(M.numpy(), min_size))
     if nlab is None:
-        nlab = int(M.max().item()) + 1 if M.numel() else 1
+        nlab = _label_bound(M)
     if nlab <= 1 or M.numel() == 0:
         return torch.zeros_like(M)
     M = M.to(torch.int32).contiguous()
-    present = label_counts(M, nlab) > 0
-    present[:, 0] = False
+    present = _present_keep(label_counts(M, nlab), 0)
     lut = (present.int() * torch.arange(nlab, dtype=torch.int32, device=M.device)[None]).contiguous()
-    plan = _plan_masks(mask_bboxes(M, nlab), present, _fill_plan_kind(), [LDS_FILL_BYTES])
+    plan = _plan_finish([_plan_launch(mask_bboxes(M, nlab), present, _fill_plan_kind())])[0]
     out = _fill_run(M, lut, nlab, plan)
-    vol = label_counts(out, nlab).sum(0, keepdim=True)
-    keep = vol > 0
-    if min_size > 0:
-        keep &= vol >= min_size
-    return _renumber(out.view(1, -1), keep).view(Z, H, W)
+    keep = _present_keep(label_counts(out, nlab).sum(0, keepdim=True), min_size)
+    return _renumber(out, keep)
 
 
 def compute_masks3d_gpu(dP, cellprob=None, niter: int = 200, cellprob_threshold: float = 0.0, min_size: int = 15,
@@ -1368,7 +1368,7 @@ def measure_masks_gpu(M: torch.Tensor, img: torch.Tensor | None = None, nlab: in
         C = img.shape[1]
     dev = M.device
     if nlab is None:
-        nlab = int(M.max().item()) + 1 if M.numel() else 1
+        nlab = _label_bound(M)
     K = max(int(nlab) - 1, 0)
     if dev.type != "cuda":
         return _measure_oracle(M, img.float() if img is not None else None, K, volume, outlines)

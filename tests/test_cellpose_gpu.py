@@ -105,12 +105,17 @@ def test_plan_masks_kernel_matches_torch_planner(gpu, kind):
     M = M.to(gpu)
     nlab = int(M.max()) + 1
     bbox = cg.mask_bboxes(M, nlab)
-    if kind == 0:
+    kind = cg.PlanKind(kind)
+    if kind == cg.PlanKind.DIFFUSE:
         caps, lds, scr, valid = [c for c, _ in cg.DIFFUSE_BUCKETS], cg._diffuse_lds_bytes, cg._diffuse_scratch_doubles, None
     else:
         caps, lds, scr = [cg.LDS_FILL_BYTES], (lambda ly, lx: (ly + 2) * (lx + 2)), (lambda ly, lx: (ly + 2) * (lx + 2))
         valid = torch.rand(B, nlab, generator=g).to(gpu) > 0.3
-    got, tot, niter = cg._plan_masks(bbox, valid, kind, caps)
+    plan = cg._plan_finish([cg._plan_launch(bbox, valid, kind)])[0]
+    assert plan.kind == kind and len(plan.lds) == len(caps)
+    for absent in (plan.sparse_big, plan.queue_wave, plan.queue_group, plan.wave_small, plan.wave_big):
+        assert tuple(absent.shape) == (0, 4)
+    got, tot, niter = plan.lds + [plan.big], plan.scratch_total, plan.niter_img
     present = bbox[..., 1] >= 0
     present[:, 0] = False
     keep = present if valid is None else present & valid
@@ -118,15 +123,16 @@ def test_plan_masks_kernel_matches_torch_planner(gpu, kind):
     want, wtot = cg._plan_jobs(bbox.view(-1, 4), (ar // nlab).int(), (ar % nlab).int(), lds, caps, scr,
                                valid=keep.view(-1))
     assert sum(int(x.shape[0]) for x in got) == int(keep.sum())
-    assert kind == 1 or got[-1].shape[0] >= 1  # the diffusion plan has a beyond-LDS mask
+    assert kind == cg.PlanKind.FILL or plan.big.shape[0] >= 1  # the diffusion plan has a beyond-LDS mask
+    assert len(got) == len(want)
     for a, b in zip(got, want):
         ka = sorted(map(tuple, a[:, :3].tolist()))
         kb = sorted(map(tuple, b[:, :3].tolist()))
         assert ka == kb
     assert tot == wtot
-    big = got[-1][:, 3].tolist()
-    assert len(set(big)) == len(big) and all(x >= 0 for x in big) and all(x == -1 for x in got[0][:, 3].tolist())
-    if kind == 0:
+    big = plan.big[:, 3].tolist()
+    assert len(set(big)) == len(big) and all(x >= 0 for x in big) and all(x == -1 for x in plan.lds[0][:, 3].tolist())
+    if kind == cg.PlanKind.DIFFUSE:
         ext = (bbox[..., 1] - bbox[..., 0] + bbox[..., 3] - bbox[..., 2] + 4).clamp(min=0) * present
         assert torch.equal(niter, (2 * ext.max(dim=1).values).int())
 
@@ -305,9 +311,9 @@ def test_sparse_diffusion_bit_identical_to_dense(gpu, monkeypatch):
 
 @pytest.mark.gpu
 def test_diffusion_queue_plan_buckets(gpu):
-    """Plan kind 2: masks of <= 256 pixels (box width + 2 <= 256) are wave jobs, <= 2048 pixels
-    (the default 512-thread build; 1024 in the 256-thread one) workgroup jobs, the rest keep kind
-    0's buckets; every present mask lands in exactly one."""
+    """The queue plan kind: masks of <= 256 pixels (box width + 2 <= 256) are wave jobs, <= 2048
+    pixels (the default 512-thread build; 1024 in the 256-thread one) workgroup jobs, the rest keep
+    the plain diffusion kind's buckets; every present mask lands in exactly one."""
     from bioengine_worker_amd.cellpose import gpu as cg
 
     M = torch.zeros(2, 300, 320, dtype=torch.int32)
@@ -320,12 +326,14 @@ def test_diffusion_queue_plan_buckets(gpu):
     nlab = 4
     counts = cg.label_counts(M, nlab)
     bbox = cg.mask_bboxes(M, nlab)
-    got, _, _ = cg._plan_finish([cg._plan_launch(bbox, None, 2, cg.DIFFUSE_CAPS, counts)])[0]
-    assert len(got) == len(cg.DIFFUSE_BUCKETS) + 4
+    plan = cg._plan_finish([cg._plan_launch(bbox, None, cg.PlanKind.DIFFUSE_QUEUE, counts)])[0]
+    assert plan.kind == cg.PlanKind.DIFFUSE_QUEUE and len(plan.lds) == len(cg.DIFFUSE_BUCKETS)
     key = lambda t: sorted((int(r[0]) & 0xFFFFFFFF, int(r[0]) >> 32) for r in t.cpu())
-    assert key(got[0]) == [(0, 1), (1, 2)]
-    assert key(got[1]) == [(0, 2), (1, 1)]
-    assert sum(len(key(g)) for g in got[2:]) == 1
+    assert key(plan.queue_wave) == [(0, 1), (1, 2)]
+    assert key(plan.queue_group) == [(0, 2), (1, 1)]
+    rest = plan.lds + [plan.sparse_big, plan.big]
+    assert sorted(k for g in rest for k in key(g)) == [(0, 3)]
+    assert plan.wave_small.shape[0] == plan.wave_big.shape[0] == 0
 
 
 @pytest.mark.gpu
