@@ -3,8 +3,11 @@
 The rules are ``search/reference.py``'s numpy oracle (written from memory of umap-learn 0.5, never
 compared with it; its departures are listed there).  Stages:
 
-* :func:`knn_table_gpu` — plumbing in torch: fp32 row normalisation, chunked ``torch.mm`` score blocks
-  (never ``n x n``), ``topk``.
+* :func:`knn_table_gpu` — fp32 row normalisation, then either torch (chunked ``torch.mm`` score blocks, never
+  ``n x n``, ``topk``) or, for large cosine tables, ``csrc/kernels/knn_topk.hip`` (:func:`_knn_fused`):
+  ``be_knn_topk_bf16`` selects candidates inside a bf16 MFMA kernel on hi / lo split operands,
+  ``be_knn_rescore_f32`` gives their fp32 scores, and a per-row certificate sends the rows it cannot vouch for
+  back to the torch rule.
 * :func:`smooth_knn_gpu` — ``be_umap_smooth_knn``: rho, sigma and the directed memberships.
 * :func:`graph_from_memberships` — reciprocal lookup, fuzzy union, one ``torch.sort`` on an int64
   ``(row, col)`` key, dedupe, pruning, ``row_ptr``.  No atomics decide the order: two runs give identical
@@ -15,7 +18,8 @@ compared with it; its departures are listed there).  Stages:
 New points onto a fitted layout (:func:`umap_transform_gpu`; the rules are ``reference.umap_transform``'s, every
 one of them per query):
 
-* :func:`knn_query_table_gpu` — torch: score blocks of query rows against the training set, ``topk``.
+* :func:`knn_query_table_gpu` — score blocks of query rows against the training set and ``topk`` in torch, or
+  the same fused kernels.
 * :func:`smooth_knn_query_gpu` — ``be_umap_smooth_knn_query``: rho (the row minimum), sigma and the ``k``
   memberships, which are the edge weights.
 * :func:`transform_init_gpu` — torch: the weighted mean of the neighbours' training positions.
@@ -48,6 +52,7 @@ class UMAPParams:
     seed: int = 42
     init: Any = "pca"
     transform_epochs: int | None = None  # of umap_transform_gpu; None: 100, whatever the number of queries
+    knn: str = "auto"  # neighbour tables: "torch", "fused" (be_knn_topk_bf16) or "auto" (_use_fused)
 
 
 def _seed32(seed: int) -> int:
@@ -55,12 +60,192 @@ def _seed32(seed: int) -> int:
     return s - (1 << 32) if s >= 1 << 31 else s
 
 
-def knn_table_gpu(x: torch.Tensor, k: int, metric: str = "cosine", budget: int = 1 << 30):
+# ------------------------------------------------------------------------------- fused neighbour tables
+KNN_METHODS = ("auto", "torch", "fused")
+KNN_SLACK = 16            # candidates beyond the listed neighbours that the coarse pass hands to the re-score
+KNN_MAX_CANDIDATES = 64   # be_knn_topk_bf16's list length
+# "auto": m * n from which the fused path is taken.  Measured (README, landscape view): at 10 000 x 10 000 the fused
+# table is slower than torch (4.5 against 2.8 ms), at 90 000 x 10 000 faster by 40 times the torch arm's spread.
+KNN_AUTO_MIN_SCORES = 900_000_000
+KNN_ROW_CHUNK = 1 << 17   # rows of A per coarse pass: bounds the K-tripled bf16 copy (768-d: 604 MB)
+_KNN_TARGET_BLOCKS = 768  # workgroups the column split aims at: the 256 CUs three times over
+
+
+def _use_fused(method: str, metric: str, t: torch.Tensor, m: int, n: int, k_others: int) -> bool:
+    """"fused" demands the kernel path; "auto" takes it for a cosine table of at least ``KNN_AUTO_MIN_SCORES``
+    scores on a GPU tensor whose candidates fit the kernel's lists."""
+    if method not in KNN_METHODS:
+        raise ValueError(f"method must be one of {KNN_METHODS}")
+    if method == "torch":
+        return False
+    if method == "fused":
+        if metric != "cosine":
+            raise ValueError("the fused neighbour table serves the cosine metric only")
+        if not (t.is_cuda and _native.hip_available()):
+            raise _native.NativeUnavailable("be_knn_topk_bf16 needs a GPU tensor and the native kernel library")
+        if k_others + KNN_SLACK > KNN_MAX_CANDIDATES:
+            raise ValueError(f"the fused neighbour table lists at most {KNN_MAX_CANDIDATES - KNN_SLACK} neighbours")
+        return True
+    return (metric == "cosine" and t.is_cuda and k_others + KNN_SLACK <= KNN_MAX_CANDIDATES
+            and m * n >= KNN_AUTO_MIN_SCORES and _native.hip_available())
+
+
+def split_bf16_k3(x: torch.Tensor, right: bool = False) -> torch.Tensor:
+    """fp32 rows ``[r, d]`` -> bf16 ``[r, K']``, ``K' = 3 d`` padded with zeros to a multiple of 32.  With
+    ``hi = bf16(x)`` and ``lo = bf16(x - hi)`` the left operand is ``[hi, hi, lo]`` and the right one
+    ``[hi', lo', hi']``, so a plain bf16 inner product of a left and a right row is ``hi.hi' + hi.lo' + lo.hi'``.
+    Any device."""
+    x = x.float()
+    r, d = x.shape
+    hi = x.to(torch.bfloat16)
+    lo = (x - hi.float()).to(torch.bfloat16)
+    out = torch.zeros(r, -(-3 * d // 32) * 32, dtype=torch.bfloat16, device=x.device)
+    for j, part in enumerate((hi, lo, hi) if right else (hi, hi, lo)):
+        out[:, j * d:(j + 1) * d] = part
+    return out
+
+
+def knn_topk_bf16(A: torch.Tensor, B: torch.Tensor, kk: int, self_base: int = -1, splits: int | None = None):
+    """``be_knn_topk_bf16`` (and ``be_knn_merge`` when the columns are split): bf16 ``A [m, K]``, ``B [n, K]`` ->
+    ``scores [m, kk]`` float32, ``idx [m, kk]`` int32, the ``kk`` largest ``A[i].B[j]`` of every row ordered by
+    (score descending, index ascending) and padded with ``-inf`` / ``-1``.  Column ``self_base + i`` is left out of
+    row ``i`` when ``self_base >= 0``.  ``splits``: the column ranges swept by separate workgroups; None fills
+    the device from the shapes."""
+    if not (A.is_cuda and B.is_cuda):
+        raise _native.NativeUnavailable("be_knn_topk_bf16 needs GPU tensors")
+    if A.dtype != torch.bfloat16 or B.dtype != torch.bfloat16 or A.dim() != 2 or B.dim() != 2 or A.shape[1] != B.shape[1]:
+        raise ValueError("A [m, K] and B [n, K] must be bfloat16 with the same K")
+    (m, K), n = A.shape, B.shape[0]
+    if not 1 <= kk <= KNN_MAX_CANDIDATES or K % 32 or K < 32 or n < 1:
+        raise ValueError("need 1 <= kk <= 64, K a positive multiple of 32 and at least one column")
+    A, B = A.contiguous(), B.contiguous()
+    tiles = -(-n // 128)
+    S = max(1, _KNN_TARGET_BLOCKS // max(1, -(-m // 128))) if splits is None else int(splits)
+    if S < 1:
+        raise ValueError("splits must be at least 1")
+    S = min(S, tiles, 64)
+    dev = A.device
+    ps = torch.empty(m, S, kk, dtype=torch.float32, device=dev)
+    pi = torch.empty(m, S, kk, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _native.call("be_knn_topk_bf16", _native.ptr(A), _native.ptr(B), m, n, K, kk, int(self_base), S, _native.ptr(ps),
+                     _native.ptr(pi), _native.stream(dev))
+        if S == 1:
+            return ps.view(m, kk), pi.view(m, kk)
+        os_ = torch.empty(m, kk, dtype=torch.float32, device=dev)
+        oi = torch.empty(m, kk, dtype=torch.int32, device=dev)
+        _native.call("be_knn_merge", _native.ptr(ps), _native.ptr(pi), m, S, kk, _native.ptr(os_), _native.ptr(oi),
+                     _native.stream(dev))
+    return os_, oi
+
+
+def knn_rescore_f32(q: torch.Tensor, x: torch.Tensor, cand: torch.Tensor) -> torch.Tensor:
+    """``be_knn_rescore_f32``: fp32 ``q [m, d]``, ``x [n, d]``, ``cand [m, kk]`` int32 -> ``q[i].x[cand[i, t]]`` in
+    fp32 (``-inf`` for a candidate of ``-1``)."""
+    if not (q.is_cuda and x.is_cuda and cand.is_cuda):
+        raise _native.NativeUnavailable("be_knn_rescore_f32 needs GPU tensors")
+    assert q.dtype == torch.float32 and x.dtype == torch.float32 and cand.dtype == torch.int32
+    q, x, cand = q.contiguous(), x.contiguous(), cand.contiguous()
+    out = torch.empty(cand.shape, dtype=torch.float32, device=q.device)
+    with torch.cuda.device(q.device):
+        _native.call("be_knn_rescore_f32", _native.ptr(q), _native.ptr(x), _native.ptr(cand), cand.shape[0], x.shape[0],
+                     x.shape[1], cand.shape[1], _native.ptr(out), _native.stream(q.device))
+    return out
+
+
+def knn_certificate_eps(d: int) -> float:
+    """How far the coarse score of a pair of unit rows can lie below its fp32 re-score: ``(5 d + 128) 2^-24 + 2^-15``.
+
+    * The split: ``x = hi + lo + r`` with ``|x - hi| <= 2^-9 |x|`` and ``|r| <= 2^-18 |x|`` per element (bf16 keeps 8
+      significand bits, twice).  The coarse sum drops ``lo.lo'`` (Cauchy-Schwarz on unit rows: ``<= 2^-18``) and the
+      two residual terms ``x.r'`` and ``r.x'`` (``<= 2^-18`` each): ``3 * 2^-18 < 2^-16``.
+    * Its ``3 d`` products of two bf16 values are exact in fp32; accumulating them in fp32, in whatever order the
+      matrix unit uses, costs at most ``3 d u`` times the sum of their magnitudes, which is ``<= 1 + 2^-7``
+      (``u = 2^-24``): below ``4 d u``.
+    * The re-score's own fp32 chain and butterfly over ``d`` products: at most ``d u``.  Together ``5 d u``.
+    * ``128 u`` covers the rows' norms, which are 1 only to a few ``u``, on both sides; the second ``2^-16`` of the
+      ``2^-15`` is margin on the split term, not a fitted value."""
+    return (5 * d + 128) * 2.0 ** -24 + 2.0 ** -15
+
+
+def _knn_rows_torch(q: torch.Tensor, x: torch.Tensor, k: int, self_cols: torch.Tensor | None, budget: int):
+    """The torch rule on the unit rows ``q`` (the rows the certificate refused): as the "torch" bodies below."""
+    n = x.shape[0]
+    rows = max(1, budget // n)
+    idx = torch.empty(q.shape[0], k, dtype=torch.int32, device=q.device)
+    dist = torch.empty(q.shape[0], k, dtype=torch.float32, device=q.device)
+    for i in range(0, q.shape[0], rows):
+        d = (1.0 - torch.mm(q[i:i + rows], x.T)).clamp_(min=0.0)
+        if self_cols is not None:
+            d[torch.arange(d.shape[0], device=q.device), self_cols[i:i + rows]] = -1.0
+        td, ti = torch.topk(d, k, dim=1, largest=False, sorted=True)
+        if self_cols is not None:
+            td[:, 0] = 0.0
+        idx[i:i + rows] = ti.int()
+        dist[i:i + rows] = td
+    return idx, dist
+
+
+def _knn_fused(q: torch.Tensor, x: torch.Tensor, k: int, is_self: bool, budget: int, splits: int | None):
+    """Cosine table of the unit fp32 rows ``q [m, d]`` against ``x [n, d]`` (``is_self``: ``q`` is ``x``, column 0 is
+    the point itself and ``k`` counts it).
+
+    1. Coarse: ``be_knn_topk_bf16`` on the :func:`split_bf16_k3` operands lists ``kk = k_others + KNN_SLACK``
+       candidates per row by a score that is within :func:`knn_certificate_eps` of the fp32 one.
+    2. ``be_knn_rescore_f32`` gives the candidates' fp32 scores; a sort of the ``[m, kk]`` arrays by (distance,
+       index) gives the table.
+    3. A row is certified when it has no other column, or when its ``k_others``-th exact score is strictly above
+       its ``kk``-th coarse score plus eps: no column outside the list can then reach the table.  The other rows
+       (typically many exact duplicates of one point) are recomputed by the torch rule: one host read of their
+       count per chunk of ``KNN_ROW_CHUNK`` rows."""
+    m, n, d = q.shape[0], x.shape[0], x.shape[1]
+    k_others = k - 1 if is_self else k
+    avail = n - 1 if is_self else n
+    kk = min(k_others + KNN_SLACK, avail)
+    eps = knn_certificate_eps(d)
+    B = split_bf16_k3(x, right=True)
+    idx = torch.empty(m, k, dtype=torch.int32, device=q.device)
+    dist = torch.empty(m, k, dtype=torch.float32, device=q.device)
+    fallback = 0
+    for i in range(0, m, KNN_ROW_CHUNK):
+        qc = q[i:i + KNN_ROW_CHUNK]
+        cs, ci = knn_topk_bf16(split_bf16_k3(qc), B, kk, i if is_self else -1, splits)
+        es = knn_rescore_f32(qc, x, ci)
+        dc = (1.0 - es).clamp_(min=0.0)
+        by_idx = ci.argsort(dim=1, stable=True)
+        order = by_idx.gather(1, dc.gather(1, by_idx).argsort(dim=1, stable=True))[:, :k_others]
+        ti, td = ci.gather(1, order), dc.gather(1, order)
+        if is_self:
+            own = torch.arange(i, i + qc.shape[0], dtype=torch.int32, device=q.device)[:, None]
+            ti, td = torch.cat([own, ti], 1), torch.cat([torch.zeros_like(td[:, :1]), td], 1)
+        idx[i:i + KNN_ROW_CHUNK], dist[i:i + KNN_ROW_CHUNK] = ti, td
+        if kk < avail:
+            kth = es.topk(k_others, dim=1).values[:, -1]
+            bad = torch.nonzero(~(kth > cs[:, kk - 1] + eps))[:, 0]  # the one host read: how many rows
+            if bad.numel():
+                fallback += int(bad.numel())
+                fi, fd = _knn_rows_torch(qc[bad], x, k, bad + i if is_self else None, budget)
+                idx[bad + i], dist[bad + i] = fi, fd
+    idx.knn_method, idx.knn_fallback_rows = "fused", fallback
+    return idx, dist
+
+
+def knn_table_gpu(x: torch.Tensor, k: int, metric: str = "cosine", budget: int = 1 << 30, method: str = "auto",
+                  splits: int | None = None):
     """``x [n, d]`` -> ``idx [n, k]`` int32, ``dist [n, k]`` float32 as ``reference.knn_table``: column 0 is
-    the point itself at distance 0, then the ``k - 1`` nearest other points, ascending.  Score blocks of
-    ``budget // n`` rows keep the temporary bounded (n = 100 000: 10 737 rows per block)."""
+    the point itself at distance 0, then the ``k - 1`` nearest other points, ascending.  ``method``: "torch"
+    (score blocks of ``budget // n`` rows keep the temporary bounded; n = 100 000: 10 737 rows per block),
+    "fused" (``be_knn_topk_bf16`` and the certified fp32 re-score, see :func:`_knn_fused`; ``splits`` forces its
+    column split count) or "auto" (:func:`_use_fused`).  ``idx.knn_method`` names the path taken and
+    ``idx.knn_fallback_rows`` the rows the fused path recomputed by the torch rule."""
     if metric not in ref.UMAP_METRICS:
         raise ValueError(f"metric must be one of {ref.UMAP_METRICS}")
+    if _use_fused(method, metric, x, x.shape[0], x.shape[0], k - 1):
+        x = x.float()
+        if not x.shape[0] > k:
+            raise ValueError(f"need more points ({x.shape[0]}) than n_neighbors ({k})")
+        x = x / x.norm(dim=1, keepdim=True)
+        return _knn_fused(x, x, k, True, budget, splits)
     x = x.float()
     n = x.shape[0]
     if not n > k:
@@ -84,6 +269,7 @@ def knn_table_gpu(x: torch.Tensor, k: int, metric: str = "cosine", budget: int =
         td[:, 0] = 0.0
         idx[i:i + rows] = ti.int()
         dist[i:i + rows] = td
+    idx.knn_method, idx.knn_fallback_rows = "torch", 0
     return idx, dist
 
 
@@ -236,7 +422,7 @@ def umap_fit_gpu(x, params: UMAPParams | None = None, device=None):
 
     with torch.cuda.device(dev):
         with trace.span("umap.knn", cuda=True, n=n):
-            idx, dist = knn_table_gpu(x, p.n_neighbors, p.metric)
+            idx, dist = knn_table_gpu(x, p.n_neighbors, p.metric, method=p.knn)
         marks.append(("knn", _mark(dev)))
         with trace.span("umap.smooth_knn", cuda=True):
             _, _, memb = smooth_knn_gpu(idx, dist)
@@ -260,7 +446,8 @@ def umap_fit_gpu(x, params: UMAPParams | None = None, device=None):
         marks[-1][1].synchronize()
     spans = {name: round(marks[i][1].elapsed_time(ev), 4) for i, (name, ev) in enumerate(marks[1:])}
     info = {"n_epochs": n_epochs, "n_edges": int(graph[1].numel()), "a": a, "b": b, "degree_median": dmed,
-            "degree_max": dmax, "spans_ms": spans}
+            "degree_max": dmax, "spans_ms": spans, "knn_method": idx.knn_method,
+            "knn_fallback_rows": idx.knn_fallback_rows}
     return Y, info
 
 
@@ -274,14 +461,19 @@ def _mark(dev):
 TRANSFORM_CHUNK = 1 << 17  # queries per pass of umap_transform_gpu; no rule looks beyond its own row
 
 
-def knn_query_table_gpu(q: torch.Tensor, x: torch.Tensor, k: int, metric: str = "cosine", budget: int = 1 << 30):
+def knn_query_table_gpu(q: torch.Tensor, x: torch.Tensor, k: int, metric: str = "cosine", budget: int = 1 << 30,
+                        method: str = "auto", splits: int | None = None):
     """``q [m, d]`` against the training rows ``x [n, d]`` -> ``idx [m, k]`` int32, ``dist [m, k]`` float32 as
-    ``reference.knn_query_table``: the ``k`` nearest training rows, ascending, no self column.  Score blocks of
-    ``budget // n`` query rows; an ``m x n`` matrix is never materialised."""
+    ``reference.knn_query_table``: the ``k`` nearest training rows, ascending, no self column.  "torch": score
+    blocks of ``budget // n`` query rows; an ``m x n`` matrix is never materialised.  ``method``, ``splits`` and the
+    attributes of ``idx`` are :func:`knn_table_gpu`'s."""
     if q.dim() != 2 or x.dim() != 2 or q.shape[1] != x.shape[1]:
         raise ValueError(f"q {tuple(q.shape)} and x {tuple(x.shape)} must be [m, d] and [n, d]")
     m, n = q.shape[0], x.shape[0]
     ref.check_transform_limits(m, n, k, metric)
+    if _use_fused(method, metric, q, m, n, k) and m > 0:
+        q, x = q.float(), x.float()
+        return _knn_fused(q / q.norm(dim=1, keepdim=True), x / x.norm(dim=1, keepdim=True), k, False, budget, splits)
     q, x = q.float(), x.float()
     if metric == "cosine":
         q = q / q.norm(dim=1, keepdim=True)
@@ -301,6 +493,7 @@ def knn_query_table_gpu(q: torch.Tensor, x: torch.Tensor, k: int, metric: str = 
         td, ti = torch.topk(d, k, dim=1, largest=False, sorted=True)
         idx[i:i + rows] = ti.int()
         dist[i:i + rows] = td
+    idx.knn_method, idx.knn_fallback_rows = "torch", 0
     return idx, dist
 
 
@@ -402,12 +595,14 @@ def umap_transform_gpu(q, x_train, Y_train, params: UMAPParams | None = None, de
     out = torch.empty(m, 2, dtype=torch.float32, device=dev)
     spans = {"knn": 0.0, "smooth_knn": 0.0, "init": 0.0, "layout": 0.0}
     marks = []
+    knn_method, knn_fallback = "torch", 0
     with torch.cuda.device(dev):
         for i in range(0, m, TRANSFORM_CHUNK):
             qc = q[i:i + TRANSFORM_CHUNK].to(dev, torch.float32)
             ev = [_mark(dev)]
             with trace.span("umap.transform.knn", cuda=True, m=qc.shape[0], n=n):
-                idx, dist = knn_query_table_gpu(qc, x, k, p.metric)
+                idx, dist = knn_query_table_gpu(qc, x, k, p.metric, method=p.knn)
+                knn_method, knn_fallback = idx.knn_method, knn_fallback + idx.knn_fallback_rows
             ev.append(_mark(dev))
             with trace.span("umap.transform.smooth_knn", cuda=True):
                 _, _, w = smooth_knn_query_gpu(dist)
@@ -426,4 +621,5 @@ def umap_transform_gpu(q, x_train, Y_train, params: UMAPParams | None = None, de
     for ev in marks:
         for j, name in enumerate(spans):
             spans[name] += ev[j].elapsed_time(ev[j + 1])
-    return out, {"n_epochs": n_epochs, "spans_ms": {s: round(v, 4) for s, v in spans.items()}}
+    return out, {"n_epochs": n_epochs, "spans_ms": {s: round(v, 4) for s, v in spans.items()}, "knn_method": knn_method,
+                 "knn_fallback_rows": knn_fallback}

@@ -3,7 +3,10 @@
 
 Data: ``n`` L2-normalised 768-d embeddings of 40 Gaussian clusters (seeded).  Per ``n`` (10 000 and
 100 000 by default) the arms are the four stages on prepared inputs (kNN, smooth-kNN, graph, layout), the
-PCA initialisation, the whole ``umap_fit_gpu`` and the PCA path of ``projection.project_2d``; they
+PCA initialisation, the whole ``umap_fit_gpu`` and the PCA path of ``projection.project_2d``, and the neighbour
+table's ``torch`` / ``fused`` pair (the table alone, the coarse kernel alone with its achieved FLOP/s from
+``2 m n K'``, the whole fit under either; ``knn_arms`` adds the share of rows that fell back, how many rows list
+other indices than the torch arm's and the spread of the torch arm timed twice); they
 alternate inside one process, HIP-event times (wall clock ending in a synchronise for the two whole-call
 arms, which return host or timed results), warmed, median of ``--reps`` (>= 10).  Reported beside them:
 the epoch kernel's time per epoch, the median / maximum degree, the launch-latency share of the layout
@@ -92,8 +95,21 @@ def bench(n: int, reps: int, n_trust: int) -> dict:
     def fresh():
         return Y0.clone(), {k: v.clone() for k, v in state0.items()}
 
+    # the neighbour table's two arms ("torch" twice: the difference of its two medians is the run-to-run spread the
+    # fused arm has to beat), the coarse kernel alone on prepared operands, and the whole fit under either
+    pt, pf = gu.UMAPParams(knn="torch"), gu.UMAPParams(knn="fused")
+    xn = x / x.norm(dim=1, keepdim=True)
+    kk = p.n_neighbors - 1 + gu.KNN_SLACK
+    rows = min(n, gu.KNN_ROW_CHUNK)
+    opA, opB = gu.split_bf16_k3(xn[:rows]), gu.split_bf16_k3(xn, right=True)
     arms = {
         "knn": (lambda: None, lambda _: gu.knn_table_gpu(x, p.n_neighbors), "event"),
+        "knn_torch": (lambda: None, lambda _: gu.knn_table_gpu(x, p.n_neighbors, method="torch"), "event"),
+        "knn_fused": (lambda: None, lambda _: gu.knn_table_gpu(x, p.n_neighbors, method="fused"), "event"),
+        "knn_torch_again": (lambda: None, lambda _: gu.knn_table_gpu(x, p.n_neighbors, method="torch"), "event"),
+        "knn_coarse": (lambda: None, lambda _: gu.knn_topk_bf16(opA, opB, kk, 0), "event"),
+        "umap_fit_torch": (lambda: None, lambda _: gu.umap_fit_gpu(x, pt), "wall"),
+        "umap_fit_fused": (lambda: None, lambda _: gu.umap_fit_gpu(x, pf), "wall"),
         "smooth_knn": (lambda: None, lambda _: gu.smooth_knn_gpu(idx, dist), "event"),
         "graph": (lambda: None, lambda _: gu.graph_from_memberships(idx, memb, n_epochs), "event"),
         "pca_init": (lambda: None, lambda _: gu.pca_init_gpu(x), "event"),
@@ -104,12 +120,18 @@ def bench(n: int, reps: int, n_trust: int) -> dict:
     }
     ms = alternate(arms, reps)
     Y, info = gu.umap_fit_gpu(x, p)
+    (ti, td), (fi, fd) = gu.knn_table_gpu(x, p.n_neighbors, method="torch"), gu.knn_table_gpu(x, p.n_neighbors, method="fused")
+    knn = {"auto_method": idx.knn_method, "fallback_share": round(fi.knn_fallback_rows / n, 6),
+           "rows_with_other_indices": int((ti != fi).any(1).sum()),
+           "largest_distance_difference": float((td - fd).abs().max()),
+           "coarse_tflops": round(2.0 * rows * n * opA.shape[1] / (ms["knn_coarse"] * 1e-3) / 1e12, 1),
+           "torch_spread_ms": round(abs(ms["knn_torch"] - ms["knn_torch_again"]), 4)}
     res = {"n": n, "d": int(x.shape[1]), "n_epochs": n_epochs, "n_edges": info["n_edges"], "degree_median": dmed,
            "degree_max": dmax, **{f"{k}_ms": round(v, 4) for k, v in ms.items()},
            "epoch_us": round(1e3 * ms["layout"] / n_epochs, 3),
            "empty_launch_us": round(1e3 * ms["empty_launches"] / n_epochs, 3),
            "launch_share_of_layout": round(ms["empty_launches"] / ms["layout"], 3),
-           "fit_spans_ms": info["spans_ms"], "finite": bool(torch.isfinite(Y).all()),
+           "fit_spans_ms": info["spans_ms"], "knn_arms": knn, "finite": bool(torch.isfinite(Y).all()),
            "range": [round(float(Y.min()), 2), round(float(Y.max()), 2)]}
     if n <= 10_000:
         sub = np.sort(np.random.default_rng(0).choice(n, size=min(n, n_trust), replace=False))

@@ -5,7 +5,9 @@
 Data: L2-normalised 768-d embeddings of 40 Gaussian clusters (seeded), ``--n-train`` of them fitted with
 ``umap_fit_gpu``, ``m`` more placed on that layout.  Per ``m`` (1, 90 000 and 1 000 000 by default) the arms are
 the four stages on prepared inputs (query table, smooth-kNN, start, layout), an empty launch of the transform
-kernel (16 queries whose every slot is pruned: all epochs, no work) and the whole ``umap_transform_gpu``; they
+kernel (16 queries whose every slot is pruned: all epochs, no work), the whole ``umap_transform_gpu`` and the
+query table's ``torch`` / ``fused`` pair (the table alone, the coarse kernel alone on one chunk with its achieved
+FLOP/s from ``2 m n K'``, the whole transform under either; ``knn_arms`` as in ``umap_bench``); they
 alternate inside one process, HIP-event times (wall clock ending in a synchronise for the whole call), warmed,
 median of ``--reps`` (>= 10).  ``layout_16_train`` is the layout with the same schedule (it does not depend on
 positions) against a 16-point training set, so that every gather hits the same two cache lines: what is left of
@@ -59,8 +61,19 @@ def bench(m: int, x: torch.Tensor, Yt: torch.Tensor, reps: int) -> dict:
     e_idx = torch.zeros(16, 1, dtype=torch.int32, device=dev)
     e_w = torch.zeros(16, 1, device=dev)  # below 1 / E: never fires
     e_Y = torch.zeros(16, 2, device=dev)
+    pt, pf = gu.UMAPParams(knn="torch"), gu.UMAPParams(knn="fused")
+    kk = min(p.n_neighbors + gu.KNN_SLACK, x.shape[0])
+    rows = min(m, gu.KNN_ROW_CHUNK)
+    opA = gu.split_bf16_k3(q[:rows] / q[:rows].norm(dim=1, keepdim=True))
+    opB = gu.split_bf16_k3(x / x.norm(dim=1, keepdim=True), right=True)
     arms = {
         "knn": (lambda: None, lambda _: gu.knn_query_table_gpu(q, x, p.n_neighbors), "event"),
+        "knn_torch": (lambda: None, lambda _: gu.knn_query_table_gpu(q, x, p.n_neighbors, method="torch"), "event"),
+        "knn_fused": (lambda: None, lambda _: gu.knn_query_table_gpu(q, x, p.n_neighbors, method="fused"), "event"),
+        "knn_torch_again": (lambda: None, lambda _: gu.knn_query_table_gpu(q, x, p.n_neighbors, method="torch"), "event"),
+        "knn_coarse": (lambda: None, lambda _: gu.knn_topk_bf16(opA, opB, kk), "event"),
+        "transform_torch": (lambda: None, lambda _: gu.umap_transform_gpu(q, x, Yt, pt), "wall"),
+        "transform_fused": (lambda: None, lambda _: gu.umap_transform_gpu(q, x, Yt, pf), "wall"),
         "smooth_knn": (lambda: None, lambda _: gu.smooth_knn_query_gpu(dist), "event"),
         "init": (lambda: None, lambda _: gu.transform_init_gpu(idx, w, Yt), "event"),
         "layout": (Y0.clone, lambda Y: gu.transform_layout_gpu(Y, Yt, idx, w, E, a, b, p.seed), "event"),
@@ -72,10 +85,17 @@ def bench(m: int, x: torch.Tensor, Yt: torch.Tensor, reps: int) -> dict:
     Y, info = gu.umap_transform_gpu(q, x, Yt, p)
     stages = ms["knn"] + ms["smooth_knn"] + ms["init"] + ms["layout"]
     live = float((w >= 1.0 / E).float().sum(1).mean())
+    ti, td = gu.knn_query_table_gpu(q, x, p.n_neighbors, method="torch")
+    fi, fd = gu.knn_query_table_gpu(q, x, p.n_neighbors, method="fused")
+    knn = {"auto_method": idx.knn_method, "fallback_share": round(fi.knn_fallback_rows / m, 6),
+           "rows_with_other_indices": int((ti != fi).any(1).sum()),
+           "largest_distance_difference": float((td - fd).abs().max()),
+           "coarse_tflops": round(2.0 * rows * x.shape[0] * opA.shape[1] / (ms["knn_coarse"] * 1e-3) / 1e12, 2),
+           "torch_spread_ms": round(abs(ms["knn_torch"] - ms["knn_torch_again"]), 4)}
     return {"m": m, "n_train": int(x.shape[0]), "d": int(x.shape[1]), "n_epochs": E,
             **{f"{k}_ms": round(v, 4) for k, v in ms.items()}, "knn_share_of_stages": round(ms["knn"] / stages, 3),
             "layout_ns_per_query": round(1e6 * ms["layout"] / m, 2), "live_slots_per_query": round(live, 2),
-            "transform_spans_ms": info["spans_ms"], "finite": bool(torch.isfinite(Y).all())}
+            "transform_spans_ms": info["spans_ms"], "knn_arms": knn, "finite": bool(torch.isfinite(Y).all())}
 
 
 def compare(x: torch.Tensor, Yt: torch.Tensor, m: int, reps: int, n_trust: int) -> dict:
