@@ -52,13 +52,15 @@ class VectorIndex:
     from ``ivfpq_threshold``; ``"flat"`` / ``"ivf"`` / ``"ivfpq"`` force a tier."""
 
     def __init__(self, dim: int = 768, device=None, ivf_threshold: int = 5_000_000, nprobe: int = 64,
-                 index_type: str = "auto", ivfpq_threshold: int = 50_000_000, pq_m: int = 96, refine: int = 4):
+                 index_type: str = "auto", ivfpq_threshold: int = 50_000_000, pq_m: int = 96, refine: int = 4,
+                 pq_build: str = "auto"):
         self.lvecs: torch.Tensor | None = None
         self.dim = dim
         self.refine = refine  # IVF-PQ: re-rank refine*k PQ candidates with the stored vectors (0 = off)
         self.kind = index_type
         self.ivfpq_threshold = ivfpq_threshold
         self.pq_m = pq_m
+        self.pq_build = pq_build  # IVFPQIndex(build=...): "auto", "torch" or "fused" (csrc/kernels/pq_build.hip)
         self.pq = None
         self.device = torch.device(device) if device is not None else (
             torch.device("cuda") if torch.cuda.is_available() else torch.device("cpu"))
@@ -109,12 +111,13 @@ class VectorIndex:
 
         n = self.ntotal
         nl = nlist or min(default_nlist(n), max(1, n // 39))
-        pq = IVFPQIndex(self.dim, nl, self.pq_m, self.nprobe, self.device)
+        pq = IVFPQIndex(self.dim, nl, self.pq_m, self.nprobe, self.device, build=self.pq_build)
         g = torch.Generator(device="cpu").manual_seed(0)
         sample = self.vecs[torch.randperm(n, generator=g)[: min(n, max(262_144, 39 * nl))].to(self.vecs.device)]
         pq.train(sample.float())
         for i in range(0, n, 1 << 22):  # encode in chunks: no fp32 copy of the whole collection
-            pq.add(self.vecs[i:i + (1 << 22)].float())
+            xc = self.vecs[i:i + (1 << 22)]
+            pq.add(xc if pq.fused_build else xc.float())  # be_pq_encode reads the stored bf16 rows
         self.pq = pq
         self.centroids = None
 

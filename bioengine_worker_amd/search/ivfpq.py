@@ -14,6 +14,12 @@ MI355X design:
   LDS) writes approximate scores for all candidates, then a top-k.  Inner product, so the score is
   ``<q, c_list> + sum_j LUT[j][code_j]``.
 
+Build: ``build="torch"`` is the torch code below (batched ``bmm`` distances, ``argmin``); ``"fused"`` runs the PQ
+codebook iterations and the residual encoding in ``csrc/kernels/pq_build.hip`` (``be_pq_kmeans_step``,
+``be_pq_encode``: fp32 MFMA scores with the argmin inside the kernel, rows read in their stored dtype);
+``"auto"`` takes the kernels on a GPU device when the library is loaded and ``D/m`` is 4 or 8.  The coarse
+assignment and the coarse k-means are torch on every path.
+
 Everything has a CPU path (same math in torch) that the GPU kernel is tested against.
 """
 from __future__ import annotations
@@ -75,12 +81,85 @@ def _pq_encode(res: torch.Tensor, cb: torch.Tensor, chunk: int = 1 << 16) -> tor
     return torch.cat(out).contiguous()
 
 
-class IVFPQIndex:
-    """Approximate inner-product index; vectors should be L2-normalised (cosine)."""
+# ------------------------------------------------------------------------------- fused build (pq_build.hip)
+PQ_BUILDS = ("auto", "torch", "fused")
+_PQ_TARGET_BLOCKS = 256  # workgroups of a k-means step: fixes its slab count, and with it its summation order
 
-    def __init__(self, dim: int = 768, nlist: int = 4096, m: int = 96, nprobe: int = 64, device=None):
+
+def pq_fused_supported(dim: int, m: int) -> bool:
+    """Shapes ``be_pq_encode`` / ``be_pq_kmeans_step`` serve: sub-spaces of 4 or 8 dims, m a multiple of 16."""
+    return m >= 16 and m % 16 == 0 and dim in (4 * m, 8 * m)
+
+
+def _pq_fused_args(x: torch.Tensor, codebooks: torch.Tensor, what: str):
+    if not (x.is_cuda and codebooks.is_cuda and _native.hip_available()):
+        raise _native.NativeUnavailable(f"{what} needs GPU tensors and the native kernel library")
+    m, k, ds = codebooks.shape
+    if k != 256 or x.dim() != 2 or x.shape[0] < 1 or x.shape[1] != m * ds or not pq_fused_supported(m * ds, m):
+        raise _native.NativeUnavailable(f"{what} serves [n >= 1, m * ds] rows with ds in (4, 8), m % 16 == 0 "
+                                        "and 256 codewords")
+    return m, ds
+
+
+def pq_encode_fused(x: torch.Tensor, centroids: torch.Tensor, assign: torch.Tensor,
+                    codebooks: torch.Tensor) -> torch.Tensor:
+    """``be_pq_encode``: ``x [n, D]`` float32 or bfloat16, ``centroids [nlist, D]``, ``assign [n]``, ``codebooks
+    [m, 256, D/m]`` -> codes ``[n, m]`` uint8 of the residuals ``fp32(x) - centroids[assign]``: per sub-space the
+    argmin of ``|cb_k|^2 - 2 r.cb_k``, a tie to the smaller ``k``.  No distance reaches HBM, nothing is read back."""
+    m, _ = _pq_fused_args(x, codebooks, "be_pq_encode")
+    if x.dtype not in (torch.float32, torch.bfloat16):
+        x = x.float()
+    x = x.contiguous()
+    cent = centroids.to(x.device, torch.float32).contiguous()
+    a = assign.to(x.device, torch.int32).contiguous()
+    cb = codebooks.float().contiguous()
+    if a.shape != (x.shape[0],) or cent.shape[1] != x.shape[1]:
+        raise ValueError("assign [n] and centroids [nlist, D] must match x [n, D]")
+    codes = torch.empty(x.shape[0], m, dtype=torch.uint8, device=x.device)
+    with torch.cuda.device(x.device):
+        _native.call("be_pq_encode", _native.ptr(x), int(x.dtype == torch.bfloat16), _native.ptr(cent), _native.ptr(a),
+                     _native.ptr(cb), x.shape[0], x.shape[1], m, cent.shape[0], _native.ptr(codes),
+                     _native.stream(x.device))
+    return codes
+
+
+def pq_kmeans_step_fused(res: torch.Tensor, codebooks: torch.Tensor) -> torch.Tensor:
+    """``be_pq_kmeans_step``: one Lloyd iteration of the codebooks ``[m, 256, D/m]`` over the residuals ``res [S, D]``
+    (float32): assignment as :func:`pq_encode_fused`, sums and counts in a fixed order (no atomics: the same
+    input gives the same bits), ``sum / count``; a codeword without rows keeps its value."""
+    m, ds = _pq_fused_args(res, codebooks, "be_pq_kmeans_step")
+    res = res.float().contiguous()
+    cb = codebooks.float().contiguous()
+    S = res.shape[0]
+    slabs = max(1, min(-(-S // 128), _PQ_TARGET_BLOCKS // (m // 16)))
+    part = torch.empty(slabs, m, 256, ds + 1, dtype=torch.float32, device=res.device)
+    new = torch.empty_like(cb)
+    with torch.cuda.device(res.device):
+        _native.call("be_pq_kmeans_step", _native.ptr(res), _native.ptr(cb), S, res.shape[1], m, slabs,
+                     _native.ptr(part), _native.ptr(new), _native.stream(res.device))
+    return new
+
+
+def _pq_train_fused(res: torch.Tensor, m: int, iters: int, g: torch.Generator) -> torch.Tensor:
+    """:func:`_pq_train` with the iterations in ``be_pq_kmeans_step``: the same initial codewords."""
+    S, D = res.shape
+    init = torch.randperm(S, generator=g)[:256].to(res.device)
+    cb = res[init].view(-1, m, D // m).transpose(0, 1).contiguous()  # [m, 256, ds]
+    for _ in range(iters):
+        cb = pq_kmeans_step_fused(res, cb)
+    return cb
+
+
+class IVFPQIndex:
+    """Approximate inner-product index; vectors should be L2-normalised (cosine).  ``build``: how the PQ
+    codebooks are trained and the rows encoded, one of ``PQ_BUILDS`` (module docstring)."""
+
+    def __init__(self, dim: int = 768, nlist: int = 4096, m: int = 96, nprobe: int = 64, device=None,
+                 build: str = "auto"):
         if dim % m or m % 16:
             raise ValueError("dim must be divisible by m, and m a multiple of 16")
+        if build not in PQ_BUILDS:
+            raise ValueError(f"build must be one of {PQ_BUILDS}")
         self.dim, self.nlist, self.m, self.nprobe = dim, nlist, m, nprobe
         self.device = torch.device(device) if device is not None else (
             torch.device("cuda") if torch.cuda.is_available() else torch.device("cpu"))
@@ -92,6 +171,19 @@ class IVFPQIndex:
         self._assign = torch.empty(0, dtype=torch.int32, device=self.device)
         self._raw_codes = torch.empty(0, m, dtype=torch.uint8, device=self.device)
         self.ntotal = 0
+        self.build = build
+        self.fused_build  # "fused" where the kernels cannot run: raise now, not in the middle of a build
+
+    @property
+    def fused_build(self) -> bool:
+        """Whether train / add run on ``pq_build.hip``."""
+        if self.build == "torch":
+            return False
+        ok = self.device.type == "cuda" and pq_fused_supported(self.dim, self.m) and _native.hip_available()
+        if self.build == "fused" and not ok:
+            raise _native.NativeUnavailable("build='fused' needs a GPU device, the native kernel library and "
+                                            "sub-spaces of 4 or 8 dims")
+        return ok
 
     @property
     def index_type(self) -> str:
@@ -111,18 +203,27 @@ class IVFPQIndex:
         from .index import _argmax_ip
 
         a = _argmax_ip(ps, self.centroids)
-        self.codebooks = _pq_train(ps - self.centroids[a], self.m, pq_iters, g)
+        self.codebooks = (_pq_train_fused if self.fused_build else _pq_train)(ps - self.centroids[a], self.m, pq_iters, g)
 
     def add(self, x, chunk: int = 1 << 18) -> None:
         assert self.centroids is not None, "train() first"
         x = torch.as_tensor(x)
+        fused = self.fused_build
         assigns, codes = [], []
         for i in range(0, x.shape[0], chunk):
-            xc = x[i:i + chunk].to(self.device, torch.float32)
             from .index import _argmax_ip
 
-            a = _argmax_ip(xc, self.centroids)
-            codes.append(_pq_encode(xc - self.centroids[a], self.codebooks))
+            if fused and x.dtype == torch.bfloat16:
+                # the kernel reads the stored bf16 rows; only the coarse assignment sees an fp32 copy of the chunk
+                xs = x[i:i + chunk].to(self.device)
+                a = _argmax_ip(xs.float(), self.centroids)
+            else:
+                xs = x[i:i + chunk].to(self.device, torch.float32)
+                a = _argmax_ip(xs, self.centroids)
+            if fused:
+                codes.append(pq_encode_fused(xs, self.centroids, a, self.codebooks))
+            else:
+                codes.append(_pq_encode(xs - self.centroids[a], self.codebooks))
             assigns.append(a.int())
         self._assign = torch.cat([self._assign] + assigns)
         raw = torch.cat([self._raw()] + codes)

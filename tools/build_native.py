@@ -67,7 +67,9 @@ PER_SOURCE_FLAGS = {"clahe": ["-ffp-contract=off"], "attention": ["-mllvm", "-am
                     # oracle does; __fmul_rn / __fadd_rn are plain operators to hipcc and were fused into v_fmac_f32
                     "umap": ["-ffp-contract=off"],
                     # knn_topk: no packed-fp32 VALU (v_pk_add/mul/fma_f32) in the selection and re-score code
-                    "knn_topk": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+                    "knn_topk": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+                    # pq_build: the same, for the residuals (float4 subtractions) and the k-means sums
+                    "pq_build": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 CXX_FLAGS = ["-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-pthread", "-I", str(CSRC / "runtime")]
 
 

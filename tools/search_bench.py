@@ -14,7 +14,8 @@ GPU; for each N the bench builds
 and reports p50 / p95 latency of one query and of a 64-query batch (top-20), build time and two
 recall figures against the exact ranking: ``recall@10`` = |approx top-10 ∩ exact top-10| / 10
 (strict) and ``R@10`` = fraction of queries whose exact nearest neighbour is in the approx top-10
-(the FAISS convention the reference's "~95 % recall@10" uses).  One JSON line per (N, tier, nprobe).
+(the FAISS convention the reference's "~95 % recall@10" uses).  One JSON line per (N, tier, nprobe), and with the
+pq96 tier one ``"stage": "pq_build"`` line: ``IVFPQIndex.add`` with ``build="torch"`` against ``build="fused"``.
 Usage: ``python tools/search_bench.py --n 10000000,58000000``
 """
 import argparse
@@ -72,6 +73,62 @@ def recalls(gt, got):
     r10 = float(np.mean([len(set(g[:10]) & set(r[:10])) / 10 for g, r in zip(gt, got)]))
     r1 = float(np.mean([g[0] in set(r[:10]) for g, r in zip(gt, got)]))
     return round(r10, 4), round(r1, 4)
+
+
+def pq_build_times(pq, x, reps=3):
+    """``IVFPQIndex.add(x)`` on the torch path and on ``csrc/kernels/pq_build.hip``, with ``pq``'s trained
+    centroids and codebooks: device-event times (ms) of the whole call, both arms warmed up once on all of
+    ``x`` and then alternating; medians, the torch arm's spread, and the share of equal code bytes."""
+    from bioengine_worker_amd.search.ivfpq import IVFPQIndex
+
+    def arm(build):
+        idx = IVFPQIndex(pq.dim, pq.nlist, pq.m, pq.nprobe, pq.device, build=build)
+        idx.centroids, idx.codebooks = pq.centroids, pq.codebooks
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record()
+        idx.add(x)
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1), idx
+
+    ts = {"torch": [], "fused": []}
+    raws = {}
+    for r in range(reps + 1):
+        for build in ts:
+            t, idx = arm(build)
+            if r:
+                ts[build].append(t)
+            raws[build] = idx._raw()
+            del idx
+    med = {b: sorted(v)[len(v) // 2] for b, v in ts.items()}
+    # the encoding alone on one chunk of add (2^18 rows, coarse assignment given): be_pq_encode on the stored rows
+    # against the residual + _pq_encode of the torch path
+    from bioengine_worker_amd.search import ivfpq
+    from bioengine_worker_amd.search.index import _argmax_ip
+
+    xc = x[: 1 << 18]
+    a = _argmax_ip(xc.float(), pq.centroids)
+    enc = {"fused": lambda: ivfpq.pq_encode_fused(xc, pq.centroids, a, pq.codebooks),
+           "torch": lambda: ivfpq._pq_encode(xc.float() - pq.centroids[a], pq.codebooks)}
+    et = {}
+    for b, fn in enc.items():
+        fn()
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(reps + 1)]
+        ev[0].record()
+        for e in ev[1:]:
+            fn()
+            e.record()
+        ev[-1].synchronize()
+        et[b] = sorted(p.elapsed_time(q) for p, q in zip(ev, ev[1:]))[reps // 2]
+    return {"n": int(x.shape[0]), "stage": "pq_build", "m": pq.m, "nlist": pq.nlist, "x_dtype": str(x.dtype),
+            "encode_rows": int(xc.shape[0]), "encode_torch_ms": round(et["torch"], 3),
+            "encode_fused_ms": round(et["fused"], 3),
+            "add_torch_ms": round(med["torch"], 2), "add_fused_ms": round(med["fused"], 2),
+            "torch_over_fused": round(med["torch"] / med["fused"], 2),
+            "torch_spread_ms": round(max(ts["torch"]) - min(ts["torch"]), 2),
+            "fused_spread_ms": round(max(ts["fused"]) - min(ts["fused"]), 2),
+            "codes_equal": round(int((raws["torch"] == raws["fused"]).sum()) / raws["torch"].numel(), 6)}
 
 
 def main():
@@ -186,6 +243,7 @@ def main():
         pq.add(x)
         torch.cuda.synchronize()
         build = time.perf_counter() - t0
+        print(json.dumps(pq_build_times(pq, x)), flush=True)
         for refine, tier in ((0, "IVFPQ-GPU m=96 nprobe=64"), (4, "IVFPQ-GPU + exact rerank 80"),
                              (200, "IVFPQ-GPU + exact rerank 4k")):
             vi = VectorIndex(dim=a.dim, device=dev, index_type="ivfpq", refine=refine)
