@@ -53,7 +53,7 @@ class VectorIndex:
 
     def __init__(self, dim: int = 768, device=None, ivf_threshold: int = 5_000_000, nprobe: int = 64,
                  index_type: str = "auto", ivfpq_threshold: int = 50_000_000, pq_m: int = 96, refine: int = 4,
-                 pq_build: str = "auto"):
+                 pq_build: str = "auto", pq_search: str = "auto"):
         self.lvecs: torch.Tensor | None = None
         self.dim = dim
         self.refine = refine  # IVF-PQ: re-rank refine*k PQ candidates with the stored vectors (0 = off)
@@ -61,6 +61,7 @@ class VectorIndex:
         self.ivfpq_threshold = ivfpq_threshold
         self.pq_m = pq_m
         self.pq_build = pq_build  # IVFPQIndex(build=...): "auto", "torch" or "fused" (csrc/kernels/pq_build.hip)
+        self.pq_search = pq_search  # IVFPQIndex(search=...): "auto", "scan" or "fused" (csrc/kernels/ivfpq_search.hip)
         self.pq = None
         self.device = torch.device(device) if device is not None else (
             torch.device("cuda") if torch.cuda.is_available() else torch.device("cpu"))
@@ -111,7 +112,7 @@ class VectorIndex:
 
         n = self.ntotal
         nl = nlist or min(default_nlist(n), max(1, n // 39))
-        pq = IVFPQIndex(self.dim, nl, self.pq_m, self.nprobe, self.device, build=self.pq_build)
+        pq = IVFPQIndex(self.dim, nl, self.pq_m, self.nprobe, self.device, build=self.pq_build, search=self.pq_search)
         g = torch.Generator(device="cpu").manual_seed(0)
         sample = self.vecs[torch.randperm(n, generator=g)[: min(n, max(262_144, 39 * nl))].to(self.vecs.device)]
         pq.train(sample.float())
@@ -197,8 +198,7 @@ class VectorIndex:
             if not self.refine or self.vecs.shape[0] != self.ntotal:
                 return self.pq.search(q.float(), k)
             # IVF-PQ shortlist of refine*k, re-scored exactly with the stored vectors (IVFPQ+R)
-            _, cand = self.pq.search(q.float(), self.refine * k)
-            c = torch.from_numpy(cand).to(self.device)
+            _, c = self.pq.search_device(q.float(), self.refine * k)  # stays on the device
             ok = c >= 0
             s = torch.einsum("qd,qkd->qk", q.float(), self._refine_rows(c.clamp(min=0)).float())
             s = torch.where(ok, s, torch.full_like(s, -float("inf")))
@@ -303,13 +303,13 @@ class VectorIndex:
         return info
 
     @classmethod
-    def load(cls, out_dir, device=None) -> "VectorIndex":
+    def load(cls, out_dir, device=None, pq_search: str = "auto") -> "VectorIndex":
         out = Path(out_dir)
         p = out / "vectors.npy"
         if not p.exists():
             raise FileNotFoundError(f"No index at {p}")
         v = np.load(p)  # allow_pickle=False
-        idx = cls(dim=v.shape[1], device=device)
+        idx = cls(dim=v.shape[1], device=device, pq_search=pq_search)
         ii = out / "index_info.json"
         info = json.loads(ii.read_text()) if ii.exists() else {}
         host = bool(info.get("host_refine")) and (out / "ivfpq_info.json").exists()
@@ -317,7 +317,7 @@ class VectorIndex:
         if (out / "ivfpq_info.json").exists():
             from .ivfpq import IVFPQIndex
 
-            idx.pq = IVFPQIndex.load(out, device=idx.device)
+            idx.pq = IVFPQIndex.load(out, device=idx.device, search=pq_search)
             idx.host_refine = host
             idx.refine = int(info.get("refine", idx.refine))
             idx.pq_m = idx.pq.m

@@ -9,10 +9,15 @@ MI355X design:
   each, trained with batched k-means (one ``bmm`` per iteration over all sub-spaces);
 * codes ``[N, m]`` uint8 stored list-sorted, so each list is one contiguous slab of HBM -- 58 M
   vectors at m=96 are 5.6 GB, scanned for a query only in its ``nprobe`` lists;
-* search: per query one ``[m, 256]`` lookup table (``bmm`` of the query's sub-vectors with the
-  codebooks, fp16), the HIP kernel ``be_ivfpq_scan`` (one workgroup per (query, list), the table in
-  LDS) writes approximate scores for all candidates, then a top-k.  Inner product, so the score is
-  ``<q, c_list> + sum_j LUT[j][code_j]``.
+* search: per query one ``[m, 256]`` fp16 lookup table of the query's sub-vectors against the codebooks; inner
+  product, so the score is ``<q, c_list> + sum_j LUT[j][code_j]``.  ``search="scan"``: the table by ``bmm``, the
+  HIP kernel ``be_ivfpq_scan`` (one workgroup per (query, list), the table in LDS) writes the scores of all
+  candidates to HBM, then ``topk`` and a slot -> id lookup in torch.  ``search="fused"``
+  (``csrc/kernels/ivfpq_search.hip``): ``be_ivfpq_lut`` makes the table, ``be_ivfpq_scan_topk`` scores equal
+  slot ranges of the query's candidate row and keeps the best ``k`` in LDS under (score descending, list-sorted
+  row ascending), ``be_ivfpq_merge`` joins the ranges and maps rows to ids: no score row in HBM and no host
+  read before the ``[Q, k]`` result.  ``"auto"``: see :meth:`IVFPQIndex.fused_search`.  The coarse probe
+  selection (``q @ centroids.T``, ``topk``) is torch on every path.
 
 Build: ``build="torch"`` is the torch code below (batched ``bmm`` distances, ``argmin``); ``"fused"`` runs the PQ
 codebook iterations and the residual encoding in ``csrc/kernels/pq_build.hip`` (``be_pq_kmeans_step``,
@@ -150,16 +155,90 @@ def _pq_train_fused(res: torch.Tensor, m: int, iters: int, g: torch.Generator) -
     return cb
 
 
+# ------------------------------------------------------------------------------- fused search (ivfpq_search.hip)
+PQ_SEARCHES = ("auto", "scan", "fused")
+PQ_SEARCH_M = (16, 32, 48, 64, 96, 128, 192)  # table sizes be_ivfpq_scan_topk is instantiated for
+PQ_SEARCH_MAX_K = 1024
+_PQ_SEARCH_BLOCKS = 256  # workgroups of a scan: one per CU
+
+
+def ivfpq_splits(Q: int, nprobe: int, kk: int) -> int:
+    """Slot ranges per query of ``be_ivfpq_scan_topk``, from the call's shape alone: about ``_PQ_SEARCH_BLOCKS``
+    workgroups, at most 16 per query (the merge takes the ranges one after the other; measured at 10 M rows, a
+    single query: 16 ranges 71 us, 64 ranges 110 us) and at most ``16384 / kk``."""
+    return max(1, min(16, _PQ_SEARCH_BLOCKS // max(Q, 1), 16384 // kk))
+
+
+def _auto_fused(m: int, Q: int, k: int) -> bool:
+    """The shapes at which ``search="auto"`` takes the fused path: those between the measured ones, at all of which it
+    was faster than ``"scan"`` (README, "IVF-PQ search": m = 96 and 192, 1 and 64 queries, k = 20 to 1000)."""
+    return m in (96, 192) and Q <= 64
+
+
+def ivfpq_lut_fused(q: torch.Tensor, codebooks: torch.Tensor) -> torch.Tensor:
+    """``be_ivfpq_lut``: ``q [Q, m * ds]``, ``codebooks [m, 256, ds]`` -> the fp16 table ``[Q, m, 256]``, entry
+    ``half_rn`` of one ``fmaf`` chain in ascending ``i`` (the same input gives the same bits)."""
+    if not (q.is_cuda and codebooks.is_cuda and _native.hip_available()):
+        raise _native.NativeUnavailable("be_ivfpq_lut needs GPU tensors and the native kernel library")
+    if codebooks.dim() != 3 or codebooks.shape[1] != 256 or q.dim() != 2 or q.shape[1] != codebooks.shape[0] * codebooks.shape[2]:
+        raise _native.NativeUnavailable("be_ivfpq_lut serves q [Q, m * ds] against codebooks [m, 256, ds]")
+    m, _, ds = codebooks.shape
+    q = q.float().contiguous()
+    cb = codebooks.float().contiguous()
+    lut = torch.empty(q.shape[0], m, 256, dtype=torch.float16, device=q.device)
+    with torch.cuda.device(q.device):
+        _native.call("be_ivfpq_lut", _native.ptr(q), _native.ptr(cb), q.shape[0], m, ds, _native.ptr(lut),
+                     _native.stream(q.device))
+    return lut
+
+
+def ivfpq_scan_topk_fused(lut_half: torch.Tensor, base: torch.Tensor, probes: torch.Tensor, list_off: torch.Tensor,
+                          codes: torch.Tensor, ids: torch.Tensor, kk: int, splits: int | None = None):
+    """``be_ivfpq_scan_topk`` + ``be_ivfpq_merge``: the ``kk`` best of ``base[q, p] + sum_j lut[q, j, code_j]`` over the
+    rows of the probed lists, ordered by (score descending, list-sorted row ascending) -> ``(scores [Q, kk] fp32,
+    ids [Q, kk] int64)`` on the device, ``-inf`` / ``-1`` in empty slots.  ``splits`` forces the slot ranges per
+    query (:func:`ivfpq_splits`).  Nothing is read back."""
+    t = (lut_half, base, probes, list_off, codes, ids)
+    if not (all(x.is_cuda for x in t) and _native.hip_available()):
+        raise _native.NativeUnavailable("be_ivfpq_scan_topk needs GPU tensors and the native kernel library")
+    Q, nprobe = probes.shape
+    m = codes.shape[1]
+    if (m not in PQ_SEARCH_M or not 1 <= kk <= PQ_SEARCH_MAX_K or codes.shape[0] >= 2 ** 31 or nprobe < 1
+            or lut_half.dtype != torch.float16 or lut_half.shape != (Q, m, 256) or codes.dtype != torch.uint8):
+        raise _native.NativeUnavailable(f"be_ivfpq_scan_topk serves m in {PQ_SEARCH_M}, 1 <= kk <= {PQ_SEARCH_MAX_K}, "
+                                        "fewer than 2^31 rows and an fp16 table [Q, m, 256]")
+    dev = codes.device
+    list_off = list_off.long().contiguous()
+    sizes = (list_off[1:] - list_off[:-1])[probes]  # [Q, nprobe]
+    cand_off = (torch.cumsum(sizes, 1) - sizes).contiguous()
+    P = int(splits) if splits else ivfpq_splits(Q, nprobe, kk)
+    part_s = torch.empty(Q, P, kk, dtype=torch.float32, device=dev)
+    part_r = torch.empty(Q, P, kk, dtype=torch.int32, device=dev)
+    out_s = torch.empty(Q, kk, dtype=torch.float32, device=dev)
+    out_i = torch.empty(Q, kk, dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        _native.call("be_ivfpq_scan_topk", _native.ptr(lut_half.contiguous()), _native.ptr(base.float().contiguous()),
+                     _native.ptr(probes.int().contiguous()), _native.ptr(list_off), _native.ptr(cand_off),
+                     _native.ptr(codes.contiguous()), codes.shape[0], Q, nprobe, m, kk, P, _native.ptr(part_s),
+                     _native.ptr(part_r), _native.stream(dev))
+        _native.call("be_ivfpq_merge", _native.ptr(part_s), _native.ptr(part_r), _native.ptr(ids.long().contiguous()),
+                     Q, P, kk, _native.ptr(out_s), _native.ptr(out_i), _native.stream(dev))
+    return out_s, out_i
+
+
 class IVFPQIndex:
     """Approximate inner-product index; vectors should be L2-normalised (cosine).  ``build``: how the PQ
-    codebooks are trained and the rows encoded, one of ``PQ_BUILDS`` (module docstring)."""
+    codebooks are trained and the rows encoded, one of ``PQ_BUILDS``; ``search``: how the probed lists are scanned,
+    one of ``PQ_SEARCHES`` (module docstring)."""
 
     def __init__(self, dim: int = 768, nlist: int = 4096, m: int = 96, nprobe: int = 64, device=None,
-                 build: str = "auto"):
+                 build: str = "auto", search: str = "auto"):
         if dim % m or m % 16:
             raise ValueError("dim must be divisible by m, and m a multiple of 16")
         if build not in PQ_BUILDS:
             raise ValueError(f"build must be one of {PQ_BUILDS}")
+        if search not in PQ_SEARCHES:
+            raise ValueError(f"search must be one of {PQ_SEARCHES}")
         self.dim, self.nlist, self.m, self.nprobe = dim, nlist, m, nprobe
         self.device = torch.device(device) if device is not None else (
             torch.device("cuda") if torch.cuda.is_available() else torch.device("cpu"))
@@ -173,6 +252,8 @@ class IVFPQIndex:
         self.ntotal = 0
         self.build = build
         self.fused_build  # "fused" where the kernels cannot run: raise now, not in the middle of a build
+        self.search_mode = search
+        self.fused_search(1, 1)  # the same for search="fused"
 
     @property
     def fused_build(self) -> bool:
@@ -184,6 +265,21 @@ class IVFPQIndex:
             raise _native.NativeUnavailable("build='fused' needs a GPU device, the native kernel library and "
                                             "sub-spaces of 4 or 8 dims")
         return ok
+
+    def fused_search(self, Q: int, k: int) -> bool:
+        """Whether a search of ``Q`` queries for ``k`` results runs on ``ivfpq_search.hip``.  ``"fused"``: always, or
+        it raises; ``"auto"``: where the kernels can run and ``_auto_fused`` holds."""
+        if self.search_mode == "scan":
+            return False
+        ok = self.device.type == "cuda" and self.m in PQ_SEARCH_M and _native.hip_available()
+        if self.search_mode == "fused":
+            if not ok:
+                raise _native.NativeUnavailable(f"search='fused' needs a GPU device, the native kernel library and "
+                                                f"m in {PQ_SEARCH_M}")
+            if k > PQ_SEARCH_MAX_K:
+                raise _native.NativeUnavailable(f"search='fused' keeps at most {PQ_SEARCH_MAX_K} results per query")
+            return True
+        return ok and k <= PQ_SEARCH_MAX_K and _auto_fused(self.m, Q, k)
 
     @property
     def index_type(self) -> str:
@@ -265,6 +361,9 @@ class IVFPQIndex:
         if q.dim() == 1:
             q = q[None]
         Q = q.shape[0]
+        if self.fused_search(Q, k):
+            ts, ids = self._search_fused(q, k, nprobe)
+            return ts.cpu().numpy(), ids.cpu().numpy()
         nprobe = min(nprobe or self.nprobe, self.nlist)
         cs = q @ self.centroids.T
         base, probes = torch.topk(cs, nprobe, dim=1)
@@ -292,6 +391,29 @@ class IVFPQIndex:
         S[:, :kk] = ts.cpu().numpy()
         I[:, :kk] = ids.cpu().numpy()
         return S, I
+
+    def _search_fused(self, q: torch.Tensor, k: int, nprobe: int | None):
+        """q [Q, D] fp32 on the device -> (scores [Q, k], ids [Q, k]) on the device; no host read on the way."""
+        Q = q.shape[0]
+        nprobe = min(nprobe or self.nprobe, self.nlist)
+        if Q == 0 or self.codes.shape[0] == 0:
+            return (torch.full((Q, k), -float("inf"), device=self.device),
+                    torch.full((Q, k), -1, dtype=torch.int64, device=self.device))
+        base, probes = torch.topk(q @ self.centroids.T, nprobe, dim=1)
+        return ivfpq_scan_topk_fused(ivfpq_lut_fused(q, self.codebooks), base, probes, self.list_off, self.codes,
+                                     self.ids, k)
+
+    @torch.no_grad()
+    def search_device(self, q, k: int = 20, nprobe: int | None = None):
+        """:meth:`search` with the results left on the index device as tensors (the re-rank shortlist of
+        ``VectorIndex.search``)."""
+        q = torch.as_tensor(np.asarray(q, np.float32) if not torch.is_tensor(q) else q).to(self.device, torch.float32)
+        if q.dim() == 1:
+            q = q[None]
+        if self.fused_search(q.shape[0], k):
+            return self._search_fused(q, k, nprobe)
+        S, I = self.search(q, k, nprobe)
+        return torch.from_numpy(S).to(self.device), torch.from_numpy(I).to(self.device)
 
     def _slot_rows(self, probes, cand_off, sizes, slots):
         """Candidate-row slot index -> list-sorted code row."""
@@ -330,12 +452,13 @@ class IVFPQIndex:
         return info
 
     @classmethod
-    def load(cls, out_dir, device=None) -> "IVFPQIndex":
+    def load(cls, out_dir, device=None, search: str = "auto") -> "IVFPQIndex":
         out = Path(out_dir)
         info = json.loads((out / "ivfpq_info.json").read_text())
         cent = np.load(out / "ivfpq_centroids.npy")
         cb = np.load(out / "ivfpq_codebooks.npy")
-        idx = cls(dim=info["embed_dim"], nlist=cent.shape[0], m=cb.shape[0], nprobe=info.get("nprobe", 64), device=device)
+        idx = cls(dim=info["embed_dim"], nlist=cent.shape[0], m=cb.shape[0], nprobe=info.get("nprobe", 64), device=device,
+                  search=search)
         idx.centroids = torch.from_numpy(cent).to(idx.device)
         idx.codebooks = torch.from_numpy(cb).to(idx.device)
         codes = torch.from_numpy(np.load(out / "ivfpq_codes.npy")).to(idx.device)

@@ -16,6 +16,8 @@ recall figures against the exact ranking: ``recall@10`` = |approx top-10 ∩ exa
 (strict) and ``R@10`` = fraction of queries whose exact nearest neighbour is in the approx top-10
 (the FAISS convention the reference's "~95 % recall@10" uses).  One JSON line per (N, tier, nprobe), and with the
 pq96 tier one ``"stage": "pq_build"`` line: ``IVFPQIndex.add`` with ``build="torch"`` against ``build="fused"``.
+With the pq96 and compressed tiers one ``"stage": "pq_search"`` line per (N, m, Q, k): ``IVFPQIndex.search`` with
+``search="scan"`` against ``search="fused"`` (``--pq-search-only`` prints these lines alone).
 Usage: ``python tools/search_bench.py --n 10000000,58000000``
 """
 import argparse
@@ -131,6 +133,51 @@ def pq_build_times(pq, x, reps=3):
             "codes_equal": round(int((raws["torch"] == raws["fused"]).sum()) / raws["torch"].numel(), 6)}
 
 
+def pq_search_arms(pq):
+    """``pq``'s trained, filled index behind ``search="scan"`` and ``search="fused"`` (shared tensors)."""
+    from bioengine_worker_amd.search.ivfpq import IVFPQIndex
+
+    arms = {}
+    for mode in ("scan", "fused"):
+        idx = IVFPQIndex(pq.dim, pq.nlist, pq.m, pq.nprobe, pq.device, search=mode)
+        idx.centroids, idx.codebooks, idx.codes, idx.ids, idx.list_off = (pq.centroids, pq.codebooks, pq.codes, pq.ids,
+                                                                          pq.list_off)
+        idx.ntotal = pq.ntotal
+        arms[mode] = idx
+    return arms
+
+
+def pq_search_times(pq, q, gt, qs=(1, 64), ks=(20, 80, 1000), reps=20):
+    """``IVFPQIndex.search`` with ``search="scan"`` against ``search="fused"`` on ``pq``'s index: the host clock around
+    the whole call (it ends in the copy of the results, which synchronises), both arms warmed twice on every
+    shape, then alternating; per arm the median and the spread (90th minus 10th percentile) of ``reps`` calls,
+    the share of queries whose score lists are bit-equal, and both arms' recall against ``gt``.  One dict per (Q, k)."""
+    arms = pq_search_arms(pq)
+    out = []
+    for Q in qs:
+        for k in ks:
+            qq = q[:Q]
+            ts = {a: [] for a in arms}
+            res = {}
+            for r in range(reps + 2):
+                for a, idx in arms.items():
+                    torch.cuda.synchronize()
+                    t = time.perf_counter()
+                    res[a] = idx.search(qq, k)
+                    if r >= 2:
+                        ts[a].append((time.perf_counter() - t) * 1e3)
+            st = {a: (np.median(v), np.percentile(v, 90) - np.percentile(v, 10)) for a, v in ts.items()}
+            same = (res["scan"][0].view(np.uint32) == res["fused"][0].view(np.uint32)).all(1)
+            rec = {a: recalls(gt[:Q], res[a][1]) for a in arms}
+            out.append({"n": pq.ntotal, "stage": "pq_search", "m": pq.m, "nlist": pq.nlist, "nprobe": pq.nprobe, "Q": Q,
+                        "k": k, "scan_ms": round(st["scan"][0], 3), "fused_ms": round(st["fused"][0], 3),
+                        "scan_spread_ms": round(st["scan"][1], 3), "fused_spread_ms": round(st["fused"][1], 3),
+                        "scan_over_fused": round(st["scan"][0] / st["fused"][0], 2),
+                        "score_lists_equal": round(float(same.mean()), 4),
+                        "recall@10": {a: rec[a][0] for a in arms}, "R@10": {a: rec[a][1] for a in arms}})
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", default="1000000,10000000")
@@ -145,6 +192,8 @@ def main():
     ap.add_argument("--refines", default="400,1000,2000", help="compressed tier: re-ranked candidates per query")
     ap.add_argument("--queries", default="near,ood", help="near: indexed vectors + small noise; "
                     "ood: held-out sub-centres of the indexed classes (ood_queries)")
+    ap.add_argument("--pq-search-only", action="store_true", help="only the pq_search lines (scan against fused search)")
+    ap.add_argument("--pq-ms", default="96,192", help="--pq-search-only: the PQ sizes")
     a = ap.parse_args()
     from bioengine_worker_amd.search.index import VectorIndex
     from bioengine_worker_amd.search.ivfpq import IVFPQIndex, default_nlist
@@ -172,6 +221,17 @@ def main():
             ts, j = torch.topk(torch.cat(gs, 1), a.k, dim=1)
             gts[qn] = torch.gather(torch.cat(gi, 1), 1, j).cpu().numpy()
         q = next(iter(qsets.values()))
+        if a.pq_search_only:  # the pq_search lines alone: the m = 96 index and the compressed tier's m = 192
+            for m in [int(v) for v in a.pq_ms.split(",")]:
+                pq = IVFPQIndex(dim=a.dim, nlist=default_nlist(n), m=m, nprobe=64, device=dev)
+                pq.train(x.float() if n <= 2_000_000 else x[torch.randperm(n, device=dev)[:2_000_000]].float())
+                for i in range(0, n, 1 << 22):
+                    pq.add(x[i:i + (1 << 22)])
+                for line in pq_search_times(pq, q, next(iter(gts.values())), reps=a.reps):
+                    print(json.dumps(line), flush=True)
+                del pq
+                torch.cuda.empty_cache()
+            continue
         for name, fn in (("flat_q1", lambda: flat.search(q[:1], a.k)), ("flat_q64", lambda: flat.search(q, a.k))):
             fn()
             p50, p95 = timeit(fn, a.reps)
@@ -214,6 +274,8 @@ def main():
             fp = cvi.compress(pq_m=192, refine=50)
             torch.cuda.synchronize()
             build = time.perf_counter() - t0
+            for line in pq_search_times(cvi.pq, q, next(iter(gts.values())), reps=a.reps):
+                print(json.dumps(line), flush=True)
             for R in [int(v) for v in a.refines.split(",")]:
                 cvi.refine = max(1, R // a.k)
                 rec = {qn: recalls(gts[qn], cvi.search(qv, a.k)[1]) for qn, qv in qsets.items()}
@@ -244,6 +306,8 @@ def main():
         torch.cuda.synchronize()
         build = time.perf_counter() - t0
         print(json.dumps(pq_build_times(pq, x)), flush=True)
+        for line in pq_search_times(pq, q, next(iter(gts.values())), reps=a.reps):
+            print(json.dumps(line), flush=True)
         for refine, tier in ((0, "IVFPQ-GPU m=96 nprobe=64"), (4, "IVFPQ-GPU + exact rerank 80"),
                              (200, "IVFPQ-GPU + exact rerank 4k")):
             vi = VectorIndex(dim=a.dim, device=dev, index_type="ivfpq", refine=refine)
