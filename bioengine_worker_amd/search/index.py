@@ -53,7 +53,7 @@ class VectorIndex:
 
     def __init__(self, dim: int = 768, device=None, ivf_threshold: int = 5_000_000, nprobe: int = 64,
                  index_type: str = "auto", ivfpq_threshold: int = 50_000_000, pq_m: int = 96, refine: int = 4,
-                 pq_build: str = "auto", pq_search: str = "auto"):
+                 pq_build: str = "auto", pq_search: str = "auto", pq_coarse: str = "auto"):
         self.lvecs: torch.Tensor | None = None
         self.dim = dim
         self.refine = refine  # IVF-PQ: re-rank refine*k PQ candidates with the stored vectors (0 = off)
@@ -62,6 +62,7 @@ class VectorIndex:
         self.pq_m = pq_m
         self.pq_build = pq_build  # IVFPQIndex(build=...): "auto", "torch" or "fused" (csrc/kernels/pq_build.hip)
         self.pq_search = pq_search  # IVFPQIndex(search=...): "auto", "scan" or "fused" (csrc/kernels/ivfpq_search.hip)
+        self.pq_coarse = pq_coarse  # IVFPQIndex(coarse=...): "auto", "torch" or "fused" (csrc/kernels/coarse_assign.hip)
         self.pq = None
         self.device = torch.device(device) if device is not None else (
             torch.device("cuda") if torch.cuda.is_available() else torch.device("cpu"))
@@ -112,7 +113,8 @@ class VectorIndex:
 
         n = self.ntotal
         nl = nlist or min(default_nlist(n), max(1, n // 39))
-        pq = IVFPQIndex(self.dim, nl, self.pq_m, self.nprobe, self.device, build=self.pq_build, search=self.pq_search)
+        pq = IVFPQIndex(self.dim, nl, self.pq_m, self.nprobe, self.device, build=self.pq_build, search=self.pq_search,
+                        coarse=self.pq_coarse)
         g = torch.Generator(device="cpu").manual_seed(0)
         sample = self.vecs[torch.randperm(n, generator=g)[: min(n, max(262_144, 39 * nl))].to(self.vecs.device)]
         pq.train(sample.float())

@@ -22,8 +22,13 @@ MI355X design:
 Build: ``build="torch"`` is the torch code below (batched ``bmm`` distances, ``argmin``); ``"fused"`` runs the PQ
 codebook iterations and the residual encoding in ``csrc/kernels/pq_build.hip`` (``be_pq_kmeans_step``,
 ``be_pq_encode``: fp32 MFMA scores with the argmin inside the kernel, rows read in their stored dtype);
-``"auto"`` takes the kernels on a GPU device when the library is loaded and ``D/m`` is 4 or 8.  The coarse
-assignment and the coarse k-means are torch on every path.
+``"auto"`` takes the kernels on a GPU device when the library is loaded and ``D/m`` is 4 or 8.
+
+Coarse quantizer (the nearest centroid of every row in ``add``, in the coarse k-means iterations and for the PQ
+sample of ``train``): ``coarse="torch"`` is an fp32 ``x @ centroids.T`` and ``argmax``; ``"fused"``
+(``csrc/kernels/coarse_assign.hip``) takes the best two split-bf16 MFMA scores per row inside the kernel, keeps the
+rows whose gap proves the argmax (:func:`coarse_certificate_eps`) and gives the others to the torch rule; the
+k-means update (``index_add_``) stays torch.  ``"auto"``: see :meth:`IVFPQIndex.fused_coarse`.
 
 Everything has a CPU path (same math in torch) that the GPU kernel is tested against.
 """
@@ -39,13 +44,14 @@ import torch
 from ..ops import _native
 
 
-def _kmeans(x: torch.Tensor, k: int, iters: int, g: torch.Generator, spherical: bool) -> torch.Tensor:
+def _kmeans(x: torch.Tensor, k: int, iters: int, g: torch.Generator, spherical: bool, assign=None) -> torch.Tensor:
+    """``assign(x, cent) -> [n] int64``: the spherical assignment, :func:`_argmax_ip` by default."""
     cent = x[torch.randperm(x.shape[0], generator=g)[:k].to(x.device)].clone()
     for _ in range(iters):
         if spherical:
             from .index import _argmax_ip
 
-            a = _argmax_ip(x, cent)
+            a = (assign or _argmax_ip)(x, cent)
         else:
             a = torch.cdist(x, cent).argmin(1)
         new = torch.zeros_like(cent).index_add_(0, a, x)
@@ -155,6 +161,100 @@ def _pq_train_fused(res: torch.Tensor, m: int, iters: int, g: torch.Generator) -
     return cb
 
 
+# ------------------------------------------------------------------------------- coarse quantizer (coarse_assign.hip)
+PQ_COARSES = ("auto", "torch", "fused")
+
+
+def coarse_fused_supported(dim: int) -> bool:
+    """Row lengths ``be_coarse_top2`` serves: whole 32-element MFMA steps, up to 8192."""
+    return 32 <= dim <= 8192 and dim % 32 == 0
+
+
+def coarse_certificate_eps(d: int, parts: int) -> float:
+    """How far the coarse score of ``be_coarse_top2`` can lie from the exact real inner product of a unit row and a
+    unit centroid: ``(2 parts - 3) 2^-18 (1 + 2^-8) + (2 parts + 1) d 2^-24 + 128 * 2^-24``.  ``parts = 2``: bf16 rows,
+    ``3``: fp32 rows.  With ``u = 2^-24``:
+
+    * The split: ``c = hi + lo + r`` with ``|c - hi| <= 2^-9 |c|`` and ``|r| <= 2^-18 |c|`` per element (bf16 keeps 8
+      significand bits, twice; ``c - hi`` is exact in fp32).  A bf16 row is its own ``hi``, so the sum ``x.hi + x.lo``
+      drops only ``x.r``: ``<= 2^-18`` by Cauchy-Schwarz.  An fp32 row is split the same way and the sum
+      ``x_hi.c_hi + x_hi.c_lo + x_lo.c_hi`` drops ``x_lo.c_lo``, ``(x_hi + x_lo).r_c`` and ``r_x.c``: each
+      ``<= 2^-18 (1 + 2^-9)^2``.  That is ``2 parts - 3`` terms of at most ``2^-18 (1 + 2^-8)``.
+    * The sum: its ``parts * d`` products of two bf16 values are exact in fp32.  Accumulating them in fp32, in
+      whatever order the matrix unit uses, costs at most ``parts * d`` roundings of a partial sum that is bounded by
+      the sum of the magnitudes, ``<= (1 + 2^-9)^2 (1 + 2^-8) < 1 + 2^-6`` (Cauchy-Schwarz per part).  The unit's adder
+      is not documented to round to nearest, so a rounding is taken as a whole ulp, ``2 u``:
+      ``2 parts d u (1 + 2^-6) / (1 - 2 parts d u) < (2 parts + 1) d u`` for ``d <= 8192``.
+    * ``128 u`` of slack: the bound in use is ``eps |x| max|c|`` with norms computed in fp32 (each within
+      ``(d / 2 + 2) u`` of the real one, relatively, in any summation order: the square root halves the sum's
+      ``d u``), fp32 products and an fp32 ``s1 - s2``; against an ``eps`` below ``2^-7`` these are under
+      ``(d + 8) 2^-7 u < 128 u``."""
+    if parts not in (2, 3):
+        raise ValueError("parts is 2 (bf16 rows) or 3 (fp32 rows)")
+    return (2 * parts - 3) * 2.0 ** -18 * (1 + 2.0 ** -8) + ((2 * parts + 1) * d + 128) * 2.0 ** -24
+
+
+def _coarse_top2(x: torch.Tensor, centroids: torch.Tensor):
+    """:func:`coarse_top2_fused` and, as a device scalar, the largest centroid norm ``be_coarse_split`` found."""
+    if not (x.is_cuda and centroids.is_cuda and _native.hip_available()):
+        raise _native.NativeUnavailable("be_coarse_top2 needs GPU tensors and the native kernel library")
+    if (x.dim() != 2 or centroids.dim() != 2 or x.shape[1] != centroids.shape[1] or not coarse_fused_supported(x.shape[1])
+            or not 1 <= x.shape[0] < 2 ** 31 or not 1 <= centroids.shape[0] < 2 ** 31):
+        raise _native.NativeUnavailable("be_coarse_top2 serves x [n >= 1, D] against centroids [nlist >= 1, D] with "
+                                        "D % 32 == 0, D <= 8192 and fewer than 2^31 of each")
+    if x.dtype not in (torch.float32, torch.bfloat16):
+        x = x.float()
+    x = x.contiguous()
+    cent = centroids.to(x.device, torch.float32).contiguous()
+    n, D = x.shape
+    nlist = cent.shape[0]
+    image = torch.empty(nlist, 2 * D, dtype=torch.bfloat16, device=x.device)
+    cmax = torch.zeros(1, dtype=torch.float32, device=x.device)
+    i1 = torch.empty(n, dtype=torch.int32, device=x.device)
+    s1 = torch.empty(n, dtype=torch.float32, device=x.device)
+    s2 = torch.empty(n, dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        _native.call("be_coarse_split", _native.ptr(cent), nlist, D, _native.ptr(image), _native.ptr(cmax),
+                     _native.stream(x.device))
+        _native.call("be_coarse_top2", _native.ptr(x), int(x.dtype == torch.bfloat16), _native.ptr(image), n, nlist, D,
+                     _native.ptr(i1), _native.ptr(s1), _native.ptr(s2), _native.stream(x.device))
+    return i1, s1, s2, cmax
+
+
+def coarse_top2_fused(x: torch.Tensor, centroids: torch.Tensor):
+    """``be_coarse_split`` + ``be_coarse_top2``: ``x [n, D]`` bfloat16 or float32, ``centroids [nlist, D]`` -> per row
+    ``(i1 int32, s1 fp32, s2 fp32)``: the column of the largest coarse score under (score descending, index
+    ascending), that score, and the largest coarse score among the other columns (``-inf`` at ``nlist == 1``).  The
+    coarse score is one fp32 MFMA accumulator over ``x.c_hi + x.c_lo`` (bf16 rows) or ``x_hi.c_hi + x_hi.c_lo +
+    x_lo.c_hi`` (fp32 rows).  No score reaches HBM, nothing is read back."""
+    return _coarse_top2(x, centroids)[:3]
+
+
+def coarse_assign_fused(x: torch.Tensor, centroids: torch.Tensor):
+    """Nearest centroid by inner product -> ``(assign int64 [n], fallback_rows)``.  A row is certified when
+    ``s1 - s2 > 2 eps |x| max|c|`` (:func:`coarse_certificate_eps`): every score is within ``eps |x| max|c|`` of the
+    exact one, so no other centroid can have a larger exact score and ``i1`` is the true argmax.  The other rows
+    (near-ties, exact ties, duplicate centroids) are gathered and get ``_argmax_ip`` of their fp32 values, the torch
+    rule: one host read of their count per call."""
+    from .index import _argmax_ip
+
+    i1, s1, s2, cmax = _coarse_top2(x, centroids)
+    eps = coarse_certificate_eps(x.shape[1], 2 if x.dtype == torch.bfloat16 else 3)
+    bound = torch.linalg.vector_norm(x, dim=1, dtype=torch.float32) * cmax * (2.0 * eps)
+    rows = torch.nonzero(~(s1 - s2 > bound)).squeeze(1)  # a NaN score is not certified either
+    assign = i1.long()
+    if rows.numel():
+        assign[rows] = _argmax_ip(x[rows].float(), centroids.to(x.device, torch.float32))
+    return assign, int(rows.numel())
+
+
+def _auto_coarse(nlist: int, dim: int) -> bool:
+    """The shapes at which ``coarse="auto"`` takes the fused path: those between the measured ones, at all of which it
+    was faster than ``"torch"`` by more than both arms' spread (README, "IVF-PQ coarse quantizer": D = 768, 4 096 and
+    12 649 lists, bf16 rows in ``add`` and fp32 rows in ``train``)."""
+    return dim == 768 and 4096 <= nlist <= 12649
+
+
 # ------------------------------------------------------------------------------- fused search (ivfpq_search.hip)
 PQ_SEARCHES = ("auto", "scan", "fused")
 PQ_SEARCH_M = (16, 32, 48, 64, 96, 128, 192)  # table sizes be_ivfpq_scan_topk is instantiated for
@@ -229,16 +329,20 @@ def ivfpq_scan_topk_fused(lut_half: torch.Tensor, base: torch.Tensor, probes: to
 class IVFPQIndex:
     """Approximate inner-product index; vectors should be L2-normalised (cosine).  ``build``: how the PQ
     codebooks are trained and the rows encoded, one of ``PQ_BUILDS``; ``search``: how the probed lists are scanned,
-    one of ``PQ_SEARCHES`` (module docstring)."""
+    one of ``PQ_SEARCHES``; ``coarse``: how rows find their list in ``train`` / ``add``, one of ``PQ_COARSES`` (module
+    docstring).  ``coarse_fallback_rows`` counts the rows the fused coarse quantizer could not certify and
+    recomputed by the torch rule."""
 
     def __init__(self, dim: int = 768, nlist: int = 4096, m: int = 96, nprobe: int = 64, device=None,
-                 build: str = "auto", search: str = "auto"):
+                 build: str = "auto", search: str = "auto", coarse: str = "auto"):
         if dim % m or m % 16:
             raise ValueError("dim must be divisible by m, and m a multiple of 16")
         if build not in PQ_BUILDS:
             raise ValueError(f"build must be one of {PQ_BUILDS}")
         if search not in PQ_SEARCHES:
             raise ValueError(f"search must be one of {PQ_SEARCHES}")
+        if coarse not in PQ_COARSES:
+            raise ValueError(f"coarse must be one of {PQ_COARSES}")
         self.dim, self.nlist, self.m, self.nprobe = dim, nlist, m, nprobe
         self.device = torch.device(device) if device is not None else (
             torch.device("cuda") if torch.cuda.is_available() else torch.device("cpu"))
@@ -254,6 +358,9 @@ class IVFPQIndex:
         self.fused_build  # "fused" where the kernels cannot run: raise now, not in the middle of a build
         self.search_mode = search
         self.fused_search(1, 1)  # the same for search="fused"
+        self.coarse = coarse
+        self.coarse_fallback_rows = 0
+        self.fused_coarse(nlist)  # and for coarse="fused"
 
     @property
     def fused_build(self) -> bool:
@@ -281,6 +388,29 @@ class IVFPQIndex:
             return True
         return ok and k <= PQ_SEARCH_MAX_K and _auto_fused(self.m, Q, k)
 
+    def fused_coarse(self, nlist: int) -> bool:
+        """Whether an assignment against ``nlist`` centroids runs on ``coarse_assign.hip``.  ``"fused"``: always, or it
+        raises; ``"auto"``: where the kernels can run and ``_auto_coarse`` holds."""
+        if self.coarse == "torch":
+            return False
+        ok = self.device.type == "cuda" and coarse_fused_supported(self.dim) and _native.hip_available()
+        if self.coarse == "fused":
+            if not ok:
+                raise _native.NativeUnavailable("coarse='fused' needs a GPU device, the native kernel library and "
+                                                "dim % 32 == 0, dim <= 8192")
+            return True
+        return ok and _auto_coarse(nlist, self.dim)
+
+    def _coarse_assign(self, x: torch.Tensor, cent: torch.Tensor) -> torch.Tensor:
+        """Nearest centroid of the rows ``x`` (fp32, or bf16 as stored) -> int64 ``[n]``."""
+        if self.fused_coarse(cent.shape[0]):
+            a, fallback = coarse_assign_fused(x, cent)
+            self.coarse_fallback_rows += fallback
+            return a
+        from .index import _argmax_ip
+
+        return _argmax_ip(x.float(), cent)
+
     @property
     def index_type(self) -> str:
         return f"IVFPQ-GPU(nlist={self.nlist}, m={self.m}, nbits=8)"
@@ -292,13 +422,12 @@ class IVFPQIndex:
         g = torch.Generator().manual_seed(seed)
         n = x.shape[0]
         sample = x[torch.randperm(n, generator=g)[: min(n, max(max_sample, 39 * self.nlist))].to(self.device)]
-        self.centroids = _kmeans(sample, min(self.nlist, sample.shape[0]), iters, g, spherical=True)
+        self.centroids = _kmeans(sample, min(self.nlist, sample.shape[0]), iters, g, spherical=True,
+                                 assign=self._coarse_assign)
         self.nlist = self.centroids.shape[0]
         self.list_off = torch.zeros(self.nlist + 1, dtype=torch.int64, device=self.device)
         ps = sample[:pq_sample]  # PQ codebooks: 256 centroids per sub-space need far fewer points
-        from .index import _argmax_ip
-
-        a = _argmax_ip(ps, self.centroids)
+        a = self._coarse_assign(ps, self.centroids)
         self.codebooks = (_pq_train_fused if self.fused_build else _pq_train)(ps - self.centroids[a], self.m, pq_iters, g)
 
     def add(self, x, chunk: int = 1 << 18) -> None:
@@ -307,15 +436,12 @@ class IVFPQIndex:
         fused = self.fused_build
         assigns, codes = [], []
         for i in range(0, x.shape[0], chunk):
-            from .index import _argmax_ip
-
             if fused and x.dtype == torch.bfloat16:
-                # the kernel reads the stored bf16 rows; only the coarse assignment sees an fp32 copy of the chunk
+                # the kernels read the stored bf16 rows; only a torch coarse assignment sees an fp32 copy of the chunk
                 xs = x[i:i + chunk].to(self.device)
-                a = _argmax_ip(xs.float(), self.centroids)
             else:
                 xs = x[i:i + chunk].to(self.device, torch.float32)
-                a = _argmax_ip(xs, self.centroids)
+            a = self._coarse_assign(xs, self.centroids)
             if fused:
                 codes.append(pq_encode_fused(xs, self.centroids, a, self.codebooks))
             else:

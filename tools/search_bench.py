@@ -15,7 +15,8 @@ and reports p50 / p95 latency of one query and of a 64-query batch (top-20), bui
 recall figures against the exact ranking: ``recall@10`` = |approx top-10 ∩ exact top-10| / 10
 (strict) and ``R@10`` = fraction of queries whose exact nearest neighbour is in the approx top-10
 (the FAISS convention the reference's "~95 % recall@10" uses).  One JSON line per (N, tier, nprobe), and with the
-pq96 tier one ``"stage": "pq_build"`` line: ``IVFPQIndex.add`` with ``build="torch"`` against ``build="fused"``.
+pq96 tier one ``"stage": "pq_build"`` line: ``IVFPQIndex.add`` with ``build="torch"`` against ``build="fused"``, and
+the coarse quantizer arms ``coarse="torch"`` against ``"fused"`` (``--pq-build-only`` prints this line alone).
 With the pq96 and compressed tiers one ``"stage": "pq_search"`` line per (N, m, Q, k): ``IVFPQIndex.search`` with
 ``search="scan"`` against ``search="fused"`` (``--pq-search-only`` prints these lines alone).
 Usage: ``python tools/search_bench.py --n 10000000,58000000``
@@ -84,7 +85,7 @@ def pq_build_times(pq, x, reps=3):
     from bioengine_worker_amd.search.ivfpq import IVFPQIndex
 
     def arm(build):
-        idx = IVFPQIndex(pq.dim, pq.nlist, pq.m, pq.nprobe, pq.device, build=build)
+        idx = IVFPQIndex(pq.dim, pq.nlist, pq.m, pq.nprobe, pq.device, build=build, coarse="torch")
         idx.centroids, idx.codebooks = pq.centroids, pq.codebooks
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         torch.cuda.synchronize()
@@ -131,6 +132,69 @@ def pq_build_times(pq, x, reps=3):
             "torch_spread_ms": round(max(ts["torch"]) - min(ts["torch"]), 2),
             "fused_spread_ms": round(max(ts["fused"]) - min(ts["fused"]), 2),
             "codes_equal": round(int((raws["torch"] == raws["fused"]).sum()) / raws["torch"].numel(), 6)}
+
+
+def _alternate(fns, reps):
+    """Device-event times (ms) of the calls ``fns[name]()``: every arm once as a warm-up, then alternating ``reps``
+    times -> per arm (median, max - min, the last call's result)."""
+    ts, res = {b: [] for b in fns}, {}
+    for r in range(reps + 1):
+        for b, fn in fns.items():
+            res[b] = None  # the previous result of this arm is freed before the next call
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            e0.record()
+            res[b] = fn()
+            e1.record()
+            e1.synchronize()
+            if r:
+                ts[b].append(e0.elapsed_time(e1))
+    return {b: (sorted(v)[len(v) // 2], max(v) - min(v), res[b]) for b, v in ts.items()}
+
+
+def pq_coarse_times(pq, x, train_rows, reps=3):
+    """The coarse quantizer arms, ``coarse="torch"`` against ``"fused"`` (``csrc/kernels/coarse_assign.hip``), with
+    ``build="fused"`` and ``pq``'s trained centroids and codebooks on both: ``IVFPQIndex.add(x)``, the assignment
+    alone on one chunk of ``add`` (2^18 stored rows; useful flop ``2 n nlist D`` over the time, the fused arm with its
+    fallback recomputation, and the kernels alone), ``IVFPQIndex.train`` on ``train_rows``; the fused arm's share of
+    fallback rows and the rows whose list differs between the arms."""
+    from bioengine_worker_amd.search import ivfpq
+    from bioengine_worker_amd.search.index import _argmax_ip
+
+    def new(coarse):
+        return ivfpq.IVFPQIndex(pq.dim, pq.nlist, pq.m, pq.nprobe, pq.device, build="fused", coarse=coarse)
+
+    def add(coarse):
+        idx = new(coarse)
+        idx.centroids, idx.codebooks = pq.centroids, pq.codebooks
+        idx.add(x)
+        return idx._assign, idx.coarse_fallback_rows
+
+    def train(coarse):
+        idx = new(coarse)
+        idx.train(train_rows)
+        return idx.coarse_fallback_rows
+
+    arms = ("torch", "fused")
+    ad = _alternate({b: (lambda b=b: add(b)) for b in arms}, reps)
+    differ = int((ad["torch"][2][0] != ad["fused"][2][0]).sum())
+    fallback = ad["fused"][2][1]
+    xc = x[: 1 << 18]
+    asg = _alternate({"torch": lambda: _argmax_ip(xc.float(), pq.centroids),
+                      "fused": lambda: ivfpq.coarse_assign_fused(xc, pq.centroids)[0],
+                      "kernels": lambda: ivfpq.coarse_top2_fused(xc, pq.centroids)[0]}, max(reps, 5))
+    tr = _alternate({b: (lambda b=b: train(b)) for b in arms}, max(1, reps - 1))
+    flop = 2.0 * xc.shape[0] * pq.nlist * pq.dim
+    out = {"coarse_assign_rows": int(xc.shape[0]), "coarse_differing_rows": differ,
+           "coarse_fallback_share": round(fallback / x.shape[0], 6), "coarse_train_rows": int(train_rows.shape[0]),
+           "coarse_train_fallback_rows": int(tr["fused"][2])}
+    for b in arms:
+        out.update({f"add_coarse_{b}_ms": round(ad[b][0], 2), f"add_coarse_{b}_spread_ms": round(ad[b][1], 2),
+                    f"train_coarse_{b}_ms": round(tr[b][0], 1), f"train_coarse_{b}_spread_ms": round(tr[b][1], 1)})
+    for b in asg:
+        out.update({f"assign_{b}_ms": round(asg[b][0], 3), f"assign_{b}_spread_ms": round(asg[b][1], 3),
+                    f"assign_{b}_tflops": round(flop / asg[b][0] * 1e-9, 1)})
+    return out
 
 
 def pq_search_arms(pq):
@@ -194,6 +258,7 @@ def main():
                     "ood: held-out sub-centres of the indexed classes (ood_queries)")
     ap.add_argument("--pq-search-only", action="store_true", help="only the pq_search lines (scan against fused search)")
     ap.add_argument("--pq-ms", default="96,192", help="--pq-search-only: the PQ sizes")
+    ap.add_argument("--pq-build-only", action="store_true", help="only the pq_build line (build and coarse arms)")
     a = ap.parse_args()
     from bioengine_worker_amd.search.index import VectorIndex
     from bioengine_worker_amd.search.ivfpq import IVFPQIndex, default_nlist
@@ -201,6 +266,14 @@ def main():
     dev = torch.device("cuda", 0)
     for n in [int(v) for v in a.n.split(",")]:
         x = synth(n, a.dim, dev)
+        if a.pq_build_only:
+            pq = IVFPQIndex(dim=a.dim, nlist=default_nlist(n), m=96, nprobe=64, device=dev)
+            train_rows = x.float() if n <= 2_000_000 else x[torch.randperm(n, device=dev)[:2_000_000]].float()
+            pq.train(train_rows)
+            print(json.dumps({**pq_build_times(pq, x), **pq_coarse_times(pq, x, train_rows)}), flush=True)
+            del x, pq, train_rows
+            torch.cuda.empty_cache()
+            continue
         gq = torch.Generator(device=dev).manual_seed(7)
         qidx = torch.randint(0, n, (64,), device=dev, generator=gq)
         qsets = {"near": torch.nn.functional.normalize(
@@ -301,11 +374,13 @@ def main():
         t0 = time.perf_counter()
         npl = default_nlist(n)
         pq = IVFPQIndex(dim=a.dim, nlist=npl, m=96, nprobe=64, device=dev)
-        pq.train(x.float() if n <= 2_000_000 else x[torch.randperm(n, device=dev)[:2_000_000]].float())
+        train_rows = x.float() if n <= 2_000_000 else x[torch.randperm(n, device=dev)[:2_000_000]].float()
+        pq.train(train_rows)
         pq.add(x)
         torch.cuda.synchronize()
         build = time.perf_counter() - t0
-        print(json.dumps(pq_build_times(pq, x)), flush=True)
+        print(json.dumps({**pq_build_times(pq, x), **pq_coarse_times(pq, x, train_rows)}), flush=True)
+        del train_rows
         for line in pq_search_times(pq, q, next(iter(gts.values())), reps=a.reps):
             print(json.dumps(line), flush=True)
         for refine, tier in ((0, "IVFPQ-GPU m=96 nprobe=64"), (4, "IVFPQ-GPU + exact rerank 80"),
