@@ -46,6 +46,68 @@ def _argmax_ip(x: torch.Tensor, cent: torch.Tensor, budget: int = 1 << 30) -> to
     return torch.cat([(x[i:i + rows] @ cent.T).argmax(1) for i in range(0, x.shape[0], rows)])
 
 
+# ------------------------------------------------------------------------------- fused IVF-Flat search (ivf_scan_topk.hip)
+IVF_SEARCHES = ("auto", "scan", "fused")
+IVF_SEARCH_CH = (1, 2, 3, 4, 6, 8)  # dim / 128 be_ivf_scan_bf16 and be_ivf_scan_topk are instantiated for
+IVF_SEARCH_MAX_K = 1024
+_IVF_SEARCH_BLOCKS = 512  # workgroups of a scan: two per CU, the occupancy the kernel is built for
+
+
+def ivf_splits(Q: int, kk: int) -> int:
+    """Slot ranges per query of ``be_ivf_scan_topk``, from the call's shape alone: about ``_IVF_SEARCH_BLOCKS``
+    workgroups over all queries, and partial lists of at most 2^20 keys per query.  Measured at D = 768, nprobe 64
+    (device time of scan + merge + the wrapper's index arithmetic, us, at 1 M / 10 M rows): one query, kk = 20:
+    137 / 195 at P = 16, 99 / 112 at 64, 96 / 105 at 256, 108 / 89 at 512, 94 / 96 at 1024, 113 / 112 at 2048;
+    kk = 1000: 182 / 273 at 64, 167 / 238 at 256, 166 / 232 at 512, 184 / 246 at 1024; 64 queries, kk = 20:
+    488 / 1520 at P = 2, 315 / 993 at 4, 310 / 945 at 8, 312 / 920 at 16, 315 / 900 at 32, 335 / 881 at 64;
+    kk = 1000: 463 / 1154 at 4, 443 / 1080 at 8, 450 / 1105 at 16, 463 / 1178 at 32."""
+    return max(1, min(_IVF_SEARCH_BLOCKS // max(Q, 1), (1 << 20) // kk))
+
+
+def _auto_ivf_fused(dim: int, n: int, Q: int, k: int) -> bool:
+    """The shapes at which ``ivf_search="auto"`` takes the fused path: those between the measured ones at which it
+    was faster than ``"scan"`` by more than both arms' spread (README, "IVF-Flat search": D = 768, 1 M and 10 M rows,
+    1 and 64 queries, k = 20 and 80; at k = 1000 the gap at 10 M rows and one query was inside the scan arm's spread)."""
+    return dim == 768 and 1_000_000 <= n <= 10_000_000 and Q <= 64 and k <= 80
+
+
+def ivf_scan_topk_fused(q: torch.Tensor, probes: torch.Tensor, list_off: torch.Tensor, lvecs: torch.Tensor,
+                        sorted_ids: torch.Tensor, kk: int, splits: int | None = None):
+    """``be_ivf_scan_topk`` + ``be_ivf_merge``: the ``kk`` best exact inner products of ``q [Q, D]`` (fp32) with the
+    rows of the probed lists in the list-sorted bf16 ``lvecs [N, D]``, ordered by (score descending, list-sorted row
+    ascending) -> ``(scores [Q, kk] fp32, ids [Q, kk] int64)`` on the device, rows mapped through ``sorted_ids``,
+    ``-inf`` / ``-1`` in empty slots.  A score is bit-equal to the one ``be_ivf_scan_bf16`` writes for that row.
+    ``splits`` forces the slot ranges per query (:func:`ivf_splits`).  Nothing is read back."""
+    from ..ops import _native
+
+    t = (q, probes, list_off, lvecs, sorted_ids)
+    if not (all(x.is_cuda for x in t) and _native.hip_available()):
+        raise _native.NativeUnavailable("be_ivf_scan_topk needs GPU tensors and the native kernel library")
+    if (q.dim() != 2 or probes.dim() != 2 or lvecs.dim() != 2 or probes.shape[0] != q.shape[0]
+            or lvecs.shape[1] != q.shape[1] or q.shape[1] % 128 or q.shape[1] // 128 not in IVF_SEARCH_CH
+            or lvecs.dtype != torch.bfloat16 or not 1 <= kk <= IVF_SEARCH_MAX_K or lvecs.shape[0] >= 2 ** 31
+            or probes.shape[1] < 1 or sorted_ids.shape[0] != lvecs.shape[0]):
+        raise _native.NativeUnavailable(f"be_ivf_scan_topk serves bf16 rows of dim / 128 in {IVF_SEARCH_CH}, "
+                                        f"1 <= kk <= {IVF_SEARCH_MAX_K}, fewer than 2^31 rows and nprobe >= 1")
+    Q, nprobe = probes.shape
+    dev = lvecs.device
+    list_off = list_off.long().contiguous()
+    sizes = (list_off[1:] - list_off[:-1])[probes]  # [Q, nprobe]
+    cand_off = (torch.cumsum(sizes, 1) - sizes).contiguous()
+    P = int(splits) if splits else ivf_splits(Q, kk)
+    part_s = torch.empty(Q, P, kk, dtype=torch.float32, device=dev)
+    part_r = torch.empty(Q, P, kk, dtype=torch.int32, device=dev)
+    out_s = torch.empty(Q, kk, dtype=torch.float32, device=dev)
+    out_i = torch.empty(Q, kk, dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        _native.call("be_ivf_scan_topk", _native.ptr(q.float().contiguous()), _native.ptr(probes.int().contiguous()),
+                     _native.ptr(list_off), _native.ptr(cand_off), _native.ptr(lvecs.contiguous()), lvecs.shape[0], Q,
+                     nprobe, q.shape[1], kk, P, _native.ptr(part_s), _native.ptr(part_r), _native.stream(dev))
+        _native.call("be_ivf_merge", _native.ptr(part_s), _native.ptr(part_r), _native.ptr(sorted_ids.long().contiguous()),
+                     Q, P, kk, _native.ptr(out_s), _native.ptr(out_i), _native.stream(dev))
+    return out_s, out_i
+
+
 class VectorIndex:
     """Tiers (reference FlatIP / IVFFlat / IVFPQ): ``index_type="auto"`` keeps exact bf16 search up
     to ``ivf_threshold`` vectors, IVF-Flat above it and IVF-PQ (``search/ivfpq.py``, m=96 x 8 bit)
@@ -53,7 +115,9 @@ class VectorIndex:
 
     def __init__(self, dim: int = 768, device=None, ivf_threshold: int = 5_000_000, nprobe: int = 64,
                  index_type: str = "auto", ivfpq_threshold: int = 50_000_000, pq_m: int = 96, refine: int = 4,
-                 pq_build: str = "auto", pq_search: str = "auto", pq_coarse: str = "auto"):
+                 pq_build: str = "auto", pq_search: str = "auto", pq_coarse: str = "auto", ivf_search: str = "auto"):
+        if ivf_search not in IVF_SEARCHES:
+            raise ValueError(f"ivf_search must be one of {IVF_SEARCHES}")
         self.lvecs: torch.Tensor | None = None
         self.dim = dim
         self.refine = refine  # IVF-PQ: re-rank refine*k PQ candidates with the stored vectors (0 = off)
@@ -74,6 +138,28 @@ class VectorIndex:
         self.assign: torch.Tensor | None = None
         self.lists: list[torch.Tensor] | None = None
         self.host_refine = False  # compressed tier: self.vecs lives in host memory (refine store only)
+        self.ivf_search = ivf_search  # IVF-Flat: "auto", "scan" or "fused" (csrc/kernels/ivf_scan_topk.hip)
+        self.fused_ivf_search(1, 1)  # "fused" where the kernels cannot run: raise now, not at the first query
+
+    def fused_ivf_search(self, Q: int, k: int) -> bool:
+        """Whether an IVF-Flat search of ``Q`` queries for ``k`` results runs on ``ivf_scan_topk.hip``.  ``"fused"``:
+        always, or it raises; ``"auto"``: where the kernels can run and ``_auto_ivf_fused`` holds."""
+        if self.ivf_search == "scan":
+            return False
+        from ..ops import _native
+
+        ok = self.device.type == "cuda" and _native.hip_available()
+        have = self.lvecs is not None and self.lvecs.shape[0] == self.ntotal
+        if self.ivf_search == "fused":
+            if not ok:
+                raise _native.NativeUnavailable("ivf_search='fused' needs a GPU device and the native kernel library")
+            if self.centroids is not None and not have:
+                raise _native.NativeUnavailable(f"ivf_search='fused' needs the list-sorted bf16 rows: dim / 128 in "
+                                                f"{IVF_SEARCH_CH}")
+            if k > IVF_SEARCH_MAX_K:
+                raise _native.NativeUnavailable(f"ivf_search='fused' keeps at most {IVF_SEARCH_MAX_K} results per query")
+            return True
+        return ok and have and k <= IVF_SEARCH_MAX_K and _auto_ivf_fused(self.dim, self.ntotal, Q, k)
 
     # ------------------------------------------------------------------ build
     @property
@@ -233,13 +319,16 @@ class VectorIndex:
         """Batched IVF-Flat: every query's probed lists become one padded candidate row (list-sorted
         vector ids, located through the list offsets).  GPU: the HIP scan kernel scores every
         candidate exactly from the list-sorted bf16 slabs, then one top-k; CPU: one batched GEMM
-        per query chunk.  No per-query Python loop either way."""
+        per query chunk.  No per-query Python loop either way.  Where :meth:`fused_ivf_search` holds the same
+        probes go to :func:`ivf_scan_topk_fused` instead, which keeps the top-k inside the scan."""
         nl = self.centroids.shape[0]
         npb = min(nprobe or self.nprobe, nl)
         if npb == nl:  # every list: no ranking needed (the candidate order does not matter)
             probes = torch.arange(nl, device=q.device).expand(q.shape[0], nl).contiguous()
         else:
             probes = torch.topk((q @ self.centroids.T).float(), npb, dim=1).indices
+        if self.fused_ivf_search(q.shape[0], k):  # scan, selection and row -> id in HIP, no host read
+            return ivf_scan_topk_fused(q.float(), probes, self.list_off, self.lvecs, self.sorted_ids, k)
         sizes = (self.list_off[1:] - self.list_off[:-1])[probes]  # [Q, nprobe]
         cand_off = torch.cumsum(sizes, 1) - sizes
         stride = int(sizes.sum(1).max())
@@ -305,13 +394,13 @@ class VectorIndex:
         return info
 
     @classmethod
-    def load(cls, out_dir, device=None, pq_search: str = "auto") -> "VectorIndex":
+    def load(cls, out_dir, device=None, pq_search: str = "auto", ivf_search: str = "auto") -> "VectorIndex":
         out = Path(out_dir)
         p = out / "vectors.npy"
         if not p.exists():
             raise FileNotFoundError(f"No index at {p}")
         v = np.load(p)  # allow_pickle=False
-        idx = cls(dim=v.shape[1], device=device, pq_search=pq_search)
+        idx = cls(dim=v.shape[1], device=device, pq_search=pq_search, ivf_search=ivf_search)
         ii = out / "index_info.json"
         info = json.loads(ii.read_text()) if ii.exists() else {}
         host = bool(info.get("host_refine")) and (out / "ivfpq_info.json").exists()

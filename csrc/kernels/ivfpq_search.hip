@@ -38,51 +38,13 @@
 #include <hip/hip_fp16.h>
 
 #include "common.h"
+#include "topk_select.h"
 
 namespace {
 
-typedef unsigned long long key_t;
 constexpr int NT = 512, RPT = 4;
-constexpr key_t KEY_PAD = ~0ull;
 
-#define PQS_NEG_INF (-__builtin_huge_valf())
-
-__device__ __forceinline__ key_t make_key(float s, int row) {
-  const unsigned u = s == 0.f ? 0u : __float_as_uint(s);
-  const unsigned hi = (u & 0x80000000u) ? u : (~u & 0x7fffffffu);
-  return ((key_t)hi << 32) | (unsigned)row;
-}
-__device__ __forceinline__ float key_score(key_t k) {
-  const unsigned hi = (unsigned)(k >> 32);
-  return __uint_as_float((hi & 0x80000000u) ? hi : (~hi & 0x7fffffffu));
-}
-
-// compare-exchange i of a bitonic step of distance j: the pair (lo, lo + j)
-__device__ __forceinline__ int pair_lo(int i, int j) { return ((i & ~(j - 1)) << 1) | (i & (j - 1)); }
-
-// The workgroup sorts the min(*cnt, cap) keys of buf, keeps the first kk and refreshes the threshold.
-// Called by all threads after a barrier; the caller places a barrier after it.
-__device__ __forceinline__ void reselect(key_t* buf, int* cnt, key_t* thr, int cap, int kk, int tid) {
-  int c = *cnt;
-  c = c < cap ? c : cap;
-  int n = 64;
-  while (n < c) n <<= 1;
-  for (int i = c + tid; i < n; i += NT) buf[i] = KEY_PAD;
-  __syncthreads();
-  for (int k = 2; k <= n; k <<= 1)
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int i = tid; i < (n >> 1); i += NT) {
-        const int lo = pair_lo(i, j);
-        const key_t a = buf[lo], b = buf[lo + j];
-        if ((a > b) == ((lo & k) == 0)) { buf[lo] = b; buf[lo + j] = a; }
-      }
-      __syncthreads();
-    }
-  if (tid == 0) {
-    *cnt = c < kk ? c : kk;
-    if (c >= kk) *thr = buf[kk - 1];
-  }
-}
+#define PQS_NEG_INF TOPK_NEG_INF
 
 // WPE: waves per SIMD the register budget must allow (4 = two workgroups on a CU, 2 = one)
 template <int M, int WPE>
@@ -195,12 +157,12 @@ __global__ __launch_bounds__(NT, WPE) void ivfpq_scan_topk_kernel(
       }
       // a bit is left only where the buffer had no slot: it is re-selected to kk <= cap / 2 keys
       if (!__syncthreads_or((int)todo)) break;
-      reselect(buf, s_cnt, s_thr, cap, kk, tid);
+      reselect<NT>(buf, s_cnt, s_thr, cap, kk, tid);
       __syncthreads();
     }
   }
 
-  reselect(buf, s_cnt, s_thr, cap, kk, tid);
+  reselect<NT>(buf, s_cnt, s_thr, cap, kk, tid);
   __syncthreads();
   const int c = *s_cnt;
   for (int i = tid; i < kk; i += NT) {

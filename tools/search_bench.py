@@ -19,6 +19,8 @@ pq96 tier one ``"stage": "pq_build"`` line: ``IVFPQIndex.add`` with ``build="tor
 the coarse quantizer arms ``coarse="torch"`` against ``"fused"`` (``--pq-build-only`` prints this line alone).
 With the pq96 and compressed tiers one ``"stage": "pq_search"`` line per (N, m, Q, k): ``IVFPQIndex.search`` with
 ``search="scan"`` against ``search="fused"`` (``--pq-search-only`` prints these lines alone).
+With the ivf tier one ``"stage": "ivf_search"`` line per (N, Q, k): ``VectorIndex.search`` with ``ivf_search="scan"``
+against ``ivf_search="fused"`` (``--ivf-search-only`` prints these lines alone).
 Usage: ``python tools/search_bench.py --n 10000000,58000000``
 """
 import argparse
@@ -242,6 +244,52 @@ def pq_search_times(pq, q, gt, qs=(1, 64), ks=(20, 80, 1000), reps=20):
     return out
 
 
+def ivf_search_arms(ivf):
+    """``ivf``'s trained IVF-Flat index behind ``ivf_search="scan"`` and ``ivf_search="fused"`` (shared tensors)."""
+    from bioengine_worker_amd.search.index import VectorIndex
+
+    arms = {}
+    for mode in ("scan", "fused"):
+        idx = VectorIndex(dim=ivf.dim, device=ivf.device, index_type="ivf", nprobe=ivf.nprobe, ivf_search=mode)
+        idx.vecs, idx.centroids, idx.assign = ivf.vecs, ivf.centroids, ivf.assign
+        idx.sorted_ids, idx.list_off, idx.lvecs = ivf.sorted_ids, ivf.list_off, ivf.lvecs
+        arms[mode] = idx
+    return arms
+
+
+def ivf_search_times(ivf, q, gt, qs=(1, 64), ks=(20, 80, 1000), reps=20):
+    """``VectorIndex.search`` with ``ivf_search="scan"`` against ``ivf_search="fused"`` on ``ivf``'s index, measured as
+    :func:`pq_search_times` measures: the host clock around the whole call (it ends in the copy of the results, which
+    synchronises), both arms warmed twice on every shape, then alternating; per arm the median and the spread (90th
+    minus 10th percentile) of ``reps`` calls, the share of queries whose score lists are bit-equal, and both arms'
+    recall against ``gt``.  One dict per (Q, k)."""
+    arms = ivf_search_arms(ivf)
+    out = []
+    for Q in qs:
+        for k in ks:
+            qq = q[:Q]
+            ts = {a: [] for a in arms}
+            res = {}
+            for r in range(reps + 2):
+                for a, idx in arms.items():
+                    torch.cuda.synchronize()
+                    t = time.perf_counter()
+                    res[a] = idx.search(qq, k)
+                    if r >= 2:
+                        ts[a].append((time.perf_counter() - t) * 1e3)
+            st = {a: (np.median(v), np.percentile(v, 90) - np.percentile(v, 10)) for a, v in ts.items()}
+            same = (res["scan"][0].view(np.uint32) == res["fused"][0].view(np.uint32)).all(1)
+            rec = {a: recalls(gt[:Q], res[a][1]) for a in arms}
+            out.append({"n": ivf.ntotal, "stage": "ivf_search", "dim": ivf.dim, "nlist": int(ivf.centroids.shape[0]),
+                        "nprobe": ivf.nprobe, "Q": Q, "k": k, "scan_ms": round(st["scan"][0], 3),
+                        "fused_ms": round(st["fused"][0], 3), "scan_spread_ms": round(st["scan"][1], 3),
+                        "fused_spread_ms": round(st["fused"][1], 3),
+                        "scan_over_fused": round(st["scan"][0] / st["fused"][0], 2),
+                        "score_lists_equal": round(float(same.mean()), 4),
+                        "recall@10": {a: rec[a][0] for a in arms}, "R@10": {a: rec[a][1] for a in arms}})
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", default="1000000,10000000")
@@ -258,6 +306,7 @@ def main():
                     "ood: held-out sub-centres of the indexed classes (ood_queries)")
     ap.add_argument("--pq-search-only", action="store_true", help="only the pq_search lines (scan against fused search)")
     ap.add_argument("--pq-ms", default="96,192", help="--pq-search-only: the PQ sizes")
+    ap.add_argument("--ivf-search-only", action="store_true", help="only the ivf_search lines (scan against fused search)")
     ap.add_argument("--pq-build-only", action="store_true", help="only the pq_build line (build and coarse arms)")
     a = ap.parse_args()
     from bioengine_worker_amd.search.index import VectorIndex
@@ -294,6 +343,15 @@ def main():
             ts, j = torch.topk(torch.cat(gs, 1), a.k, dim=1)
             gts[qn] = torch.gather(torch.cat(gi, 1), 1, j).cpu().numpy()
         q = next(iter(qsets.values()))
+        if a.ivf_search_only:  # the ivf_search lines alone
+            ivf = VectorIndex(dim=a.dim, device=dev, index_type="ivf")
+            ivf.vecs = x
+            ivf.train_ivf()
+            for line in ivf_search_times(ivf, q, next(iter(gts.values())), reps=a.reps):
+                print(json.dumps(line), flush=True)
+            del ivf, x, flat
+            torch.cuda.empty_cache()
+            continue
         if a.pq_search_only:  # the pq_search lines alone: the m = 96 index and the compressed tier's m = 192
             for m in [int(v) for v in a.pq_ms.split(",")]:
                 pq = IVFPQIndex(dim=a.dim, nlist=default_nlist(n), m=m, nprobe=64, device=dev)
@@ -332,6 +390,9 @@ def main():
                                   "recall@10_by_queries": {k: v[0] for k, v in rec.items()},
                                   "R@10_by_queries": {k: v[1] for k, v in rec.items()},
                                   "build_s": round(build, 2), "hbm_gb": round(2 * x.numel() * 2 / 1e9, 2)}), flush=True)
+        if "ivf" in tiers:
+            for line in ivf_search_times(ivf, q, next(iter(gts.values())), reps=a.reps):
+                print(json.dumps(line), flush=True)
         del ivf
         torch.cuda.empty_cache()
         if a.no_pq:
