@@ -27,6 +27,8 @@ from pathlib import Path
 import numpy as np
 import torch
 
+from .list_scan import candidate_offsets, scan_topk_merge, slot_rows
+
 CHUNK = 1 << 20  # database rows per GEMM chunk
 
 
@@ -73,7 +75,7 @@ def _auto_ivf_fused(dim: int, n: int, Q: int, k: int) -> bool:
 
 def ivf_scan_topk_fused(q: torch.Tensor, probes: torch.Tensor, list_off: torch.Tensor, lvecs: torch.Tensor,
                         sorted_ids: torch.Tensor, kk: int, splits: int | None = None):
-    """``be_ivf_scan_topk`` + ``be_ivf_merge``: the ``kk`` best exact inner products of ``q [Q, D]`` (fp32) with the
+    """``be_ivf_scan_topk`` + ``be_topk_merge``: the ``kk`` best exact inner products of ``q [Q, D]`` (fp32) with the
     rows of the probed lists in the list-sorted bf16 ``lvecs [N, D]``, ordered by (score descending, list-sorted row
     ascending) -> ``(scores [Q, kk] fp32, ids [Q, kk] int64)`` on the device, rows mapped through ``sorted_ids``,
     ``-inf`` / ``-1`` in empty slots.  A score is bit-equal to the one ``be_ivf_scan_bf16`` writes for that row.
@@ -90,22 +92,15 @@ def ivf_scan_topk_fused(q: torch.Tensor, probes: torch.Tensor, list_off: torch.T
         raise _native.NativeUnavailable(f"be_ivf_scan_topk serves bf16 rows of dim / 128 in {IVF_SEARCH_CH}, "
                                         f"1 <= kk <= {IVF_SEARCH_MAX_K}, fewer than 2^31 rows and nprobe >= 1")
     Q, nprobe = probes.shape
-    dev = lvecs.device
     list_off = list_off.long().contiguous()
-    sizes = (list_off[1:] - list_off[:-1])[probes]  # [Q, nprobe]
-    cand_off = (torch.cumsum(sizes, 1) - sizes).contiguous()
     P = int(splits) if splits else ivf_splits(Q, kk)
-    part_s = torch.empty(Q, P, kk, dtype=torch.float32, device=dev)
-    part_r = torch.empty(Q, P, kk, dtype=torch.int32, device=dev)
-    out_s = torch.empty(Q, kk, dtype=torch.float32, device=dev)
-    out_i = torch.empty(Q, kk, dtype=torch.int64, device=dev)
-    with torch.cuda.device(dev):
+
+    def launch(cand_off, part_s, part_r):
         _native.call("be_ivf_scan_topk", _native.ptr(q.float().contiguous()), _native.ptr(probes.int().contiguous()),
                      _native.ptr(list_off), _native.ptr(cand_off), _native.ptr(lvecs.contiguous()), lvecs.shape[0], Q,
-                     nprobe, q.shape[1], kk, P, _native.ptr(part_s), _native.ptr(part_r), _native.stream(dev))
-        _native.call("be_ivf_merge", _native.ptr(part_s), _native.ptr(part_r), _native.ptr(sorted_ids.long().contiguous()),
-                     Q, P, kk, _native.ptr(out_s), _native.ptr(out_i), _native.stream(dev))
-    return out_s, out_i
+                     nprobe, q.shape[1], kk, P, _native.ptr(part_s), _native.ptr(part_r), _native.stream(lvecs.device))
+
+    return scan_topk_merge(launch, list_off, probes, sorted_ids, kk, P)
 
 
 class VectorIndex:
@@ -329,8 +324,7 @@ class VectorIndex:
             probes = torch.topk((q @ self.centroids.T).float(), npb, dim=1).indices
         if self.fused_ivf_search(q.shape[0], k):  # scan, selection and row -> id in HIP, no host read
             return ivf_scan_topk_fused(q.float(), probes, self.list_off, self.lvecs, self.sorted_ids, k)
-        sizes = (self.list_off[1:] - self.list_off[:-1])[probes]  # [Q, nprobe]
-        cand_off = torch.cumsum(sizes, 1) - sizes
+        sizes, cand_off = candidate_offsets(self.list_off, probes)
         stride = int(sizes.sum(1).max())
         Q = q.shape[0]
         best_s = torch.full((Q, k), -float("inf"), device=self.device)
@@ -342,12 +336,10 @@ class VectorIndex:
 
             out = torch.full((Q, stride), -float("inf"), dtype=torch.float32, device=self.device)
             _native.call("be_ivf_scan_bf16", _native.ptr(q.float().contiguous()), _native.ptr(probes.int().contiguous()),
-                         _native.ptr(self.list_off), _native.ptr(cand_off.contiguous()), _native.ptr(self.lvecs), Q,
+                         _native.ptr(self.list_off), _native.ptr(cand_off), _native.ptr(self.lvecs), Q,
                          probes.shape[1], self.dim, stride, _native.ptr(out), _native.stream(self.device))
             ts, ti = torch.topk(out, min(k, stride), dim=1)
-            p = (torch.searchsorted(cand_off.contiguous(), ti.contiguous(), right=True) - 1).clamp(min=0)
-            rows = self.list_off[torch.gather(probes, 1, p)] + (ti - torch.gather(cand_off, 1, p))
-            ids = self.sorted_ids[rows.clamp(0, self.ntotal - 1)]
+            ids = self.sorted_ids[slot_rows(self.list_off, probes, cand_off, ti).clamp(0, self.ntotal - 1)]
             best_s[:, : ts.shape[1]] = ts
             best_i[:, : ts.shape[1]] = torch.where(torch.isfinite(ts), ids, torch.full_like(ids, -1))
             return best_s, best_i
@@ -355,12 +347,9 @@ class VectorIndex:
         for a in range(0, Q, q_chunk):
             b = min(Q, a + q_chunk)
             sl = slots.expand(b - a, stride).contiguous()
-            p = (torch.searchsorted(cand_off[a:b].contiguous(), sl, right=True) - 1).clamp(min=0)
-            lists = torch.gather(probes[a:b], 1, p)
-            within = sl - torch.gather(cand_off[a:b], 1, p)
-            valid = within < torch.gather(sizes[a:b], 1, p)
-            rows = (self.list_off[lists] + within).clamp(max=self.sorted_ids.numel() - 1)
-            ids = self.sorted_ids[rows]
+            valid = sl < sizes[a:b].sum(1, keepdim=True)  # the row's end: an empty list holds no slot below it
+            rows = slot_rows(self.list_off, probes[a:b], cand_off[a:b], sl)
+            ids = self.sorted_ids[rows.clamp(max=self.sorted_ids.numel() - 1)]
             sc = torch.bmm(self.vecs[ids], q[a:b, :, None]).squeeze(-1).float()
             sc = torch.where(valid, sc, torch.full_like(sc, -float("inf")))
             ts, ti = torch.topk(sc, min(k, stride), dim=1)

@@ -42,6 +42,7 @@ import numpy as np
 import torch
 
 from ..ops import _native
+from .list_scan import candidate_offsets, scan_topk_merge, slot_rows
 
 
 def _kmeans(x: torch.Tensor, k: int, iters: int, g: torch.Generator, spherical: bool, assign=None) -> torch.Tensor:
@@ -264,8 +265,8 @@ _PQ_SEARCH_BLOCKS = 256  # workgroups of a scan: one per CU
 
 def ivfpq_splits(Q: int, nprobe: int, kk: int) -> int:
     """Slot ranges per query of ``be_ivfpq_scan_topk``, from the call's shape alone: about ``_PQ_SEARCH_BLOCKS``
-    workgroups, at most 16 per query (the merge takes the ranges one after the other; measured at 10 M rows, a
-    single query: 16 ranges 71 us, 64 ranges 110 us) and at most ``16384 / kk``."""
+    workgroups, at most 16 per query (``be_ivfpq_merge`` takes the ranges one after the other; measured at 10 M rows,
+    a single query: 16 ranges 71 us, 64 ranges 110 us) and at most ``16384 / kk``."""
     return max(1, min(16, _PQ_SEARCH_BLOCKS // max(Q, 1), 16384 // kk))
 
 
@@ -307,23 +308,16 @@ def ivfpq_scan_topk_fused(lut_half: torch.Tensor, base: torch.Tensor, probes: to
             or lut_half.dtype != torch.float16 or lut_half.shape != (Q, m, 256) or codes.dtype != torch.uint8):
         raise _native.NativeUnavailable(f"be_ivfpq_scan_topk serves m in {PQ_SEARCH_M}, 1 <= kk <= {PQ_SEARCH_MAX_K}, "
                                         "fewer than 2^31 rows and an fp16 table [Q, m, 256]")
-    dev = codes.device
     list_off = list_off.long().contiguous()
-    sizes = (list_off[1:] - list_off[:-1])[probes]  # [Q, nprobe]
-    cand_off = (torch.cumsum(sizes, 1) - sizes).contiguous()
     P = int(splits) if splits else ivfpq_splits(Q, nprobe, kk)
-    part_s = torch.empty(Q, P, kk, dtype=torch.float32, device=dev)
-    part_r = torch.empty(Q, P, kk, dtype=torch.int32, device=dev)
-    out_s = torch.empty(Q, kk, dtype=torch.float32, device=dev)
-    out_i = torch.empty(Q, kk, dtype=torch.int64, device=dev)
-    with torch.cuda.device(dev):
+
+    def launch(cand_off, part_s, part_r):
         _native.call("be_ivfpq_scan_topk", _native.ptr(lut_half.contiguous()), _native.ptr(base.float().contiguous()),
                      _native.ptr(probes.int().contiguous()), _native.ptr(list_off), _native.ptr(cand_off),
                      _native.ptr(codes.contiguous()), codes.shape[0], Q, nprobe, m, kk, P, _native.ptr(part_s),
-                     _native.ptr(part_r), _native.stream(dev))
-        _native.call("be_ivfpq_merge", _native.ptr(part_s), _native.ptr(part_r), _native.ptr(ids.long().contiguous()),
-                     Q, P, kk, _native.ptr(out_s), _native.ptr(out_i), _native.stream(dev))
-    return out_s, out_i
+                     _native.ptr(part_r), _native.stream(codes.device))
+
+    return scan_topk_merge(launch, list_off, probes, ids, kk, P, merge="be_ivfpq_merge")
 
 
 class IVFPQIndex:
@@ -493,8 +487,7 @@ class IVFPQIndex:
         nprobe = min(nprobe or self.nprobe, self.nlist)
         cs = q @ self.centroids.T
         base, probes = torch.topk(cs, nprobe, dim=1)
-        sizes = (self.list_off[1:] - self.list_off[:-1])[probes]  # [Q, nprobe]
-        cand_off = torch.cumsum(sizes, 1) - sizes
+        sizes, cand_off = candidate_offsets(self.list_off, probes)
         tot = sizes.sum(1)
         stride = int(tot.max()) if Q else 0
         S = np.full((Q, k), -np.inf, np.float32)
@@ -505,14 +498,14 @@ class IVFPQIndex:
         out = torch.full((Q, stride), -float("inf"), dtype=torch.float32, device=self.device)
         if self.device.type == "cuda":
             _native.call("be_ivfpq_scan", _native.ptr(lut.half().contiguous()), _native.ptr(base.contiguous()),
-                         _native.ptr(probes.int().contiguous()), _native.ptr(self.list_off), _native.ptr(cand_off.contiguous()),
+                         _native.ptr(probes.int().contiguous()), _native.ptr(self.list_off), _native.ptr(cand_off),
                          _native.ptr(self.codes), Q, nprobe, self.m, stride, _native.ptr(out), _native.stream(self.device))
         else:
             self._scan_reference(lut, base, probes, cand_off, out)
         kk = min(k, stride)
         ts, ti = torch.topk(out, kk, dim=1)
         # candidate slot -> list-sorted row -> original id
-        rows = self._slot_rows(probes, cand_off, sizes, ti)
+        rows = slot_rows(self.list_off, probes, cand_off, ti)
         ids = torch.where(torch.isfinite(ts), self.ids[rows.clamp(min=0)], torch.full_like(rows, -1))
         S[:, :kk] = ts.cpu().numpy()
         I[:, :kk] = ids.cpu().numpy()
@@ -540,15 +533,6 @@ class IVFPQIndex:
             return self._search_fused(q, k, nprobe)
         S, I = self.search(q, k, nprobe)
         return torch.from_numpy(S).to(self.device), torch.from_numpy(I).to(self.device)
-
-    def _slot_rows(self, probes, cand_off, sizes, slots):
-        """Candidate-row slot index -> list-sorted code row."""
-        # which probed list holds the slot: last p with cand_off[p] <= slot
-        p = torch.searchsorted(cand_off.contiguous(), slots.contiguous(), right=True) - 1
-        p = p.clamp(min=0)
-        lists = torch.gather(probes, 1, p)
-        within = slots - torch.gather(cand_off, 1, p)
-        return self.list_off[lists] + within
 
     def _scan_reference(self, lut, base, probes, cand_off, out):
         """torch oracle of be_ivfpq_scan (same fp16 table)."""

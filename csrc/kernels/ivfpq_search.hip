@@ -4,10 +4,7 @@
 //   be_ivfpq_scan_topk  per (query, split) the kk best (score, list-sorted row) pairs of one slot range
 //   be_ivfpq_merge      the splits' partial lists [Q, P, kk] -> [Q, kk], rows mapped to ids (no PQ in it)
 //
-// Order everywhere: (score descending, row ascending).  A pair is packed into one 64-bit key, the high word
-// a bit pattern that falls as the score rises (-0 counts as +0), the low word the row, so "precedes" is one
-// unsigned compare and rows, unique within a query, make every key unique: what is kept never depends on the
-// order in which candidates arrive.
+// Order everywhere: (score descending, list-sorted row ascending), the 64-bit keys of topk_select.h.
 //
 // be_ivfpq_scan_topk, MI355X design:
 //  * A workgroup of 512 threads (8 waves) owns one query and slots [s tot / P, (s + 1) tot / P) of the query's
@@ -15,16 +12,11 @@
 //    workgroup of a query scores the same number of rows whatever the list sizes, and the query's table is
 //    staged into LDS once per workgroup for all of them.
 //  * The range is swept in chunks of 2048 slots, 4 per thread (slot = chunk + 512 r + tid): four independent
-//    chains of LDS lookups per thread hide the lookup latency.  A thread's slots only grow, so it keeps its
-//    current list (first slot, end slot, first row, base score) in registers, finds the first one by a
-//    binary search of the query's cand_off row and steps to the next list when a slot passes the end; empty
-//    lists are stepped over.  Codes are read as 16-byte loads; the score is base + sum_j t[j][code_j] in
-//    fp32, ascending j, starting from base: the order of be_ivfpq_scan, so the scores are bit-equal.
-//  * Selection in LDS: `cap` keys (the power of two >= 2 kk, at least 256), a count and a threshold, the
-//    current kk-th key (all ones while fewer than kk were selected).  A candidate is appended (LDS atomic on
-//    the count) only if its key is below the threshold.  When a thread finds no slot, the workgroup sorts the
-//    buffer (bitonic, ascending keys), keeps the first kk, refreshes the threshold, and the threads that
-//    could not append test their candidates again.  One barrier per chunk.
+//    chains of LDS lookups per thread hide the lookup latency.  Each thread walks the row with a cursor that
+//    carries its list's base score (list_cursor.h).  Codes are read as 16-byte loads; the score is
+//    base + sum_j t[j][code_j] in fp32, ascending j, starting from base: the order of be_ivfpq_scan, so the
+//    scores are bit-equal.
+//  * Selection in LDS behind the table (topk_select.h); one barrier per chunk.
 //  * Output: the sorted first kk keys unpacked to (score, row), padded with (-inf, -1).
 //  * LDS = table m * 512 B + cap * 8 B + 16 B:   m    16   32   48   64   96   128   192
 //                                 kk <= 128 (KiB)     10   18   26   34   50    66    98
@@ -34,17 +26,18 @@
 //
 // be_ivfpq_merge: one workgroup per query.  The running list (KP = power of two >= kk keys, ascending, in
 // LDS) takes one split at a time: element i becomes min(list[i], split[KP - 1 - i]), which leaves the KP
-// smallest keys of both as a bitonic sequence, and log2(KP) compare-exchange steps sort it again.
+// smallest keys of both as a bitonic sequence, and log2(KP) compare-exchange steps sort it again.  It takes the same
+// arguments as be_topk_merge (topk_merge.hip) and returns the same bits; at P <= 16 and kk = 1000 it measured
+// 0.05 ms faster per search than the level sweep, so this path keeps it.
 #include <hip/hip_fp16.h>
 
 #include "common.h"
+#include "list_cursor.h"
 #include "topk_select.h"
 
 namespace {
 
 constexpr int NT = 512, RPT = 4;
-
-#define PQS_NEG_INF TOPK_NEG_INF
 
 // WPE: waves per SIMD the register budget must allow (4 = two workgroups on a CU, 2 = one)
 template <int M, int WPE>
@@ -55,51 +48,24 @@ __global__ __launch_bounds__(NT, WPE) void ivfpq_scan_topk_kernel(
     int* __restrict__ out_r) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   __half* t = reinterpret_cast<__half*>(smem);
-  key_t* buf = reinterpret_cast<key_t*>(smem + M * 512);
-  key_t* s_thr = buf + cap;
-  int* s_cnt = reinterpret_cast<int*>(s_thr + 1);
   const int tid = threadIdx.x;
   const int q = blockIdx.x / P, split = blockIdx.x - q * P;
-  const long long* co = cand_off + (size_t)q * nprobe;
-  const int* pr = probes + (size_t)q * nprobe;
-  const float* bs = base + (size_t)q * nprobe;
   float* os = out_s + (size_t)blockIdx.x * kk;
   int* orow = out_r + (size_t)blockIdx.x * kk;
 
-  const int last = pr[nprobe - 1];
-  const long long tot = co[nprobe - 1] + (list_off[last + 1] - list_off[last]);
-  const long long lo = split * tot / P, hi = (split + 1) * tot / P;
+  ListCursor<true> cur(cand_off, probes, list_off, base, q, nprobe);
+  long long lo, hi;
+  cur.range(split, P, lo, hi);
   if (lo >= hi) {  // the whole workgroup: nothing staged, nothing selected
-    for (int i = tid; i < kk; i += NT) { os[i] = PQS_NEG_INF; orow[i] = -1; }
+    select_nothing<NT>(kk, tid, os, orow);
     return;
   }
   const __half* lq = lut + (size_t)q * M * 256;
   for (int e = tid * 8; e < M * 256; e += NT * 8)
     *reinterpret_cast<uint4*>(t + e) = *reinterpret_cast<const uint4*>(lq + e);
-  if (tid == 0) { *s_cnt = 0; *s_thr = KEY_PAD; }
+  const Selector sel(smem + M * 512, cap, kk, tid);
   __syncthreads();
-
-  // the list that holds this thread's current slot
-  int p = 0;
-  long long seg_start = 0, seg_end = 0, seg_row = 0;
-  float seg_base = 0.f;
-  auto load_seg = [&]() {
-    const int l = pr[p];
-    const long long a = list_off[l];
-    seg_start = co[p];
-    seg_end = seg_start + (list_off[l + 1] - a);
-    seg_row = a;
-    seg_base = bs[p];
-  };
-  if (lo + tid < hi) {  // last p with co[p] <= slot: of lists that start at one slot, the one that is not empty
-    int a = 0, b = nprobe - 1;
-    while (a < b) {
-      const int mid = (a + b + 1) >> 1;
-      if (co[mid] <= lo + tid) a = mid; else b = mid - 1;
-    }
-    p = a;
-    load_seg();
-  }
+  if (lo + tid < hi) cur.seek(lo + tid);
 
   for (long long c0 = lo; c0 < hi; c0 += NT * RPT) {
     float acc[RPT];
@@ -111,9 +77,8 @@ __global__ __launch_bounds__(NT, WPE) void ivfpq_scan_topk_kernel(
       acc[r] = 0.f;
       row[r] = 0;
       if (slot < hi) {
-        while (slot >= seg_end && p + 1 < nprobe) { ++p; load_seg(); }
-        row[r] = (int)(seg_row + (slot - seg_start));
-        acc[r] = seg_base;
+        row[r] = cur.row(slot);
+        acc[r] = cur.base;
         todo |= 1u << r;
       }
     }
@@ -143,33 +108,9 @@ __global__ __launch_bounds__(NT, WPE) void ivfpq_scan_topk_kernel(
     key_t key[RPT];
 #pragma unroll
     for (int r = 0; r < RPT; ++r) key[r] = make_key(acc[r], row[r]);
-    for (;;) {
-      const key_t th = *s_thr;
-#pragma unroll
-      for (int r = 0; r < RPT; ++r) {
-        if (!(todo >> r & 1u)) continue;
-        if (key[r] < th) {
-          const int pos = atomicAdd(s_cnt, 1);
-          if (pos < cap) { buf[pos] = key[r]; todo &= ~(1u << r); }
-        } else {
-          todo &= ~(1u << r);
-        }
-      }
-      // a bit is left only where the buffer had no slot: it is re-selected to kk <= cap / 2 keys
-      if (!__syncthreads_or((int)todo)) break;
-      reselect<NT>(buf, s_cnt, s_thr, cap, kk, tid);
-      __syncthreads();
-    }
+    select_offer<NT, RPT>(sel, todo, [&](int r) { return key[r]; }, tid);
   }
-
-  reselect<NT>(buf, s_cnt, s_thr, cap, kk, tid);
-  __syncthreads();
-  const int c = *s_cnt;
-  for (int i = tid; i < kk; i += NT) {
-    const key_t k = i < c ? buf[i] : KEY_PAD;
-    os[i] = i < c ? key_score(k) : PQS_NEG_INF;
-    orow[i] = i < c ? (int)(unsigned)k : -1;
-  }
+  select_finish<NT>(sel, tid, os, orow, nullptr);
 }
 
 __global__ __launch_bounds__(NT) void topk_merge_kernel(const float* __restrict__ ps, const int* __restrict__ pr,
@@ -205,7 +146,7 @@ __global__ __launch_bounds__(NT) void topk_merge_kernel(const float* __restrict_
     const key_t k = mb[i];
     const bool has = k != KEY_PAD;
     const int r = (int)(unsigned)k;
-    out_s[q * kk + i] = has ? key_score(k) : PQS_NEG_INF;
+    out_s[q * kk + i] = has ? key_score(k) : TOPK_NEG_INF;
     out_i[q * kk + i] = has ? (ids ? ids[r] : (long long)r) : -1;
   }
 }
@@ -226,8 +167,8 @@ template <int M, int WPE>
 int launch_scan_topk(int slot, const __half* lut, const float* base, const int* probes, const long long* list_off,
                      const long long* cand_off, const unsigned char* codes, int Q, int nprobe, int kk, int cap, int P,
                      float* out_s, int* out_r, hipStream_t s) {
-  const int lds = M * 512 + cap * 8 + 16;
-  constexpr int LDS_MAX = M * 512 + 2048 * 8 + 16;
+  const int lds = M * 512 + select_lds_bytes(cap);
+  constexpr int LDS_MAX = M * 512 + select_lds_bytes(select_cap(1024));
   static_assert(LDS_MAX <= 160 * 1024, "LDS of one CU");
   static bool attr[8][BE_MAX_DEV] = {};
   if (!attr[slot][be_cur_dev()]) {
@@ -266,8 +207,7 @@ int be_ivfpq_scan_topk(const void* lut, const float* base, const int* probes, co
   if (Q < 0 || nprobe < 1) return -4;
   if ((long long)Q * P >= (1LL << 31)) return -5;
   if (Q == 0) return 0;
-  int cap = 256;
-  while (cap < 2 * kk) cap <<= 1;
+  const int cap = select_cap(kk);
   const __half* l = reinterpret_cast<const __half*>(lut);
 #define PQS_LAUNCH(slot, M, WPE)                                                                                     \
   case M:                                                                                                            \

@@ -74,6 +74,8 @@ PER_SOURCE_FLAGS = {"clahe": ["-ffp-contract=off"], "attention": ["-mllvm", "-am
                     "ivfpq_search": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
                     # ivf_scan_topk: the same, for the interleaved score chains of the rows in flight
                     "ivf_scan_topk": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+                    # topk_merge: the same, it is built on the scans' selection header
+                    "topk_merge": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
                     # coarse_assign: the same, for the loader's hi / lo split and the selection epilogue
                     "coarse_assign": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 CXX_FLAGS = ["-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-pthread", "-I", str(CSRC / "runtime")]

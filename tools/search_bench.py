@@ -213,12 +213,11 @@ def pq_search_arms(pq):
     return arms
 
 
-def pq_search_times(pq, q, gt, qs=(1, 64), ks=(20, 80, 1000), reps=20):
-    """``IVFPQIndex.search`` with ``search="scan"`` against ``search="fused"`` on ``pq``'s index: the host clock around
-    the whole call (it ends in the copy of the results, which synchronises), both arms warmed twice on every
-    shape, then alternating; per arm the median and the spread (90th minus 10th percentile) of ``reps`` calls,
-    the share of queries whose score lists are bit-equal, and both arms' recall against ``gt``.  One dict per (Q, k)."""
-    arms = pq_search_arms(pq)
+def search_times(arms, stage, fields, q, gt, qs=(1, 64), ks=(20, 80, 1000), reps=20):
+    """``search`` of the ``"scan"`` arm against the ``"fused"`` arm: the host clock around the whole call (it ends in the
+    copy of the results, which synchronises), both arms warmed twice on every shape, then alternating; per arm the
+    median and the spread (90th minus 10th percentile) of ``reps`` calls, the share of queries whose score lists are
+    bit-equal, and both arms' recall against ``gt``.  One dict per (Q, k), opening with the index's ``fields``."""
     out = []
     for Q in qs:
         for k in ks:
@@ -235,13 +234,19 @@ def pq_search_times(pq, q, gt, qs=(1, 64), ks=(20, 80, 1000), reps=20):
             st = {a: (np.median(v), np.percentile(v, 90) - np.percentile(v, 10)) for a, v in ts.items()}
             same = (res["scan"][0].view(np.uint32) == res["fused"][0].view(np.uint32)).all(1)
             rec = {a: recalls(gt[:Q], res[a][1]) for a in arms}
-            out.append({"n": pq.ntotal, "stage": "pq_search", "m": pq.m, "nlist": pq.nlist, "nprobe": pq.nprobe, "Q": Q,
-                        "k": k, "scan_ms": round(st["scan"][0], 3), "fused_ms": round(st["fused"][0], 3),
+            out.append({**fields, "stage": stage, "Q": Q, "k": k,
+                        "scan_ms": round(st["scan"][0], 3), "fused_ms": round(st["fused"][0], 3),
                         "scan_spread_ms": round(st["scan"][1], 3), "fused_spread_ms": round(st["fused"][1], 3),
                         "scan_over_fused": round(st["scan"][0] / st["fused"][0], 2),
                         "score_lists_equal": round(float(same.mean()), 4),
                         "recall@10": {a: rec[a][0] for a in arms}, "R@10": {a: rec[a][1] for a in arms}})
     return out
+
+
+def pq_search_times(pq, q, gt, **kw):
+    """:func:`search_times` of ``IVFPQIndex.search`` with ``search="scan"`` against ``search="fused"`` on ``pq``'s index."""
+    fields = {"n": pq.ntotal, "m": pq.m, "nlist": pq.nlist, "nprobe": pq.nprobe}
+    return search_times(pq_search_arms(pq), "pq_search", fields, q, gt, **kw)
 
 
 def ivf_search_arms(ivf):
@@ -257,37 +262,10 @@ def ivf_search_arms(ivf):
     return arms
 
 
-def ivf_search_times(ivf, q, gt, qs=(1, 64), ks=(20, 80, 1000), reps=20):
-    """``VectorIndex.search`` with ``ivf_search="scan"`` against ``ivf_search="fused"`` on ``ivf``'s index, measured as
-    :func:`pq_search_times` measures: the host clock around the whole call (it ends in the copy of the results, which
-    synchronises), both arms warmed twice on every shape, then alternating; per arm the median and the spread (90th
-    minus 10th percentile) of ``reps`` calls, the share of queries whose score lists are bit-equal, and both arms'
-    recall against ``gt``.  One dict per (Q, k)."""
-    arms = ivf_search_arms(ivf)
-    out = []
-    for Q in qs:
-        for k in ks:
-            qq = q[:Q]
-            ts = {a: [] for a in arms}
-            res = {}
-            for r in range(reps + 2):
-                for a, idx in arms.items():
-                    torch.cuda.synchronize()
-                    t = time.perf_counter()
-                    res[a] = idx.search(qq, k)
-                    if r >= 2:
-                        ts[a].append((time.perf_counter() - t) * 1e3)
-            st = {a: (np.median(v), np.percentile(v, 90) - np.percentile(v, 10)) for a, v in ts.items()}
-            same = (res["scan"][0].view(np.uint32) == res["fused"][0].view(np.uint32)).all(1)
-            rec = {a: recalls(gt[:Q], res[a][1]) for a in arms}
-            out.append({"n": ivf.ntotal, "stage": "ivf_search", "dim": ivf.dim, "nlist": int(ivf.centroids.shape[0]),
-                        "nprobe": ivf.nprobe, "Q": Q, "k": k, "scan_ms": round(st["scan"][0], 3),
-                        "fused_ms": round(st["fused"][0], 3), "scan_spread_ms": round(st["scan"][1], 3),
-                        "fused_spread_ms": round(st["fused"][1], 3),
-                        "scan_over_fused": round(st["scan"][0] / st["fused"][0], 2),
-                        "score_lists_equal": round(float(same.mean()), 4),
-                        "recall@10": {a: rec[a][0] for a in arms}, "R@10": {a: rec[a][1] for a in arms}})
-    return out
+def ivf_search_times(ivf, q, gt, **kw):
+    """:func:`search_times` of ``VectorIndex.search`` with ``ivf_search="scan"`` against ``"fused"`` on ``ivf``'s index."""
+    fields = {"n": ivf.ntotal, "dim": ivf.dim, "nlist": int(ivf.centroids.shape[0]), "nprobe": ivf.nprobe}
+    return search_times(ivf_search_arms(ivf), "ivf_search", fields, q, gt, **kw)
 
 
 def main():
