@@ -106,7 +106,9 @@ def ivf_scan_topk_fused(q: torch.Tensor, probes: torch.Tensor, list_off: torch.T
 class VectorIndex:
     """Tiers (reference FlatIP / IVFFlat / IVFPQ): ``index_type="auto"`` keeps exact bf16 search up
     to ``ivf_threshold`` vectors, IVF-Flat above it and IVF-PQ (``search/ivfpq.py``, m=96 x 8 bit)
-    from ``ivfpq_threshold``; ``"flat"`` / ``"ivf"`` / ``"ivfpq"`` force a tier."""
+    from ``ivfpq_threshold``; ``"flat"`` / ``"ivf"`` / ``"ivfpq"`` force a tier.  ``"ivfsq8"`` (never picked by
+    ``"auto"``) is IVF with a list-sorted int8 copy in place of the list-sorted bf16 one (``search/sq8.py``): 3 D bytes
+    per vector, the ``refine * k`` best int8 scores re-ranked exactly from the stored rows on the device."""
 
     def __init__(self, dim: int = 768, device=None, ivf_threshold: int = 5_000_000, nprobe: int = 64,
                  index_type: str = "auto", ivfpq_threshold: int = 50_000_000, pq_m: int = 96, refine: int = 4,
@@ -114,8 +116,10 @@ class VectorIndex:
         if ivf_search not in IVF_SEARCHES:
             raise ValueError(f"ivf_search must be one of {IVF_SEARCHES}")
         self.lvecs: torch.Tensor | None = None
+        self.sq_codes: torch.Tensor | None = None  # "ivfsq8": list-sorted int8 codes [N, D] and fp32 scales [N]
+        self.sq_scales: torch.Tensor | None = None
         self.dim = dim
-        self.refine = refine  # IVF-PQ: re-rank refine*k PQ candidates with the stored vectors (0 = off)
+        self.refine = refine  # IVF-PQ, IVF-SQ8: re-rank refine*k candidates with the stored vectors (0 = off)
         self.kind = index_type
         self.ivfpq_threshold = ivfpq_threshold
         self.pq_m = pq_m
@@ -135,6 +139,13 @@ class VectorIndex:
         self.host_refine = False  # compressed tier: self.vecs lives in host memory (refine store only)
         self.ivf_search = ivf_search  # IVF-Flat: "auto", "scan" or "fused" (csrc/kernels/ivf_scan_topk.hip)
         self.fused_ivf_search(1, 1)  # "fused" where the kernels cannot run: raise now, not at the first query
+        if index_type == "ivfsq8":  # the tier has no other path: the same rule
+            from ..ops import _native
+            from .sq8 import SQ8_CH, sq8_dim_ok
+
+            if not (self.device.type == "cuda" and _native.hip_available() and sq8_dim_ok(dim)):
+                raise _native.NativeUnavailable(f"index_type='ivfsq8' needs a GPU device, the native kernel library and "
+                                                f"dim / 256 in {SQ8_CH}")
 
     def fused_ivf_search(self, Q: int, k: int) -> bool:
         """Whether an IVF-Flat search of ``Q`` queries for ``k`` results runs on ``ivf_scan_topk.hip``.  ``"fused"``:
@@ -165,6 +176,8 @@ class VectorIndex:
     def index_type(self) -> str:
         if self.pq is not None:
             return self.pq.index_type
+        if self.centroids is not None and self.kind == "ivfsq8":
+            return f"IVFSQ8-GPU(nlist={self.centroids.shape[0]})"
         return f"IVFFlat-GPU(nlist={self.centroids.shape[0]})" if self.centroids is not None else "FlatIP-GPU"
 
     def add(self, x) -> None:
@@ -178,7 +191,7 @@ class VectorIndex:
             self.train_ivfpq()
         elif self.centroids is not None:
             self._assign_new(x, self.ntotal - x.shape[0])
-        elif self.kind == "ivf" or (self.kind == "auto" and self.ntotal >= self.ivf_threshold):
+        elif self.kind in ("ivf", "ivfsq8") or (self.kind == "auto" and self.ntotal >= self.ivf_threshold):
             self.train_ivf()
 
     def _fits_hbm(self, n: int) -> bool:
@@ -210,7 +223,7 @@ class VectorIndex:
         vectors in host memory as the exact re-rank store.  Search returns the top-k of the
         ``refine * k`` PQ candidates re-scored exactly.  Returns the GPU / host footprint (bytes)."""
         self.pq_m, self.refine = pq_m, refine
-        self.lvecs = None
+        self.lvecs = self.sq_codes = self.sq_scales = None
         self.train_ivfpq(nlist)
         self.vecs = self.vecs.cpu()  # bf16 on the host: ~1.5 KB per vector, gathered per query
         self.host_refine = True
@@ -224,6 +237,15 @@ class VectorIndex:
             return self.vecs[c]
         rows = self.vecs.index_select(0, c.reshape(-1).cpu())  # host gather (multi-threaded)
         return rows.to(self.device, non_blocking=False).view(*c.shape, self.dim)
+
+    def _rerank(self, q: torch.Tensor, c: torch.Tensor, k: int):
+        """Shortlist ids ``c [Q, R]`` (-1 = empty) re-scored exactly with the stored vectors and cut to the best
+        ``min(k, R)`` -> ``(scores, ids)`` on the device, ``-inf`` / ``-1`` in empty slots."""
+        ok = c >= 0
+        s = torch.einsum("qd,qkd->qk", q.float(), self._refine_rows(c.clamp(min=0)).float())
+        s = torch.where(ok, s, torch.full_like(s, -float("inf")))
+        ts, ti = torch.topk(s, min(k, s.shape[1]), dim=1)
+        return ts, torch.where(torch.isfinite(ts), torch.gather(c, 1, ti), torch.full_like(ti, -1))
 
     def train_ivf(self, nlist: int | None = None, iters: int = 10, seed: int = 0) -> None:
         n = self.ntotal
@@ -254,6 +276,12 @@ class VectorIndex:
         self.sorted_ids = order  # vector ids grouped by list
         self.list_off = torch.cat([counts.new_zeros(1), torch.cumsum(counts, 0)])
         self.lists = None
+        if self.kind == "ivfsq8":  # the list-sorted int8 copy instead, gathered inside the encoder
+            from .sq8 import sq8_encode
+
+            self.lvecs = None
+            self.sq_codes, self.sq_scales = sq8_encode(self.vecs, order)
+            return
         # list-sorted copy of the vectors: every IVF list is one contiguous HBM slab that the exact
         # scan kernel streams (be_ivf_scan_bf16); built chunk by chunk to bound the temporary
         # (be_ivf_scan_bf16 is instantiated for dim/128 in {1,2,3,4,6,8}; other dims use the bmm path)
@@ -282,11 +310,7 @@ class VectorIndex:
                 return self.pq.search(q.float(), k)
             # IVF-PQ shortlist of refine*k, re-scored exactly with the stored vectors (IVFPQ+R)
             _, c = self.pq.search_device(q.float(), self.refine * k)  # stays on the device
-            ok = c >= 0
-            s = torch.einsum("qd,qkd->qk", q.float(), self._refine_rows(c.clamp(min=0)).float())
-            s = torch.where(ok, s, torch.full_like(s, -float("inf")))
-            ts, ti = torch.topk(s, min(k, s.shape[1]), dim=1)
-            ids = torch.where(torch.isfinite(ts), torch.gather(c, 1, ti), torch.full_like(ti, -1))
+            ts, ids = self._rerank(q, c, k)
             S = np.full((Q, k), -np.inf, np.float32)
             I = np.full((Q, k), -1, np.int64)
             S[:, : ts.shape[1]] = ts.cpu().numpy()
@@ -322,6 +346,8 @@ class VectorIndex:
             probes = torch.arange(nl, device=q.device).expand(q.shape[0], nl).contiguous()
         else:
             probes = torch.topk((q @ self.centroids.T).float(), npb, dim=1).indices
+        if self.kind == "ivfsq8":
+            return self._search_sq8(q, probes, k)
         if self.fused_ivf_search(q.shape[0], k):  # scan, selection and row -> id in HIP, no host read
             return ivf_scan_topk_fused(q.float(), probes, self.list_off, self.lvecs, self.sorted_ids, k)
         sizes, cand_off = candidate_offsets(self.list_off, probes)
@@ -357,6 +383,20 @@ class VectorIndex:
             best_i[a:b, : ts.shape[1]] = torch.where(torch.isfinite(ts), torch.gather(ids, 1, ti), torch.full_like(ti, -1))
         return best_s, best_i
 
+    def _search_sq8(self, q: torch.Tensor, probes: torch.Tensor, k: int):
+        """The IVF-SQ8 tier: the best ``min(refine * k, 1024)`` int8 scores of the probed lists
+        (``csrc/kernels/ivf_sq8.hip``), re-scored exactly from ``self.vecs`` and cut to ``k``; ``refine == 0``: the
+        ``k`` best int8 scores as they are."""
+        from ..ops import _native
+        from .sq8 import SQ8_MAX_K, ivf_sq8_scan_topk_fused
+
+        if k > SQ8_MAX_K:
+            raise _native.NativeUnavailable(f"index_type='ivfsq8' keeps at most {SQ8_MAX_K} results per query")
+        kk = min(self.refine * k, SQ8_MAX_K) if self.refine else k
+        s, c = ivf_sq8_scan_topk_fused(q.float(), probes, self.list_off, self.sq_codes, self.sq_scales, self.sorted_ids,
+                                       kk)
+        return self._rerank(q, c, k) if self.refine else (s, c)
+
     def reconstruct_batch(self, ids) -> np.ndarray:
         return self.vecs[torch.as_tensor(np.asarray(ids), device=self.vecs.device)].float().cpu().numpy()
 
@@ -376,6 +416,7 @@ class VectorIndex:
             (out / "ivf_centroids.npy").unlink(missing_ok=True)
         info = {"n_cells": self.ntotal, "embed_dim": self.dim, "index_type": self.index_type,
                 "host_refine": self.host_refine, "refine": self.refine,
+                **({"sq8": True} if self.kind == "ivfsq8" and self.pq is None else {}),
                 "index_size_mb": round((out / "vectors.npy").stat().st_size / 2 ** 20, 3),
                 "build_seconds": round(time.time() - t0, 3),
                 "build_time_iso": time.strftime("%Y-%m-%dT%H:%M:%SZ", time.gmtime())}
@@ -389,9 +430,11 @@ class VectorIndex:
         if not p.exists():
             raise FileNotFoundError(f"No index at {p}")
         v = np.load(p)  # allow_pickle=False
-        idx = cls(dim=v.shape[1], device=device, pq_search=pq_search, ivf_search=ivf_search)
         ii = out / "index_info.json"
         info = json.loads(ii.read_text()) if ii.exists() else {}
+        # "sq8": the int8 codes are a function of vectors.npy and are rebuilt by _assign_new below
+        idx = cls(dim=v.shape[1], device=device, pq_search=pq_search, ivf_search=ivf_search,
+                  index_type="ivfsq8" if info.get("sq8") else "auto")
         host = bool(info.get("host_refine")) and (out / "ivfpq_info.json").exists()
         idx.vecs = torch.from_numpy(v.astype(np.float32)).to("cpu" if host else idx.device, idx.dtype)
         if (out / "ivfpq_info.json").exists():
@@ -403,6 +446,8 @@ class VectorIndex:
             idx.pq_m = idx.pq.m
             return idx
         c = out / "ivf_centroids.npy"
+        if info.get("sq8"):
+            idx.refine = int(info.get("refine", idx.refine))
         if c.exists():
             idx.centroids = torch.from_numpy(np.load(c)).to(idx.device, idx.dtype)
             idx.assign = torch.empty(0, dtype=torch.int32, device=idx.device)

@@ -21,6 +21,8 @@ With the pq96 and compressed tiers one ``"stage": "pq_search"`` line per (N, m, 
 ``search="scan"`` against ``search="fused"`` (``--pq-search-only`` prints these lines alone).
 With the ivf tier one ``"stage": "ivf_search"`` line per (N, Q, k): ``VectorIndex.search`` with ``ivf_search="scan"``
 against ``ivf_search="fused"`` (``--ivf-search-only`` prints these lines alone).
+``--sq8-only`` prints one ``"stage": "sq8"`` line per (N, Q, k): the IVF-Flat tier with ``ivf_search="fused"`` against
+``index_type="ivfsq8"`` on the same centroids (:func:`sq8_times`).
 Usage: ``python tools/search_bench.py --n 10000000,58000000``
 """
 import argparse
@@ -268,6 +270,56 @@ def ivf_search_times(ivf, q, gt, **kw):
     return search_times(ivf_search_arms(ivf), "ivf_search", fields, q, gt, **kw)
 
 
+def sq8_times(ivf, q, qs=(1, 64), ks=(20, 80), reps=20):
+    """``ivf``'s trained IVF-Flat index behind ``ivf_search="fused"`` against the same centroids and lists behind
+    ``index_type="ivfsq8"`` (``csrc/kernels/ivf_sq8.hip``), all through :func:`_alternate`: the encode, then per (Q, k)
+    the whole ``search`` call of the bf16 arm and of the SQ8 arm with ``refine`` 0 and 4, the fused scan + merge alone
+    on the same probes (``kk = k``), the candidate rows and the bytes they stream, and the SQ8 arms' recall@k against
+    the bf16 arm's ids.  One ``"stage": "sq8"`` dict per (Q, k), opening with the tiers' device bytes."""
+    from bioengine_worker_amd.search.index import VectorIndex, ivf_scan_topk_fused
+    from bioengine_worker_amd.search.list_scan import candidate_offsets
+    from bioengine_worker_amd.search.sq8 import ivf_sq8_scan_topk_fused, sq8_encode
+
+    arms = {"ivf": VectorIndex(dim=ivf.dim, device=ivf.device, index_type="ivf", nprobe=ivf.nprobe, ivf_search="fused"),
+            "sq8_r0": VectorIndex(dim=ivf.dim, device=ivf.device, index_type="ivfsq8", nprobe=ivf.nprobe, refine=0),
+            "sq8_r4": VectorIndex(dim=ivf.dim, device=ivf.device, index_type="ivfsq8", nprobe=ivf.nprobe, refine=4)}
+    enc = _alternate({"encode": lambda: sq8_encode(ivf.vecs, ivf.sorted_ids)}, 3)["encode"]
+    for name, idx in arms.items():
+        idx.vecs, idx.centroids, idx.assign = ivf.vecs, ivf.centroids, ivf.assign
+        idx.sorted_ids, idx.list_off = ivf.sorted_ids, ivf.list_off
+        if name == "ivf":
+            idx.lvecs = ivf.lvecs
+        else:
+            idx.sq_codes, idx.sq_scales = enc[2]
+    nbytes = lambda *ts: int(sum(t.numel() * t.element_size() for t in ts))  # noqa: E731
+    fields = {"n": ivf.ntotal, "dim": ivf.dim, "nlist": int(ivf.centroids.shape[0]), "nprobe": ivf.nprobe, "stage": "sq8",
+              "ivf_bytes": nbytes(ivf.vecs, ivf.lvecs), "sq8_bytes": nbytes(ivf.vecs, *enc[2]),
+              "encode_ms": round(enc[0], 2), "encode_spread_ms": round(enc[1], 2)}
+    out = []
+    for Q in qs:
+        qq = q[:Q].to(ivf.dtype)
+        probes = torch.topk((qq @ ivf.centroids.T).float(), ivf.nprobe, dim=1).indices
+        rows = int(candidate_offsets(ivf.list_off, probes)[0].sum())
+        for k in ks:
+            ts = _alternate({a: (lambda idx=idx: idx.search(qq, k)) for a, idx in arms.items()}, reps)
+            sc = _alternate({"ivf": lambda: ivf_scan_topk_fused(qq.float(), probes, ivf.list_off, ivf.lvecs,
+                                                                 ivf.sorted_ids, k),
+                             "sq8": lambda: ivf_sq8_scan_topk_fused(qq.float(), probes, ivf.list_off, *enc[2],
+                                                                     ivf.sorted_ids, k)}, reps)
+            line = {**fields, "Q": Q, "k": k, "candidate_rows": rows, "ivf_scan_bytes": rows * ivf.dim * 2,
+                    "sq8_scan_bytes": rows * (ivf.dim + 4)}
+            for a in arms:
+                line.update({f"{a}_ms": round(ts[a][0], 3), f"{a}_spread_ms": round(ts[a][1], 3)})
+            for a in sc:
+                line.update({f"scan_{a}_ms": round(sc[a][0], 4), f"scan_{a}_spread_ms": round(sc[a][1], 4)})
+            line["scan_ivf_over_sq8"] = round(sc["ivf"][0] / sc["sq8"][0], 2)
+            gt = ts["ivf"][2][1]
+            for a in ("sq8_r0", "sq8_r4"):
+                line[f"recall@{k}_{a}"] = round(float(np.mean([len(set(g) & set(r)) / k for g, r in zip(gt, ts[a][2][1])])), 4)
+            out.append(line)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", default="1000000,10000000")
@@ -285,6 +337,7 @@ def main():
     ap.add_argument("--pq-search-only", action="store_true", help="only the pq_search lines (scan against fused search)")
     ap.add_argument("--pq-ms", default="96,192", help="--pq-search-only: the PQ sizes")
     ap.add_argument("--ivf-search-only", action="store_true", help="only the ivf_search lines (scan against fused search)")
+    ap.add_argument("--sq8-only", action="store_true", help="only the sq8 lines (fused IVF-Flat against IVF-SQ8)")
     ap.add_argument("--pq-build-only", action="store_true", help="only the pq_build line (build and coarse arms)")
     a = ap.parse_args()
     from bioengine_worker_amd.search.index import VectorIndex
@@ -307,6 +360,15 @@ def main():
             x[qidx].float() + 0.02 * torch.randn(64, a.dim, device=dev, generator=gq), dim=1),
             "ood": ood_queries(64, a.dim, dev)}
         qsets = {k: v for k, v in qsets.items() if k in a.queries.split(",")}
+        if a.sq8_only:  # the sq8 lines alone; the reference is the IVF-Flat arm, no exact ground truth is needed
+            ivf = VectorIndex(dim=a.dim, device=dev, index_type="ivf", ivf_search="fused")
+            ivf.vecs = x
+            ivf.train_ivf()
+            for line in sq8_times(ivf, next(iter(qsets.values())), reps=a.reps):
+                print(json.dumps(line), flush=True)
+            del ivf, x
+            torch.cuda.empty_cache()
+            continue
         flat = VectorIndex(dim=a.dim, device=dev, index_type="flat")
         flat.vecs = x
         # ground truth in fp32 (fp32 query x bf16 vectors upcast per chunk): exact up to fp32 rounding
