@@ -27,6 +27,7 @@ from pathlib import Path
 import numpy as np
 import torch
 
+from .flat import FLAT_MAX_K, flat_scan_topk_fused
 from .list_scan import candidate_offsets, scan_topk_merge, slot_rows
 
 CHUNK = 1 << 20  # database rows per GEMM chunk
@@ -103,6 +104,20 @@ def ivf_scan_topk_fused(q: torch.Tensor, probes: torch.Tensor, list_off: torch.T
     return scan_topk_merge(launch, list_off, probes, sorted_ids, kk, P)
 
 
+# ------------------------------------------------------------------------------- fused flat search (flat_scan_topk.hip)
+FLAT_SEARCHES = ("auto", "gemm", "fused")
+
+
+def _auto_flat_fused(dim: int, n: int, Q: int, k: int) -> bool:
+    """The shapes at which ``flat_search="auto"`` takes the fused path: those between the measured ones at which it
+    was faster than ``"gemm"`` by more than both arms' spread (README, "Flat search": D = 768, 100 k / 1 M / 5 M rows,
+    1 and 64 queries, k = 20 and 100).  One query won at all six shapes; 64 queries won at k = 20 from 1 M rows on, tied
+    at 100 k rows and lost or tied at k = 100."""
+    if dim != 768 or not 100_000 <= n <= 5_000_000:
+        return False
+    return k <= 100 if Q == 1 else Q <= 64 and k <= 20 and n >= 1_000_000
+
+
 class VectorIndex:
     """Tiers (reference FlatIP / IVFFlat / IVFPQ): ``index_type="auto"`` keeps exact bf16 search up
     to ``ivf_threshold`` vectors, IVF-Flat above it and IVF-PQ (``search/ivfpq.py``, m=96 x 8 bit)
@@ -112,9 +127,12 @@ class VectorIndex:
 
     def __init__(self, dim: int = 768, device=None, ivf_threshold: int = 5_000_000, nprobe: int = 64,
                  index_type: str = "auto", ivfpq_threshold: int = 50_000_000, pq_m: int = 96, refine: int = 4,
-                 pq_build: str = "auto", pq_search: str = "auto", pq_coarse: str = "auto", ivf_search: str = "auto"):
+                 pq_build: str = "auto", pq_search: str = "auto", pq_coarse: str = "auto", ivf_search: str = "auto",
+                 flat_search: str = "auto"):
         if ivf_search not in IVF_SEARCHES:
             raise ValueError(f"ivf_search must be one of {IVF_SEARCHES}")
+        if flat_search not in FLAT_SEARCHES:
+            raise ValueError(f"flat_search must be one of {FLAT_SEARCHES}")
         self.lvecs: torch.Tensor | None = None
         self.sq_codes: torch.Tensor | None = None  # "ivfsq8": list-sorted int8 codes [N, D] and fp32 scales [N]
         self.sq_scales: torch.Tensor | None = None
@@ -139,6 +157,8 @@ class VectorIndex:
         self.host_refine = False  # compressed tier: self.vecs lives in host memory (refine store only)
         self.ivf_search = ivf_search  # IVF-Flat: "auto", "scan" or "fused" (csrc/kernels/ivf_scan_topk.hip)
         self.fused_ivf_search(1, 1)  # "fused" where the kernels cannot run: raise now, not at the first query
+        self.flat_search = flat_search  # flat tier: "auto", "gemm" or "fused" (csrc/kernels/flat_scan_topk.hip)
+        self.fused_flat_search(1, 1)  # the same rule
         if index_type == "ivfsq8":  # the tier has no other path: the same rule
             from ..ops import _native
             from .sq8 import SQ8_CH, sq8_dim_ok
@@ -166,6 +186,23 @@ class VectorIndex:
                 raise _native.NativeUnavailable(f"ivf_search='fused' keeps at most {IVF_SEARCH_MAX_K} results per query")
             return True
         return ok and have and k <= IVF_SEARCH_MAX_K and _auto_ivf_fused(self.dim, self.ntotal, Q, k)
+
+    def fused_flat_search(self, Q: int, k: int) -> bool:
+        """Whether a flat search of ``Q`` queries for ``k`` results runs on ``flat_scan_topk.hip``.  ``"fused"``:
+        always, or it raises; ``"auto"``: where the kernel can run and ``_auto_flat_fused`` holds."""
+        if self.flat_search == "gemm":
+            return False
+        from ..ops import _native
+
+        ok = self.device.type == "cuda" and _native.hip_available() and self.dim >= 32 and self.dim % 32 == 0
+        if self.flat_search == "fused":
+            if not ok:
+                raise _native.NativeUnavailable("flat_search='fused' needs a GPU device, the native kernel library and "
+                                                "dim % 32 == 0")
+            if k > FLAT_MAX_K:
+                raise _native.NativeUnavailable(f"flat_search='fused' keeps at most {FLAT_MAX_K} results per query")
+            return True
+        return ok and k <= FLAT_MAX_K and _auto_flat_fused(self.dim, self.ntotal, Q, k)
 
     # ------------------------------------------------------------------ build
     @property
@@ -316,7 +353,9 @@ class VectorIndex:
             S[:, : ts.shape[1]] = ts.cpu().numpy()
             I[:, : ids.shape[1]] = ids.cpu().numpy()
             return S, I
-        if self.centroids is None:
+        if self.centroids is None and self.fused_flat_search(Q, k_eff):  # scan and selection in HIP
+            best_s, best_i = flat_scan_topk_fused(q, self.vecs, k_eff)
+        elif self.centroids is None:
             best_s = torch.full((Q, 0), -float("inf"), device=self.device)
             best_i = torch.empty(Q, 0, dtype=torch.long, device=self.device)
             for i in range(0, self.ntotal, CHUNK):
@@ -424,7 +463,8 @@ class VectorIndex:
         return info
 
     @classmethod
-    def load(cls, out_dir, device=None, pq_search: str = "auto", ivf_search: str = "auto") -> "VectorIndex":
+    def load(cls, out_dir, device=None, pq_search: str = "auto", ivf_search: str = "auto",
+             flat_search: str = "auto") -> "VectorIndex":
         out = Path(out_dir)
         p = out / "vectors.npy"
         if not p.exists():
@@ -433,7 +473,7 @@ class VectorIndex:
         ii = out / "index_info.json"
         info = json.loads(ii.read_text()) if ii.exists() else {}
         # "sq8": the int8 codes are a function of vectors.npy and are rebuilt by _assign_new below
-        idx = cls(dim=v.shape[1], device=device, pq_search=pq_search, ivf_search=ivf_search,
+        idx = cls(dim=v.shape[1], device=device, pq_search=pq_search, ivf_search=ivf_search, flat_search=flat_search,
                   index_type="ivfsq8" if info.get("sq8") else "auto")
         host = bool(info.get("host_refine")) and (out / "ivfpq_info.json").exists()
         idx.vecs = torch.from_numpy(v.astype(np.float32)).to("cpu" if host else idx.device, idx.dtype)

@@ -76,6 +76,8 @@ PER_SOURCE_FLAGS = {"clahe": ["-ffp-contract=off"], "attention": ["-mllvm", "-am
                     "ivf_scan_topk": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
                     # ivf_sq8: the same, for the int8 scan's score chains and the encoder's products
                     "ivf_sq8": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+                    # flat_scan_topk: the same, for the key packing and the rank counting of the selection
+                    "flat_scan_topk": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
                     # topk_merge: the same, it is built on the scans' selection header
                     "topk_merge": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
                     # coarse_assign: the same, for the loader's hi / lo split and the selection epilogue

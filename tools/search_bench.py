@@ -23,6 +23,8 @@ With the ivf tier one ``"stage": "ivf_search"`` line per (N, Q, k): ``VectorInde
 against ``ivf_search="fused"`` (``--ivf-search-only`` prints these lines alone).
 ``--sq8-only`` prints one ``"stage": "sq8"`` line per (N, Q, k): the IVF-Flat tier with ``ivf_search="fused"`` against
 ``index_type="ivfsq8"`` on the same centroids (:func:`sq8_times`).
+``--flat-search-only`` prints one ``"stage": "flat_search"`` line per (N, Q, k): the flat tier's ``VectorIndex.search``
+with ``flat_search="gemm"`` against ``flat_search="fused"`` (:func:`flat_search_times`); the full run prints them too.
 Usage: ``python tools/search_bench.py --n 10000000,58000000``
 """
 import argparse
@@ -138,9 +140,10 @@ def pq_build_times(pq, x, reps=3):
             "codes_equal": round(int((raws["torch"] == raws["fused"]).sum()) / raws["torch"].numel(), 6)}
 
 
-def _alternate(fns, reps):
+def _alternate(fns, reps, pct=False):
     """Device-event times (ms) of the calls ``fns[name]()``: every arm once as a warm-up, then alternating ``reps``
-    times -> per arm (median, max - min, the last call's result)."""
+    times -> per arm (median, max - min, the last call's result); ``pct``: the spread is the 90th minus the 10th
+    percentile instead."""
     ts, res = {b: [] for b in fns}, {}
     for r in range(reps + 1):
         for b, fn in fns.items():
@@ -153,7 +156,8 @@ def _alternate(fns, reps):
             e1.synchronize()
             if r:
                 ts[b].append(e0.elapsed_time(e1))
-    return {b: (sorted(v)[len(v) // 2], max(v) - min(v), res[b]) for b, v in ts.items()}
+    spread = (lambda v: np.percentile(v, 90) - np.percentile(v, 10)) if pct else (lambda v: max(v) - min(v))
+    return {b: (sorted(v)[len(v) // 2], spread(v), res[b]) for b, v in ts.items()}
 
 
 def pq_coarse_times(pq, x, train_rows, reps=3):
@@ -320,6 +324,39 @@ def sq8_times(ivf, q, qs=(1, 64), ks=(20, 80), reps=20):
     return out
 
 
+def flat_search_times(x, q, qs=(1, 64), ks=(20, 100), reps=20, hbm_tbps=8.0):
+    """The flat tier over the bf16 rows ``x`` behind ``flat_search="gemm"`` (the chunked GEMM + ``topk`` loop) and
+    ``flat_search="fused"`` (``csrc/kernels/flat_scan_topk.hip``), shared tensors, all through :func:`_alternate`: per
+    (Q, k) the whole ``search`` call of both arms (median, spread = 90th - 10th percentile), their ratio, the fused scan
+    + merge alone, the bytes of rows it streams (once per query group) over that time as a share of ``hbm_tbps``, and
+    the share of queries whose id sets agree.  One ``"stage": "flat_search"`` dict per (Q, k)."""
+    from bioengine_worker_amd.search.flat import flat_group, flat_scan_topk_fused
+    from bioengine_worker_amd.search.index import VectorIndex
+
+    arms = {}
+    for mode in ("gemm", "fused"):
+        arms[mode] = VectorIndex(dim=x.shape[1], device=x.device, index_type="flat", flat_search=mode)
+        arms[mode].vecs = x
+    out = []
+    for Q in qs:
+        qq = q[:Q].to(x.dtype)
+        for k in ks:
+            ts = _alternate({a: (lambda idx=idx: idx.search(qq, k)) for a, idx in arms.items()}, reps, pct=True)
+            sc = _alternate({"scan": lambda: flat_scan_topk_fused(qq, x, k)}, reps, pct=True)["scan"]
+            group = flat_group(Q, x.shape[1], k)
+            nbytes = -(-Q // group) * x.numel() * 2
+            same = [set(a) == set(b) for a, b in zip(ts["gemm"][2][1], ts["fused"][2][1])]
+            out.append({"n": int(x.shape[0]), "dim": int(x.shape[1]), "stage": "flat_search", "Q": Q, "k": k,
+                        "gemm_ms": round(ts["gemm"][0], 3), "fused_ms": round(ts["fused"][0], 3),
+                        "gemm_spread_ms": round(ts["gemm"][1], 3), "fused_spread_ms": round(ts["fused"][1], 3),
+                        "gemm_over_fused": round(ts["gemm"][0] / ts["fused"][0], 2), "query_group": group,
+                        "fused_scan_ms": round(sc[0], 3), "fused_scan_spread_ms": round(sc[1], 3),
+                        "rows_bytes": nbytes, "scan_tbps": round(nbytes / sc[0] * 1e-9, 2),
+                        "share_of_hbm_peak": round(nbytes / sc[0] * 1e-9 / hbm_tbps, 3),
+                        "id_sets_equal": round(float(np.mean(same)), 4)})
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", default="1000000,10000000")
@@ -339,6 +376,8 @@ def main():
     ap.add_argument("--ivf-search-only", action="store_true", help="only the ivf_search lines (scan against fused search)")
     ap.add_argument("--sq8-only", action="store_true", help="only the sq8 lines (fused IVF-Flat against IVF-SQ8)")
     ap.add_argument("--pq-build-only", action="store_true", help="only the pq_build line (build and coarse arms)")
+    ap.add_argument("--flat-search-only", action="store_true", help="only the flat_search lines (gemm against fused)")
+    ap.add_argument("--flat-ks", default="20,100", help="the flat_search lines' k values")
     a = ap.parse_args()
     from bioengine_worker_amd.search.index import VectorIndex
     from bioengine_worker_amd.search.ivfpq import IVFPQIndex, default_nlist
@@ -360,6 +399,13 @@ def main():
             x[qidx].float() + 0.02 * torch.randn(64, a.dim, device=dev, generator=gq), dim=1),
             "ood": ood_queries(64, a.dim, dev)}
         qsets = {k: v for k, v in qsets.items() if k in a.queries.split(",")}
+        if a.flat_search_only:  # the flat_search lines alone; the two arms are compared with each other
+            for line in flat_search_times(x, next(iter(qsets.values())), ks=[int(v) for v in a.flat_ks.split(",")],
+                                          reps=a.reps):
+                print(json.dumps(line), flush=True)
+            del x
+            torch.cuda.empty_cache()
+            continue
         if a.sq8_only:  # the sq8 lines alone; the reference is the IVF-Flat arm, no exact ground truth is needed
             ivf = VectorIndex(dim=a.dim, device=dev, index_type="ivf", ivf_search="fused")
             ivf.vecs = x
@@ -408,6 +454,8 @@ def main():
             p50, p95 = timeit(fn, a.reps)
             print(json.dumps({"n": n, "tier": "FlatIP-GPU bf16", "query": name, "p50_ms": round(p50, 3),
                               "p95_ms": round(p95, 3), "recall@10": 1.0, "R@10": 1.0}), flush=True)
+        for line in flat_search_times(x, q, ks=[int(v) for v in a.flat_ks.split(",")], reps=a.reps):
+            print(json.dumps(line), flush=True)
         tiers = a.tiers.split(",")
         # ---- IVF exact scan over list-sorted HBM slabs
         t0 = time.perf_counter()
