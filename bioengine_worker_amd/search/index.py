@@ -27,7 +27,7 @@ from pathlib import Path
 import numpy as np
 import torch
 
-from .flat import FLAT_MAX_K, flat_scan_topk_fused
+from .flat import FLAT_MAX_K, FLAT_SQ8_MAX_K, flat_scan_topk_fused, flat_sq8_scan_topk_fused
 from .list_scan import candidate_offsets, scan_topk_merge, slot_rows
 
 CHUNK = 1 << 20  # database rows per GEMM chunk
@@ -123,7 +123,10 @@ class VectorIndex:
     to ``ivf_threshold`` vectors, IVF-Flat above it and IVF-PQ (``search/ivfpq.py``, m=96 x 8 bit)
     from ``ivfpq_threshold``; ``"flat"`` / ``"ivf"`` / ``"ivfpq"`` force a tier.  ``"ivfsq8"`` (never picked by
     ``"auto"``) is IVF with a list-sorted int8 copy in place of the list-sorted bf16 one (``search/sq8.py``): 3 D bytes
-    per vector, the ``refine * k`` best int8 scores re-ranked exactly from the stored rows on the device."""
+    per vector, the ``refine * k`` best int8 scores re-ranked exactly from the stored rows on the device.
+    ``"flatsq8"`` (never picked by ``"auto"`` either) is the flat tier over an id-ordered int8 copy next to the bf16
+    rows (``csrc/kernels/flat_sq8_scan_topk.hip``): no lists, every row scored by an int8 MFMA scan, the same re-rank;
+    ``3 D + 4`` bytes per vector, so it buys speed and no memory."""
 
     def __init__(self, dim: int = 768, device=None, ivf_threshold: int = 5_000_000, nprobe: int = 64,
                  index_type: str = "auto", ivfpq_threshold: int = 50_000_000, pq_m: int = 96, refine: int = 4,
@@ -134,7 +137,8 @@ class VectorIndex:
         if flat_search not in FLAT_SEARCHES:
             raise ValueError(f"flat_search must be one of {FLAT_SEARCHES}")
         self.lvecs: torch.Tensor | None = None
-        self.sq_codes: torch.Tensor | None = None  # "ivfsq8": list-sorted int8 codes [N, D] and fp32 scales [N]
+        # int8 codes [N, D] and fp32 scales [N]: list-sorted ("ivfsq8") or in id order ("flatsq8")
+        self.sq_codes: torch.Tensor | None = None
         self.sq_scales: torch.Tensor | None = None
         self.dim = dim
         self.refine = refine  # IVF-PQ, IVF-SQ8: re-rank refine*k candidates with the stored vectors (0 = off)
@@ -159,13 +163,13 @@ class VectorIndex:
         self.fused_ivf_search(1, 1)  # "fused" where the kernels cannot run: raise now, not at the first query
         self.flat_search = flat_search  # flat tier: "auto", "gemm" or "fused" (csrc/kernels/flat_scan_topk.hip)
         self.fused_flat_search(1, 1)  # the same rule
-        if index_type == "ivfsq8":  # the tier has no other path: the same rule
+        if index_type in ("ivfsq8", "flatsq8"):  # the tiers have no other path: the same rule
             from ..ops import _native
             from .sq8 import SQ8_CH, sq8_dim_ok
 
             if not (self.device.type == "cuda" and _native.hip_available() and sq8_dim_ok(dim)):
-                raise _native.NativeUnavailable(f"index_type='ivfsq8' needs a GPU device, the native kernel library and "
-                                                f"dim / 256 in {SQ8_CH}")
+                raise _native.NativeUnavailable(f"index_type='{index_type}' needs a GPU device, the native kernel "
+                                                f"library and dim / 256 in {SQ8_CH}")
 
     def fused_ivf_search(self, Q: int, k: int) -> bool:
         """Whether an IVF-Flat search of ``Q`` queries for ``k`` results runs on ``ivf_scan_topk.hip``.  ``"fused"``:
@@ -215,7 +219,9 @@ class VectorIndex:
             return self.pq.index_type
         if self.centroids is not None and self.kind == "ivfsq8":
             return f"IVFSQ8-GPU(nlist={self.centroids.shape[0]})"
-        return f"IVFFlat-GPU(nlist={self.centroids.shape[0]})" if self.centroids is not None else "FlatIP-GPU"
+        if self.centroids is not None:
+            return f"IVFFlat-GPU(nlist={self.centroids.shape[0]})"
+        return "FlatSQ8-GPU" if self.kind == "flatsq8" else "FlatIP-GPU"
 
     def add(self, x) -> None:
         x = torch.as_tensor(np.asarray(x, np.float32) if not torch.is_tensor(x) else x).to(self.device, self.dtype)
@@ -223,6 +229,8 @@ class VectorIndex:
         self.vecs = torch.cat([self.vecs, x.to(self.vecs.device)], 0)
         if self.pq is not None:
             self.pq.add(x.float())
+        elif self.kind == "flatsq8":  # the new rows' codes alone: a row's code does not depend on the others
+            self._encode_flat_sq8(self.ntotal - x.shape[0])
         elif self.kind == "ivfpq" or (self.kind == "auto" and self.ntotal >= self.ivfpq_threshold
                                        and not self._fits_hbm(self.ntotal)):
             self.train_ivfpq()
@@ -230,6 +238,15 @@ class VectorIndex:
             self._assign_new(x, self.ntotal - x.shape[0])
         elif self.kind in ("ivf", "ivfsq8") or (self.kind == "auto" and self.ntotal >= self.ivf_threshold):
             self.train_ivf()
+
+    def _encode_flat_sq8(self, base: int) -> None:
+        """``"flatsq8"``: the id-ordered codes of the stored rows from ``base`` on, appended to those before them."""
+        from .sq8 import sq8_encode
+
+        codes, scales = sq8_encode(self.vecs[base:], None)
+        if base:
+            codes, scales = torch.cat([self.sq_codes[:base], codes]), torch.cat([self.sq_scales[:base], scales])
+        self.sq_codes, self.sq_scales = codes, scales
 
     def _fits_hbm(self, n: int) -> bool:
         """The exact-scan IVF tier keeps the vectors twice (id order + list-sorted): use it while
@@ -353,7 +370,9 @@ class VectorIndex:
             S[:, : ts.shape[1]] = ts.cpu().numpy()
             I[:, : ids.shape[1]] = ids.cpu().numpy()
             return S, I
-        if self.centroids is None and self.fused_flat_search(Q, k_eff):  # scan and selection in HIP
+        if self.kind == "flatsq8":
+            best_s, best_i = self._search_flat_sq8(q, k_eff)
+        elif self.centroids is None and self.fused_flat_search(Q, k_eff):  # scan and selection in HIP
             best_s, best_i = flat_scan_topk_fused(q, self.vecs, k_eff)
         elif self.centroids is None:
             best_s = torch.full((Q, 0), -float("inf"), device=self.device)
@@ -436,6 +455,18 @@ class VectorIndex:
                                        kk)
         return self._rerank(q, c, k) if self.refine else (s, c)
 
+    def _search_flat_sq8(self, q: torch.Tensor, k: int):
+        """The flat SQ8 tier: the best ``min(refine * k, 256)`` int8 scores of all rows
+        (``csrc/kernels/flat_sq8_scan_topk.hip``), re-scored exactly from ``self.vecs`` and cut to ``k``;
+        ``refine == 0``: the ``k`` best int8 scores as they are."""
+        from ..ops import _native
+
+        if k > FLAT_SQ8_MAX_K:
+            raise _native.NativeUnavailable(f"index_type='flatsq8' keeps at most {FLAT_SQ8_MAX_K} results per query")
+        kk = min(self.refine * k, FLAT_SQ8_MAX_K) if self.refine else k
+        s, c = flat_sq8_scan_topk_fused(q.float(), self.sq_codes, self.sq_scales, kk)
+        return self._rerank(q, c, k) if self.refine else (s, c)
+
     def reconstruct_batch(self, ids) -> np.ndarray:
         return self.vecs[torch.as_tensor(np.asarray(ids), device=self.vecs.device)].float().cpu().numpy()
 
@@ -456,6 +487,7 @@ class VectorIndex:
         info = {"n_cells": self.ntotal, "embed_dim": self.dim, "index_type": self.index_type,
                 "host_refine": self.host_refine, "refine": self.refine,
                 **({"sq8": True} if self.kind == "ivfsq8" and self.pq is None else {}),
+                **({"flat_sq8": True} if self.kind == "flatsq8" and self.pq is None else {}),
                 "index_size_mb": round((out / "vectors.npy").stat().st_size / 2 ** 20, 3),
                 "build_seconds": round(time.time() - t0, 3),
                 "build_time_iso": time.strftime("%Y-%m-%dT%H:%M:%SZ", time.gmtime())}
@@ -472,9 +504,9 @@ class VectorIndex:
         v = np.load(p)  # allow_pickle=False
         ii = out / "index_info.json"
         info = json.loads(ii.read_text()) if ii.exists() else {}
-        # "sq8": the int8 codes are a function of vectors.npy and are rebuilt by _assign_new below
+        # "sq8" / "flat_sq8": the int8 codes are a function of vectors.npy and are rebuilt below
         idx = cls(dim=v.shape[1], device=device, pq_search=pq_search, ivf_search=ivf_search, flat_search=flat_search,
-                  index_type="ivfsq8" if info.get("sq8") else "auto")
+                  index_type="ivfsq8" if info.get("sq8") else "flatsq8" if info.get("flat_sq8") else "auto")
         host = bool(info.get("host_refine")) and (out / "ivfpq_info.json").exists()
         idx.vecs = torch.from_numpy(v.astype(np.float32)).to("cpu" if host else idx.device, idx.dtype)
         if (out / "ivfpq_info.json").exists():
@@ -486,8 +518,10 @@ class VectorIndex:
             idx.pq_m = idx.pq.m
             return idx
         c = out / "ivf_centroids.npy"
-        if info.get("sq8"):
+        if info.get("sq8") or info.get("flat_sq8"):
             idx.refine = int(info.get("refine", idx.refine))
+        if idx.kind == "flatsq8" and idx.ntotal:
+            idx._encode_flat_sq8(0)
         if c.exists():
             idx.centroids = torch.from_numpy(np.load(c)).to(idx.device, idx.dtype)
             idx.assign = torch.empty(0, dtype=torch.int32, device=idx.device)

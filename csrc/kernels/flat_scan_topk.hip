@@ -5,7 +5,8 @@
 // The ranges' partial lists [Q, P, kk] are joined by be_topk_merge (topk_merge.hip), called without an id table.
 //
 // Order everywhere: (score descending, row ascending), the 64-bit keys of topk_select.h (make_key, key_score,
-// write_topk are used from it unchanged; the bitonic reselect is not: see "Selection").
+// write_topk are used from it unchanged; the bitonic reselect is not: see "Selection").  The selection code is in
+// flat_select.h, shared with flat_sq8_scan_topk.hip.
 //
 // be_flat_scan_topk, MI355X design:
 //  * Work split.  grid.x = P contiguous ranges of 256-row tiles (tile t of range p: p T / P <= t < (p + 1) T / P),
@@ -55,48 +56,11 @@
 //  vmcnt(0) before the first of the two fetches, because it reuses registers of that set for addresses, so every
 //  second stage is requested only once the stage before it has arrived.
 #include "common.h"
-#include "topk_select.h"
+#include "flat_select.h"
 
 namespace {
 
-constexpr int NT = 256, TILE = 256, FLAT_MAX_K = 256, CAP_MAX = 320;
-constexpr int LDS_BUDGET = 160 * 1024 - 256;
-
-constexpr int flat_lds_bytes(int qr, int D, int cap) { return qr * D * 2 + qr * (cap * 8 + 12); }
-
-// One wave sorts the min(cnt, cap) keys of one query's list in place by rank counting, keeps the first kk and
-// refreshes the threshold.  NS: list slots per lane.
-template <int NS>
-__device__ __forceinline__ void rank_select(key_t* buf, key_t* thr, int* cnt, int cap, int kk, int lane) {
-  int c = *cnt;
-  c = c < cap ? c : cap;
-  key_t k[NS];
-  int rank[NS];
-#pragma unroll
-  for (int j = 0; j < NS; ++j) {
-    k[j] = lane + 64 * j < c ? buf[lane + 64 * j] : KEY_PAD;
-    rank[j] = 0;
-  }
-  // four keys per step, so that their LDS reads are in flight together (cap is a multiple of 8: a step may read
-  // past c, never past the list; what it reads there is not counted)
-  for (int t0 = 0; t0 < c; t0 += 4) {
-    key_t w[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) w[u] = buf[t0 + u];
-#pragma unroll
-    for (int u = 0; u < 4; ++u)
-#pragma unroll
-      for (int j = 0; j < NS; ++j) rank[j] += (t0 + u < c && w[u] < k[j]) ? 1 : 0;
-  }
-  __builtin_amdgcn_wave_barrier();  // every lane has read the list before any lane rewrites it
-#pragma unroll
-  for (int j = 0; j < NS; ++j) {
-    const bool has = lane + 64 * j < c;
-    if (has && rank[j] < kk) buf[rank[j]] = k[j];
-    if (has && c >= kk && rank[j] == kk - 1) *thr = k[j];
-  }
-  if (lane == 0) *cnt = c < kk ? c : kk;
-}
+constexpr int flat_lds_bytes(int qr, int D, int cap) { return qr * D * 2 + flat_lists_bytes(qr, cap); }
 
 template <int QT>
 __global__ __launch_bounds__(NT, 1) void flat_scan_topk_kernel(const bf16_t* __restrict__ q,
@@ -106,9 +70,7 @@ __global__ __launch_bounds__(NT, 1) void flat_scan_topk_kernel(const bf16_t* __r
   constexpr int QR = 16 * QT;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   unsigned char* img = smem;
-  key_t* keys = reinterpret_cast<key_t*>(smem + (size_t)QR * D * 2);
-  key_t* thr = keys + QR * cap;
-  int* cnt = reinterpret_cast<int*>(thr + QR);
+  const FlatLists lists(smem + (size_t)QR * D * 2, QR, cap, kk);
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int fr = lane & 15, fg = lane >> 4;
@@ -131,10 +93,7 @@ __global__ __launch_bounds__(NT, 1) void flat_scan_topk_kernel(const bf16_t* __r
     if (r < nq) v = *reinterpret_cast<const u32x4*>(q + (size_t)(qbase + r) * D + j * 8);
     *reinterpret_cast<u32x4*>(img + (((j >> 2) * QR + r) << 6) + (((j & 3) ^ ((r >> 2) & 3)) << 4)) = v;
   }
-  for (int r = tid; r < QR; r += NT) {
-    thr[r] = KEY_PAD;
-    cnt[r] = 0;
-  }
+  lists.clear(QR, tid);
   __syncthreads();
 
   const int S = (KS + 3) >> 2;  // stages of a tile
@@ -188,54 +147,7 @@ __global__ __launch_bounds__(NT, 1) void flat_scan_topk_kernel(const bf16_t* __r
 
   // the complete accumulators of the tile at row0 are offered to the queries' lists
   auto offer = [&](int row0) {
-    const int rbase = row0 + wave * 64 + 4 * fg;
-    unsigned todo[QT];
-#pragma unroll
-    for (int t = 0; t < QT; ++t) {
-      todo[t] = 0;
-      if (16 * t + fr < nq) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-          for (int e = 0; e < 4; ++e)
-            if (rbase + 16 * i + e < N) todo[t] |= 1u << (i * 4 + e);
-      }
-    }
-    for (;;) {
-      unsigned open = 0;
-#pragma unroll
-      for (int t = 0; t < QT; ++t) {
-        if (!todo[t]) continue;
-        const int qq = 16 * t + fr;
-        const key_t th = thr[qq];
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const unsigned bit = 1u << (i * 4 + e);
-            if (!(todo[t] & bit)) continue;
-            const key_t key = make_key(acc[i][t][e], rbase + 16 * i + e);
-            if (key < th) {
-              const int pos = atomicAdd(&cnt[qq], 1);
-              if (pos < cap) {
-                keys[qq * cap + pos] = key;
-                todo[t] &= ~bit;
-              }
-            } else {
-              todo[t] &= ~bit;
-            }
-          }
-        open |= todo[t];
-      }
-      // a bit is left only where a query had no slot: that list is at cap and is re-selected to kk < cap
-      if (!__syncthreads_or(open != 0)) break;
-      for (int qq = wave; qq < nq; qq += 4) {
-        if (__builtin_amdgcn_readfirstlane(cnt[qq]) < cap) continue;
-        if (cap <= 128) rank_select<2>(keys + qq * cap, thr + qq, cnt + qq, cap, kk, lane);
-        else rank_select<CAP_MAX / 64>(keys + qq * cap, thr + qq, cnt + qq, cap, kk, lane);
-      }
-      __syncthreads();
-    }
+    flat_offer<QT>(lists, nq, N, row0, wave, lane, [&](int i, int t, int e) { return acc[i][t][e]; });
   };
 
   // ---- the sweep: two register sets that swap roles (a copy between them would wait for the loads just issued)
@@ -278,26 +190,16 @@ __global__ __launch_bounds__(NT, 1) void flat_scan_topk_kernel(const bf16_t* __r
   }
 
   // ---- every list sorted (the vote that ended the last offer is the barrier before this), and written
-  for (int qq = wave; qq < nq; qq += 4) {
-    key_t* buf = keys + qq * cap;
-    if (cap <= 128) rank_select<2>(buf, thr + qq, cnt + qq, cap, kk, lane);
-    else rank_select<CAP_MAX / 64>(buf, thr + qq, cnt + qq, cap, kk, lane);
-    __builtin_amdgcn_wave_barrier();
-    write_topk<64, int>(buf, cnt[qq], kk, lane, out_s + out_of(qq), out_r + out_of(qq), nullptr);
-  }
+  flat_finish(lists, nq, wave, lane, out_of, out_s, out_r);
 }
 
 template <int QT>
 int launch_flat(const bf16_t* q, const bf16_t* vecs, int N, int Q, int D, int kk, int P, float* part_s, int* part_r,
                 hipStream_t s) {
   constexpr int QR = 16 * QT;
-  int want = 2 * kk + 16 < CAP_MAX ? 2 * kk + 16 : CAP_MAX;
-  want = want > kk + 16 ? want : kk + 16;
-  const long long room = ((long long)LDS_BUDGET - (long long)QR * D * 2) / QR;  // bytes per query for its list
-  long long cap = (room - 12) / 8;
-  if (room < 12 || (cap & ~7LL) < kk + 16) return -8;
-  cap = (cap < want ? cap : want) & ~7LL;  // rank_select reads the list four keys at a time
-  const int lds = flat_lds_bytes(QR, D, (int)cap);
+  const int cap = flat_cap(QR, (long long)QR * D * 2, kk);
+  if (!cap) return -8;
+  const int lds = flat_lds_bytes(QR, D, cap);
   static bool attr[BE_MAX_DEV] = {};
   if (!attr[be_cur_dev()]) {
     if (hipFuncSetAttribute((const void*)flat_scan_topk_kernel<QT>, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -306,7 +208,7 @@ int launch_flat(const bf16_t* q, const bf16_t* vecs, int N, int Q, int D, int kk
     attr[be_cur_dev()] = true;
   }
   const dim3 grid((unsigned)P, (unsigned)((Q + QR - 1) / QR));
-  hipLaunchKernelGGL(flat_scan_topk_kernel<QT>, grid, dim3(NT), lds, s, q, vecs, N, Q, D, kk, (int)cap, P, part_s, part_r);
+  hipLaunchKernelGGL(flat_scan_topk_kernel<QT>, grid, dim3(NT), lds, s, q, vecs, N, Q, D, kk, cap, P, part_s, part_r);
   return BE_CHECK_LAUNCH();
 }
 

@@ -78,6 +78,10 @@ PER_SOURCE_FLAGS = {"clahe": ["-ffp-contract=off"], "attention": ["-mllvm", "-am
                     "ivf_sq8": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
                     # flat_scan_topk: the same, for the key packing and the rank counting of the selection
                     "flat_scan_topk": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+                    # flat_sq8_scan_topk: the same; and its query split (t = q * inv, then t - h) and its score
+                    # (H + L * 2^-8) are the float32 oracle's separately rounded operations, never an fma
+                    "flat_sq8_scan_topk": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops",
+                                           "-ffp-contract=off"],
                     # topk_merge: the same, it is built on the scans' selection header
                     "topk_merge": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
                     # coarse_assign: the same, for the loader's hi / lo split and the selection epilogue

@@ -25,6 +25,8 @@ against ``ivf_search="fused"`` (``--ivf-search-only`` prints these lines alone).
 ``index_type="ivfsq8"`` on the same centroids (:func:`sq8_times`).
 ``--flat-search-only`` prints one ``"stage": "flat_search"`` line per (N, Q, k): the flat tier's ``VectorIndex.search``
 with ``flat_search="gemm"`` against ``flat_search="fused"`` (:func:`flat_search_times`); the full run prints them too.
+``--flat-sq8-only`` prints one ``"stage": "flat_sq8"`` line per (N, Q, k): the flat tier with ``flat_search="fused"``
+against ``index_type="flatsq8"`` over the same rows (:func:`flat_sq8_times`).
 Usage: ``python tools/search_bench.py --n 10000000,58000000``
 """
 import argparse
@@ -357,6 +359,55 @@ def flat_search_times(x, q, qs=(1, 64), ks=(20, 100), reps=20, hbm_tbps=8.0):
     return out
 
 
+def flat_sq8_times(x, q, qs=(1, 16, 32, 64), ks=(20, 100), reps=20, hbm_tbps=8.0):
+    """The flat tier over the bf16 rows ``x`` behind ``flat_search="fused"`` against ``index_type="flatsq8"`` with
+    ``refine`` 0 and 4 over the same rows (``csrc/kernels/flat_sq8_scan_topk.hip``), all through :func:`_alternate`
+    (median, spread = 90th - 10th percentile): the encode, then per (Q, k) the whole ``search`` call of the three arms,
+    the two scans alone (kernel + merge, ``kk = k``), alternating with each other, the bytes each streams (once per
+    query group; ``N (D + 4)`` for SQ8) over that time as a share of ``hbm_tbps``, the ratio of the row rates, and the
+    SQ8 arms' recall@k against the bf16 arm's ids.  One ``"stage": "flat_sq8"`` dict per (Q, k)."""
+    from bioengine_worker_amd.search.flat import (flat_group, flat_scan_topk_fused, flat_sq8_group,
+                                                  flat_sq8_scan_topk_fused)
+    from bioengine_worker_amd.search.index import VectorIndex
+    from bioengine_worker_amd.search.sq8 import sq8_encode
+
+    n, d = int(x.shape[0]), int(x.shape[1])
+    enc = _alternate({"encode": lambda: sq8_encode(x, None)}, 3)["encode"]
+    codes, scales = enc[2]
+    arms = {"bf16": VectorIndex(dim=d, device=x.device, index_type="flat", flat_search="fused"),
+            "sq8_r0": VectorIndex(dim=d, device=x.device, index_type="flatsq8", refine=0),
+            "sq8_r4": VectorIndex(dim=d, device=x.device, index_type="flatsq8", refine=4)}
+    for name, idx in arms.items():
+        idx.vecs = x
+        if name != "bf16":
+            idx.sq_codes, idx.sq_scales = codes, scales
+    out = []
+    for Q in qs:
+        qq = q[:Q].to(x.dtype)
+        qf = qq.float()
+        for k in ks:
+            ts = _alternate({a: (lambda idx=idx: idx.search(qq, k)) for a, idx in arms.items()}, reps, pct=True)
+            sc = _alternate({"bf16": lambda: flat_scan_topk_fused(qq, x, k),
+                             "sq8": lambda: flat_sq8_scan_topk_fused(qf, codes, scales, k)}, reps, pct=True)
+            groups = {"bf16": -(-Q // flat_group(Q, d, k)), "sq8": -(-Q // flat_sq8_group(Q, d, k))}
+            nbytes = {"bf16": groups["bf16"] * n * d * 2, "sq8": groups["sq8"] * n * (d + 4)}
+            line = {"n": n, "dim": d, "stage": "flat_sq8", "Q": Q, "k": k, "encode_ms": round(enc[0], 3),
+                    "encode_spread_ms": round(enc[1], 3)}
+            for a in arms:
+                line.update({f"{a}_ms": round(ts[a][0], 3), f"{a}_spread_ms": round(ts[a][1], 3)})
+            for a in sc:
+                line.update({f"scan_{a}_ms": round(sc[a][0], 3), f"scan_{a}_spread_ms": round(sc[a][1], 3),
+                             f"scan_{a}_groups": groups[a], f"scan_{a}_bytes": nbytes[a],
+                             f"scan_{a}_tbps": round(nbytes[a] / sc[a][0] * 1e-9, 2),
+                             f"scan_{a}_share_of_hbm_peak": round(nbytes[a] / sc[a][0] * 1e-9 / hbm_tbps, 3)})
+            line["scan_bf16_over_sq8"] = round(sc["bf16"][0] / sc["sq8"][0], 2)
+            gt = ts["bf16"][2][1]
+            for a in ("sq8_r0", "sq8_r4"):
+                line[f"recall@{k}_{a}"] = round(float(np.mean([len(set(g) & set(r)) / k for g, r in zip(gt, ts[a][2][1])])), 4)
+            out.append(line)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", default="1000000,10000000")
@@ -377,7 +428,8 @@ def main():
     ap.add_argument("--sq8-only", action="store_true", help="only the sq8 lines (fused IVF-Flat against IVF-SQ8)")
     ap.add_argument("--pq-build-only", action="store_true", help="only the pq_build line (build and coarse arms)")
     ap.add_argument("--flat-search-only", action="store_true", help="only the flat_search lines (gemm against fused)")
-    ap.add_argument("--flat-ks", default="20,100", help="the flat_search lines' k values")
+    ap.add_argument("--flat-sq8-only", action="store_true", help="only the flat_sq8 lines (fused bf16 flat against flatsq8)")
+    ap.add_argument("--flat-ks", default="20,100", help="the flat_search and flat_sq8 lines' k values")
     a = ap.parse_args()
     from bioengine_worker_amd.search.index import VectorIndex
     from bioengine_worker_amd.search.ivfpq import IVFPQIndex, default_nlist
@@ -402,6 +454,13 @@ def main():
         if a.flat_search_only:  # the flat_search lines alone; the two arms are compared with each other
             for line in flat_search_times(x, next(iter(qsets.values())), ks=[int(v) for v in a.flat_ks.split(",")],
                                           reps=a.reps):
+                print(json.dumps(line), flush=True)
+            del x
+            torch.cuda.empty_cache()
+            continue
+        if a.flat_sq8_only:  # the flat_sq8 lines alone; the reference is the fused bf16 arm
+            for line in flat_sq8_times(x, next(iter(qsets.values())), ks=[int(v) for v in a.flat_ks.split(",")],
+                                       reps=a.reps):
                 print(json.dumps(line), flush=True)
             del x
             torch.cuda.empty_cache()
